@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — frames/sec of the HDN homography hot path on MI355X + roofline of the correlation kernel.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -18,7 +18,10 @@ Pairs are independent, so ranks hold disjoint batches (weak scaling) and `value`
 Before the W warm-up steps the GPU is kept busy for --prewarm-ms (150 ms, untimed, rank-local): from idle an MI355X needs
 ~40 ms of sustained load to reach steady clocks, and the first ~80 steps would otherwise be timed on the ramp.
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit, higher_is_better, dtype,
+ms_per_step, the run's parameters and config).  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy
+(see dump_outputs).  With --full the JSON line also carries the blocks below (each --no-* switch drops one of them again), and
+N > 1 runs the "collective" audit block:
     "roofline"      for the dominant kernel (the 31x31 (x) 61x61 correlation), measured with events on the launch stream around every
                     launch of the TIMED region (mean / min / median); with a --head-stream other than the default, in
                     --roofline-steps separate after-north steps behind it
@@ -60,6 +63,9 @@ CIRC_BYTES_PER_PAIR = 4 * C * 3 * 13 * 13                         # 519,168
 SF_BYTES_PER_IMG = 2 * 4 * 127 * 127                              # 129,032
 WARP_BYTES_PER_PAIR = 2 * 4 * 127 * 127 + 64 + 36                 # 129,132
 
+DUMP_SAMPLE = 1 << 19                  # --dump-outputs: elements kept of a larger array (a fixed, seeded sample)
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000   # --dump-outputs: all files together
+
 
 def parse():
     ap = argparse.ArgumentParser()
@@ -98,7 +104,48 @@ def parse():
     ap.add_argument("--workload", choices=["kernels", "full"], default="kernels",
                     help="kernels = BASELINE configs[1] (default); full = configs[2]: the whole HomoModelBuilder head "
                          "incl. the PyTorch-ROCm ResNet-34 trunk on 64 pairs per GPU, then the offsets all-gather")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check everything else: roofline of the dominant kernel, per-kernel breakdown, "
+                         "full_head, sequence, CPU baselines, the N > 1 collective audit (off by default: a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32 / float64; arrays of more "
+                         "than %d elements as a fixed, seeded sample of them)" % DUMP_SAMPLE)
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
+
+
+def _keep(keep, name, value):
+    """The last timed step hands its results to `keep` (--dump-outputs); every other step drops them as soon as they are launched."""
+    if keep is not None:
+        keep[name] = value
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: the arrays the timed path returned in its last step -> out_dir/<name>.npy, float32 (float64 stays float64); a list
+    or tuple of arrays -> <name>_0, <name>_1, ...  An array of more than DUMP_SAMPLE elements is written as a sample of its flattened
+    elements at sorted indices drawn from a generator seeded with SEED and the element count: the same indices in every run, so two builds
+    can be compared output for output.  Inputs are seeded, so the same arguments give the same inputs."""
+    flat = {}
+    for name, v in arrays.items():
+        if isinstance(v, (list, tuple)):
+            flat.update({"%s_%d" % (name, i): t for i, t in enumerate(v)})
+        else:
+            flat[name] = v
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in flat.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng([SEED, t.numel()]).choice(t.numel(), DUMP_SAMPLE, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        a = t.cpu().numpy()
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        total += a.nbytes
+        if total > DUMP_BUDGET_BYTES:
+            raise SystemExit("bench.py: --dump-outputs would write more than %d bytes" % DUMP_BUDGET_BYTES)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def make_inputs(dev, rank):
@@ -226,26 +273,30 @@ def main():
     if args.workload == "full":
         full_net, full_data, full_cpu_sd = build_full()
 
-    def step_full(record, collective):
+    def step_full(record, collective, keep=None):
         st = homo_stages(full_net, full_data)
+        if keep is not None:
+            keep.update(st)
         if world > 1 and collective:
-            hdist.all_gather_offsets(st["x"], PAIRS * world, comm=comm)
+            _keep(keep, "x_gathered", hdist.all_gather_offsets(st["x"], PAIRS * world, comm=comm))
 
     # HDN_BENCH_HEAD_PRIORITY (A/B switch, tools/experiments/ab_priority.sh): queue priority of the head stream relative to the
     # correlation stream (torch: lower number = higher priority)
     _prio = os.environ.get("HDN_BENCH_HEAD_PRIORITY")
     head_stream = torch.cuda.Stream(device=dev) if _prio is None else torch.cuda.Stream(device=dev, priority=int(_prio))
 
-    def step(record, collective=True, mode=None, sink=None):
+    def step(record, collective=True, mode=None, sink=None, keep=None):
         if args.workload == "full":
-            return step_full(record, collective)
+            return step_full(record, collective, keep)
         main = torch.cuda.current_stream()
 
         def head():
             feats = SF.share_feature(imgs2, folded).reshape(PAIRS, 2, 127, 127)
             Hm, warped = G.dlt_warp(d["h4p"], d["off"], tmpl)
             pf = SF.share_feature(warped, folded)
-            G.l1_score2(feats[0, 1], pf[0, 0], feats[0, 0], 1.0 / (127 * 127))
+            _keep(keep, "l1_scores", G.l1_score2(feats[0, 1], pf[0, 0], feats[0, 0], 1.0 / (127 * 127)))
+            if keep is not None:
+                keep.update(share_feature_pairs=feats, dlt_warp_H=Hm, dlt_warp_warped=warped, share_feature_warped=pf)
 
         def fork_head(after=None):
             # `after`: the 31x31 launch's own stop event (launch-carried brackets): the head stream waits for THAT, and the main stream gets no marker
@@ -258,7 +309,7 @@ def main():
             with torch.cuda.stream(head_stream):
                 head()
                 if world > 1 and collective:  # the head's results are gathered while the correlation stream is still busy
-                    hdist.all_gather_offsets(d["off"], PAIRS * world, comm=comm)
+                    _keep(keep, "offsets_gathered", hdist.all_gather_offsets(d["off"], PAIRS * world, comm=comm))
 
         # The step's two branches are independent, as in the tracker (similarity-branch correlations | homography head).
         # Rounds 2-3 (tools/experiments/exp_streams2.py): one stream 0.324 ms; head beside the 13x13 and 5x5 launches 0.317; head from
@@ -275,7 +326,7 @@ def main():
         elif record:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-        X.xcorr_depthwise(d["north_x"], d["north_k"])
+        _keep(keep, "xcorr_31x31_61x61", X.xcorr_depthwise(d["north_x"], d["north_k"]))
         if record:
             if bracket_mode != "launch":
                 e1.record()
@@ -286,14 +337,14 @@ def main():
         if mode == "after-north":
             fork_head(e1 if (record and bracket_mode == "launch") else None)
         # 13x13 before the write-heavy 5x5 (x) 29x29 launch: 2 % faster than the other way round (tools/experiments/exp_step_order.py)
-        X.xcorr_depthwise_multi(d["circ_x"], d["circ_k"], circular=True)
+        _keep(keep, "xcorr_circ_13x13", X.xcorr_depthwise_multi(d["circ_x"], d["circ_k"], circular=True))
         if mode == "inline":
             head()
-        X.xcorr_depthwise_multi(d["prod_x"], d["prod_k"])
+        _keep(keep, "xcorr_5x5_29x29", X.xcorr_depthwise_multi(d["prod_x"], d["prod_k"]))
         if mode != "inline" and join_every_step:
             main.wait_stream(head_stream)
         elif world > 1 and collective:
-            hdist.all_gather_offsets(d["off"], PAIRS * world, comm=comm)
+            _keep(keep, "offsets_gathered", hdist.all_gather_offsets(d["off"], PAIRS * world, comm=comm))
 
     def fence():
         torch.cuda.synchronize()
@@ -301,22 +352,35 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    def finish(result):
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+
     t_pre = time.perf_counter()
     while (time.perf_counter() - t_pre) * 1e3 < args.prewarm_ms:  # clock / power ramp from idle, untimed
         for _ in range(5):
             step(False, collective=False)  # wall-clock bounded, so rank-local: no collective in here
         torch.cuda.synchronize()
-    for _ in range(args.warmup + (5 if args.workload == "full" else 0)):
-        step(False)
+    n_warm = args.warmup + (5 if args.workload == "full" else 0)
+    kept = {}
+    for i_ in range(n_warm):
+        # --dump-outputs: the last warm-up step keeps its results as the last timed step will, so that the allocator's cache already
+        # holds blocks for them and the timed step allocates nothing new
+        step(False, keep=kept if (args.dump_outputs and i_ == n_warm - 1) else None)
     fence()
+    kept.clear()
     no_brackets = os.environ.get("HDN_BENCH_NO_BRACKETS") == "1"      # A/B switch (profiles/round6_experiments.txt section 3): what the event pairs cost the step
     t0 = time.perf_counter()
     every = max(1, int(os.environ.get("HDN_BENCH_BRACKET_EVERY", "1")))     # A/B switch: start + stop events on every N-th timed step only
     for i_ in range(args.steps):
-        step(False if no_brackets else (True if (i_ % every == 0 or bracket_mode != "launch") else "stop"))
+        step(False if no_brackets else (True if (i_ % every == 0 or bracket_mode != "launch") else "stop"),
+             keep=kept if (args.dump_outputs and i_ == args.steps - 1) else None)
     fence()
     elapsed = time.perf_counter() - t0
-    if no_brackets and args.workload != "full":
+    if no_brackets and args.workload != "full" and args.full:
         for _ in range(max(1, args.roofline_steps)):
             step(True, collective=False)
         torch.cuda.synchronize()
@@ -327,10 +391,13 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, kept)
+    kept.clear()
 
     if args.workload == "full":
         coll = None
-        if world > 1:
+        if world > 1 and args.full:
             x_local = homo_stages(full_net, full_data)["x"]
             coll = collective_block(x_local, dev, rank, world, dist, hdist, comm)
             if rank == 0:      # SURVEY 8d cfg 3: parity against the CPU on a 16-pair sample of this rank's shard
@@ -348,6 +415,40 @@ def main():
         if world > 1:
             dist.barrier()
             dist.destroy_process_group()
+        return
+    result = {
+        "metric": "frames/sec on 127/255 template/search pairs",
+        "value": PAIRS * world * args.steps / elapsed,
+        "unit": "frames/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "prewarm_ms": args.prewarm_ms,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,  # BASELINE.md: the reference publishes no number for this metric
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {
+            "workload": ("north-star correlation only" if args.only_north else
+                         "BASELINE configs[1]: batch=64 synthetic 127/255 pairs per GPU, 256-ch features; HIP kernels only: "
+                         "1x xcorr 31x31(x)61x61 + 6x xcorr 5x5(x)29x29 + 6x circular xcorr 13x13(x)13x13 + "
+                         "3x PreShareFeature 127x127 + fused DLT/warp + the 2 L1 scores (one launch)" + ((" + direct-write all-gather of [64,8] offsets (hdn_gather_offsets_oneshot)" if oneshot_used else " + RCCL all-gather of [64,8] offsets") if world > 1 else "")),
+            "pairs_per_gpu": PAIRS,
+            "channels": C,
+            "parallelism": f"pairs sharded over {world} GPU(s), no data-path collective except the offsets all-gather",
+            "streams": {"inline": "one stream",
+                        "after-north": "two streams: the homography head (PreShareFeature, DLT+warp, scores) runs beside the 13x13 and "
+                                       "5x5 correlation launches, the 31x31 launch alone (kernel durations of the two streams overlap: "
+                                       "their sum exceeds the step)",
+                        "parallel": "two streams: the homography head (PreShareFeature, DLT+warp, scores) runs beside all three correlation "
+                                    "launches from the start of the step (kernel durations of the two streams overlap: their sum exceeds the step)"}[
+                            "inline" if args.only_north else args.head_stream],
+        },
+    }
+    if not args.full:
+        finish(result)
         return
     # Roofline of the 31x31 (x) 61x61 kernel: HIP events on its launch stream around the launch.  Under the default schedule
     # (after-north: the head stream is forked behind that launch, which therefore has the chip to itself) the brackets of the
@@ -400,63 +501,32 @@ def main():
         raise SystemExit("bench.py: no committed PMC traffic measurement under profiles/*_pmc_hbm_traffic.json names the kernel the "
                          "roofline block times (" + north_kernel + "); run tools/profile_round.sh and commit its output")
 
-    result = {
-        "metric": "frames/sec on 127/255 template/search pairs",
-        "value": PAIRS * world * args.steps / elapsed,
-        "unit": "frames/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "prewarm_ms": args.prewarm_ms,
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,  # BASELINE.md: the reference publishes no number for this metric
-        "dtype": "f32",
-        "data": "synthetic",
-        "config": {
-            "workload": ("north-star correlation only" if args.only_north else
-                         "BASELINE configs[1]: batch=64 synthetic 127/255 pairs per GPU, 256-ch features; HIP kernels only: "
-                         "1x xcorr 31x31(x)61x61 + 6x xcorr 5x5(x)29x29 + 6x circular xcorr 13x13(x)13x13 + "
-                         "3x PreShareFeature 127x127 + fused DLT/warp + the 2 L1 scores (one launch)" + ((" + direct-write all-gather of [64,8] offsets (hdn_gather_offsets_oneshot)" if oneshot_used else " + RCCL all-gather of [64,8] offsets") if world > 1 else "")),
-            "pairs_per_gpu": PAIRS,
-            "channels": C,
-            "parallelism": f"pairs sharded over {world} GPU(s), no data-path collective except the offsets all-gather",
-            "streams": {"inline": "one stream",
-                        "after-north": "two streams: the homography head (PreShareFeature, DLT+warp, scores) runs beside the 13x13 and "
-                                       "5x5 correlation launches, the 31x31 launch alone (kernel durations of the two streams overlap: "
-                                       "their sum exceeds the step)",
-                        "parallel": "two streams: the homography head (PreShareFeature, DLT+warp, scores) runs beside all three correlation "
-                                    "launches from the start of the step (kernel durations of the two streams overlap: their sum exceeds the step)"}[
-                            "inline" if args.only_north else args.head_stream],
-        },
-        "roofline": {
-            "kernel": "hdn::%s (hdn_xcorr_depthwise_f32, 31x31 (x) 61x61, variant %s)" % (north_kernel, north_variant),
-            "bound": "hbm",
-            "achieved": north_gbps,
-            "peak": HBM_PEAK_GBPS,
-            "unit": "GB/s",
-            "frac": north_gbps / HBM_PEAK_GBPS,
-            "traffic": traffic,
-            "traffic_source": traffic_note,
-            "traffic_source_matches_kernel_source": traffic_fresh,   # None: the committed PMC file predates the source hash (round <= 4)
-            "algorithmic_bytes_per_launch": NORTH_BYTES_PER_PAIR * PAIRS,
-            "avg_launch_ms": north_ms,
-            "min_launch_ms": float(solo.min()),
-            "median_launch_ms": float(np.median(solo)),
-            "bracket": ("hipEvent pair carried by the launch itself (hipExtLaunchKernelGGL through hdn_xcorr_north_launch_events): the dispatch's start / end "
-                        "timestamps on its own stream" if bracket_mode == "launch" else "torch.cuda.Event pair recorded on the launch stream before / after the call"),
-            "timing": ("in-step, %d brackets: HIP events on the launch stream around every 31x31 launch of the timed region (after-north "
-                       "schedule: the head stream is forked behind that launch, it has the chip to itself); achieved / frac use the mean"
-                       % len(solo)) if timed_is_clean else
-                      ("in-step, %d brackets: HIP events on the launch stream around the 31x31 launch in %d separate steps run after the "
-                       "timed region with the head stream forked AFTER that launch (it has the chip to itself); achieved / frac use the mean"
-                       % (len(solo), len(solo))),
-            "timed_region_launch_ms": {"schedule": "inline" if args.only_north else args.head_stream, "mean": float(in_region.mean()),
-                                       "min": float(in_region.min()), "median": float(np.median(in_region)),
-                                       "note": "the brackets inside the timed region (identical to the above under the default schedule; under "
-                                               "the parallel schedule the kernel shares the chip with the homography head there)"},
-        },
+    result["roofline"] = {
+        "kernel": "hdn::%s (hdn_xcorr_depthwise_f32, 31x31 (x) 61x61, variant %s)" % (north_kernel, north_variant),
+        "bound": "hbm",
+        "achieved": north_gbps,
+        "peak": HBM_PEAK_GBPS,
+        "unit": "GB/s",
+        "frac": north_gbps / HBM_PEAK_GBPS,
+        "traffic": traffic,
+        "traffic_source": traffic_note,
+        "traffic_source_matches_kernel_source": traffic_fresh,   # None: the committed PMC file predates the source hash (round <= 4)
+        "algorithmic_bytes_per_launch": NORTH_BYTES_PER_PAIR * PAIRS,
+        "avg_launch_ms": north_ms,
+        "min_launch_ms": float(solo.min()),
+        "median_launch_ms": float(np.median(solo)),
+        "bracket": ("hipEvent pair carried by the launch itself (hipExtLaunchKernelGGL through hdn_xcorr_north_launch_events): the dispatch's start / end "
+                    "timestamps on its own stream" if bracket_mode == "launch" else "torch.cuda.Event pair recorded on the launch stream before / after the call"),
+        "timing": ("in-step, %d brackets: HIP events on the launch stream around every 31x31 launch of the timed region (after-north "
+                   "schedule: the head stream is forked behind that launch, it has the chip to itself); achieved / frac use the mean"
+                   % len(solo)) if timed_is_clean else
+                  ("in-step, %d brackets: HIP events on the launch stream around the 31x31 launch in %d separate steps run after the "
+                   "timed region with the head stream forked AFTER that launch (it has the chip to itself); achieved / frac use the mean"
+                   % (len(solo), len(solo))),
+        "timed_region_launch_ms": {"schedule": "inline" if args.only_north else args.head_stream, "mean": float(in_region.mean()),
+                                   "min": float(in_region.min()), "median": float(np.median(in_region)),
+                                   "note": "the brackets inside the timed region (identical to the above under the default schedule; under "
+                                           "the parallel schedule the kernel shares the chip with the homography head there)"},
     }
     # The in-step brackets see the kernel at the step's duty cycle (~1/3 of the time; the chip cools between launches).  Ten launches
     # back to back inside one hipGraph show what it sustains (round 4: 110 us = 0.42 against 92 us = 0.50 in the step): both are reported.
@@ -514,11 +584,7 @@ def main():
         result["sequence"] = sequence_block(args.sequence_frames, dev, args.multi_sequence)
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(d, sf_cpu_sd)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
-    if rank == 0:
-        print(json.dumps(result), flush=True)
+    finish(result)
 
 
 def collective_block(x_local, dev, rank, world, dist, hdist, comm):
@@ -591,11 +657,11 @@ def run_config5(args, dev, rank, world, dist, hdist, comm, sf, folded):
     Hc = torch.eye(3, dtype=torch.float64, device=dev).repeat(PAIRS, 1, 1).contiguous()
     ev = []
 
-    def step(record):
+    def step(record, keep=None):
         if record:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-        X.xcorr_depthwise_multi(xs, ks)
+        _keep(keep, "xcorr_5x5_35x35", X.xcorr_depthwise_multi(xs, ks))
         if record:
             e1.record()
             ev.append((e0, e1))
@@ -604,10 +670,13 @@ def run_config5(args, dev, rank, world, dist, hdist, comm, sf, folded):
             p2 = SF.share_feature(cur, folded)
             Hm, warped = G.dlt_warp(h4p, offs[it], tmpl)
             pf = SF.share_feature(warped, folded)
-            G.l1_score2(p2[0, 0], pf[0, 0], p1[0, 0], 1.0 / (127 * 127))
+            _keep(keep, "l1_scores_it%d" % it, G.l1_score2(p2[0, 0], pf[0, 0], p1[0, 0], 1.0 / (127 * 127)))
             cur = R.refine_warp(Hm, cur, Hc)
+            if keep is not None:
+                keep.update({"share_feature_search_it%d" % it: p2, "dlt_warp_H_it%d" % it: Hm, "dlt_warp_warped_it%d" % it: warped,
+                             "share_feature_warped_it%d" % it: pf, "refine_warp_it%d" % it: cur})
         if world > 1:
-            hdist.all_gather_offsets(offs[1], PAIRS * world, comm=comm)
+            _keep(keep, "offsets_gathered", hdist.all_gather_offsets(offs[1], PAIRS * world, comm=comm))
 
     def fence():
         torch.cuda.synchronize()
@@ -620,35 +689,42 @@ def run_config5(args, dev, rank, world, dist, hdist, comm, sf, folded):
         for _ in range(5):
             step(False) if world == 1 else X.xcorr_depthwise_multi(xs, ks)
         torch.cuda.synchronize()
-    for _ in range(args.warmup):
-        step(False)
+    kept = {}
+    for i_ in range(args.warmup):
+        step(False, keep=kept if (args.dump_outputs and i_ == args.warmup - 1) else None)   # (see main: the allocator's cache)
     fence()
+    kept.clear()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step(True)
+    for i_ in range(args.steps):
+        step(True, keep=kept if (args.dump_outputs and i_ == args.steps - 1) else None)
     fence()
     elapsed = time.perf_counter() - t0
     if world > 1:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
-    ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
-    nbytes = 6 * 4 * C * (35 * 35 + 25 + 31 * 31) * PAIRS
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, kept)
+    kept.clear()
+    result = {
+        "metric": "frames/sec on 127/255 template/search pairs", "value": PAIRS * world * args.steps / elapsed, "unit": "frames/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "BASELINE configs[4] per GPU (64 pairs = 256 over 4 GPUs), HIP kernels only: 6x xcorr 5x5(x)35x35 "
+                               "(303-px search window) + 2 refinement iterations x (PreShareFeature, fused DLT/warp, "
+                               "PreShareFeature, 2 scores, restated cv2.warpPerspective)", "pairs_per_gpu": PAIRS, "channels": C}}
+    if args.full:
+        ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
+        nbytes = 6 * 4 * C * (35 * 35 + 25 + 31 * 31) * PAIRS
+        result["roofline"] = {"kernel": "hdn::xcorr_cfg5_kernel x6 in one launch (" + X.last_variant() + ")", "bound": "hbm",
+                              "achieved": nbytes / (ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                              "frac": nbytes / (ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, "traffic": None,
+                              "algorithmic_bytes_per_launch": nbytes, "avg_launch_ms": ms}
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        print(json.dumps({
-            "metric": "frames/sec on 127/255 template/search pairs", "value": PAIRS * world * args.steps / elapsed, "unit": "frames/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "BASELINE configs[4] per GPU (64 pairs = 256 over 4 GPUs), HIP kernels only: 6x xcorr 5x5(x)35x35 "
-                                   "(303-px search window) + 2 refinement iterations x (PreShareFeature, fused DLT/warp, "
-                                   "PreShareFeature, 2 scores, restated cv2.warpPerspective)", "pairs_per_gpu": PAIRS, "channels": C},
-            "roofline": {"kernel": "hdn::xcorr_cfg5_kernel x6 in one launch (" + X.last_variant() + ")", "bound": "hbm",
-                         "achieved": nbytes / (ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": nbytes / (ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, "traffic": None,
-                         "algorithmic_bytes_per_launch": nbytes, "avg_launch_ms": ms}}), flush=True)
+        print(json.dumps(result), flush=True)
 
 
 def sequence_block(n_frames, dev, multi=""):

@@ -297,6 +297,68 @@ def gen_transform(ref_utils):
          img3=img3, theta3=th3.numpy(), y3=y3.numpy(), cond3=np.array(float(cond3)))
 
 
+def seeded_trunk_state_(m, tag=620):
+    """Fills every tensor of the ResNet-34 trunk's state_dict, in key order, from rng(tag): He-scaled convolution / linear weights,
+    BatchNorm statistics as seeded_bn_ draws them at a smaller gain (so that activations stay O(1) through the 16 blocks).  Depends on
+    the key names and shapes only, not on a constructor's init stream, so the reference's trunk and ours get the same weights."""
+    g = rng(tag)
+    sd = m.state_dict()
+    for k, v in sd.items():
+        if v.dtype != torch.float32:
+            continue
+        leaf = k.rsplit(".", 1)[-1]
+        if v.dim() > 1:
+            a = g.standard_normal(tuple(v.shape)) * np.sqrt(2.0 / (v[0].numel()))
+        elif leaf == "weight":
+            a = g.uniform(0.2, 0.6, v.shape)
+        elif leaf == "running_var":
+            a = g.uniform(0.5, 2.0, v.shape)
+        else:                                                   # bias, running_mean
+            a = g.uniform(-0.3, 0.3, v.shape)
+        v.copy_(t(a.astype(np.float32)))
+    return m
+
+
+def gen_trunk(ref_resnet):
+    """trunk_resnet34.npz: the reference's ResNet-34 trunk (resnet34(used_layers=[4])) with seeded_trunk_state_ weights on a seeded
+    [2, 2, 127, 127] input: its state_dict keys / shapes and its [2, 512, 4, 4] output (the weights themselves are not stored)."""
+    m = seeded_trunk_state_(ref_resnet.resnet34(used_layers=[4]).eval())
+    x = rng(621).standard_normal((2, 2, 127, 127)).astype(np.float32)
+    with torch.no_grad():
+        out = m(t(x))
+    sd = m.state_dict()
+    save("trunk_resnet34", keys=np.array(list(sd.keys())), shapes=np.array([str(tuple(v.shape)) for v in sd.values()]), x=x,
+         out=out.numpy(), param_sum=np.float64(sum(float(v.double().sum()) for v in sd.values() if v.dtype == torch.float32)))
+
+
+def gen_standin(ref_mb):
+    """standin_backbone.npz: the reference ModelBuilder's ResNet-50 backbone and both necks (resnet_atrous.py, neck.py) with
+    seeded_trunk_state_ weights, on one seeded crop per size (127, 255; rng(630 + size), not stored): state_dict keys / shapes of the three modules and, per output
+    tensor (3 features, 3 neck, 3 neck_lp maps), its shape, float64 sum and a fixed sample of 4096 elements (sorted indices from rng(631),
+    not stored).
+    tests/test_host_logic.py::test_production_standin_is_the_reference_architecture holds tests/production_standin.py to it."""
+    m = ref_mb.ModelBuilder().eval()
+    parts = {"backbone": m.backbone, "neck": m.neck, "neck_lp": m.neck_lp}
+    out = {}
+    for i, (name, mod) in enumerate(parts.items()):
+        seeded_trunk_state_(mod, 625 + i)
+        sd = mod.state_dict()
+        out[name + "_keys"] = np.array(list(sd.keys()))
+        out[name + "_shapes"] = np.array([str(tuple(v.shape)) for v in sd.values()])
+    for side in (127, 255):
+        x = rng(630 + side).standard_normal((1, 3, side, side)).astype(np.float32)
+        with torch.no_grad():
+            f = m.backbone(t(x))
+            ts = list(f) + list(m.neck(f)) + list(m.neck_lp(f))
+        for j, v in enumerate(ts):
+            a = v.numpy().reshape(-1)
+            idx = np.sort(rng(631).choice(a.size, 4096, replace=False)) if a.size > 4096 else np.arange(a.size)
+            out["s%d_%d_shape" % (side, j)] = np.array(v.shape)
+            out["s%d_%d_sum" % (side, j)] = np.float64(a.astype(np.float64).sum())
+            out["s%d_%d_val" % (side, j)] = a[idx]
+    save("standin_backbone", **out)
+
+
 def gen_homo_model(ref_hmb, ref_gi):
     """HomoModelBuilder.forward / track_proj on cfg-1 style inputs (B=2), seeded weights.
 
@@ -1185,6 +1247,12 @@ def main():
         import hdn.tracker.base_tracker as ref_bt
         import hdn.tracker.hdn_tracker_proj_e2e as ref_te
         gen_config5(ref_te, ref_ban, ref_bt, cfg)
+    if want("trunk_resnet34"):
+        import homo_estimator.Deep_homography.Oneline_DLTv1.backbone.resnet as ref_resnet
+        gen_trunk(ref_resnet)
+    if want("standin_backbone"):
+        import hdn.models.model_builder_e2e_unconstrained_v2 as ref_mb
+        gen_standin(ref_mb)
     if want("tracker_loop"):
         import hdn.models.model_builder_e2e_unconstrained_v2 as ref_mb
         import hdn.tracker.hdn_tracker_proj_e2e as ref_te

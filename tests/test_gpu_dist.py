@@ -159,7 +159,7 @@ def test_bench_two_ranks_one_device_json_contract(dev, workload):
     env = dict(os.environ, HDN_BENCH_ONE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--prewarm-ms", "5",
-           "--no-cpu-baseline", "--no-breakdown", "--no-full-head", "--roofline-steps", "2"]
+           "--full", "--no-cpu-baseline", "--no-breakdown", "--no-full-head", "--roofline-steps", "2"]
     if workload == "full":
         cmd += ["--workload", "full"]
     if workload == "kernels-oneshot":      # the exchange as the direct-write gather between the two processes

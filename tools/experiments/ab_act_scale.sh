@@ -25,7 +25,7 @@ if [ "$1" = build ]; then
 fi
 for i in 1 2 3; do for t in "" noscale; do
   if [ -z "$t" ]; then L=$PWD/hdn_amd/libhdn_hip.so; else L=$PWD/hdn_amd/libhdn_hip_$t.so; fi
-  HDN_TRUNK_SCALED_DOMAIN=0 HDN_LIB_PATH=$L python bench.py --no-cpu-baseline --no-sequence --steps 30 2>/dev/null | python -c "
+  HDN_TRUNK_SCALED_DOMAIN=0 HDN_LIB_PATH=$L python bench.py --full --no-cpu-baseline --no-sequence --steps 30 2>/dev/null | python -c "
 import sys, json
 d = json.loads([l for l in sys.stdin if l.startswith('{')][0]); f = d.get('full_head', {})
 print('${t:-x 2^-8 (shipping)}'.ljust(22), 'full head ms/step', round(f.get('ms_per_step', float('nan')), 4), 'frames/s', round(f.get('value', float('nan'))), '| kernels-only step ms', round(d['ms_per_step'], 4))"

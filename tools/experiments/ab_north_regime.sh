@@ -1,6 +1,6 @@
 run() {  # $1 tag, rest: env assignments / bench args
   tag=$1; shift
-  env "$@" python bench.py --no-cpu-baseline --no-full-head --no-breakdown $EXTRA 2>/dev/null | python -c "
+  env "$@" python bench.py --full --no-cpu-baseline --no-full-head --no-breakdown $EXTRA 2>/dev/null | python -c "
 import sys, json
 d = json.loads([l for l in sys.stdin if l.startswith('{')][0]); r = d['roofline']
 print('$tag', 'ms/step', round(d['ms_per_step'], 4), 'frames/s', round(d['value']), '| north mean', round(r['avg_launch_ms']*1e3, 1), 'min', round(r['min_launch_ms']*1e3, 1), 'frac', round(r['frac'], 4))"

@@ -3,7 +3,7 @@
 #   HDN_BENCH_HEAD_PRIORITY: queue priority of the head stream (torch.cuda.Stream(priority=...); the correlation stream is the default stream)
 python -c "import torch; print('priority range', torch.cuda.Stream.priority_range())"
 run() {
-  python bench.py --no-cpu-baseline --no-full-head --no-sequence 2>/dev/null | python -c "
+  python bench.py --full --no-cpu-baseline --no-full-head --no-sequence 2>/dev/null | python -c "
 import sys, json
 d = json.loads([l for l in sys.stdin if l.startswith('{')][0]); r = d['roofline']
 print('$1', 'ms/step', round(d['ms_per_step'], 4), 'frames/s', round(d['value']), '| north mean us', round(r['avg_launch_ms']*1e3, 1), 'frac', round(r['frac'], 4))"

@@ -3,7 +3,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/step_trace
 rm -rf $O; mkdir -p $O
-rocprofv3 --kernel-trace -d $O --output-format csv -- python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-breakdown --no-sequence --no-full-head --roofline-steps 2 ${BENCH_EXTRA} > $O/log.txt 2>&1
+rocprofv3 --kernel-trace -d $O --output-format csv -- python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-breakdown --no-sequence --no-full-head --roofline-steps 2 ${BENCH_EXTRA} > $O/log.txt 2>&1
 f=$(find $O -name "*kernel_trace.csv" | head -1)
 python - <<PY
 import csv

@@ -1,7 +1,7 @@
 # rocprofv3 kernel stats of the full head at B = 64 (tools/experiments/exp_full_head_graph.py); run on the GPU box through gpurun
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
-O=$R/gpurun_out/prof_full
+O=$R/${PROFILE_OUT:-profile_out}/prof_full
 rm -rf $O; mkdir -p $O
 rocprofv3 --kernel-trace --stats -d $O --output-format csv -- python $R/tools/experiments/exp_full_head_graph.py > $O/log.txt 2>&1
 f=$(find $O -name "*kernel_stats.csv" | head -1)

@@ -17,10 +17,10 @@ run() {  # n tag extra-args...
   if [ "$n" -gt "$NG" ]; then echo "skip $tag: $n GPUs asked, $NG present" >&2; return; fi
   port=$((port + 1))
   if [ "$n" -eq 1 ]; then
-    python bench.py --gpus 1 --steps $STEPS --warmup $WARM --no-sequence --no-cpu-baseline "$@" > $OUT/$tag.json 2> $OUT/$tag.log
+    python bench.py --full --gpus 1 --steps $STEPS --warmup $WARM --no-sequence --no-cpu-baseline "$@" > $OUT/$tag.json 2> $OUT/$tag.log
   else
     python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $port \
-      bench.py --gpus $n --steps $STEPS --warmup $WARM --no-sequence --no-cpu-baseline "$@" > $OUT/$tag.json 2> $OUT/$tag.log
+      bench.py --gpus $n --full --steps $STEPS --warmup $WARM --no-sequence --no-cpu-baseline "$@" > $OUT/$tag.json 2> $OUT/$tag.log
   fi
   echo "$tag rc=$?" >&2
 }
