@@ -165,11 +165,16 @@ def get_search_info(frame, pos, original_sz, avg_chans, model_sz: int = 127, par
 
 
 def _matrices(frame, M, width, what):
+    """M -> (B, keep, pointer, stride).  At B = 1 a device tensor may have any shape holding `width` values ([3, 3], [9],
+    [2, 3], ...); a [1, width] row, possibly a column slice of a wider per-sequence array, is passed with its own stride."""
     B = frame.shape[0] if frame.dim() == 4 else 1
     if isinstance(M, torch.Tensor):
-        m = M if (B > 1 or M.dim() == 2) else M.contiguous().reshape(1, -1)
-        if B == 1 and m.numel() != width:
-            raise ValueError(f"M must be {what}")
+        m = M
+        if B == 1:
+            if M.numel() != width:
+                raise ValueError(f"M must be {what}")
+            if not (M.dim() == 2 and M.shape[0] == 1):
+                m = M.contiguous().reshape(1, width)
     else:
         a = np.asarray(M, np.float64)
         if a.size != B * width:

@@ -5,8 +5,10 @@ Pinned (held to fixtures produced by the reference's own functions, tests/golden
     get_subwindow / get_subwindow_for_homo WITHOUT the resize  <- hdn/tracker/base_tracker.py:61-213 (crop, uint8 mean padding)
     get_search_info / get_template_info on 127-px crops        <- .../Oneline_DLTv1/tools/get_img_info.py:8-70
 PARITY UNPINNED (OpenCV is a third-party dependency that neither the reference tree nor this image contains; these restate
-OpenCV 4.x's published 8-bit algorithms from modules/imgproc/src/{resize,imgwarp}.cpp and are checked through properties
-only — identity, integer shifts, borders, monotonicity):
+OpenCV 4.x's published 8-bit algorithms from modules/imgproc/src/{resize,imgwarp}.cpp.  Their conventions are checked per
+pixel against tests/cv_semantics.py, an independent float64 statement of each call with continuous coordinates, within
+bars the fixed-point quantisation explains (tests/test_opencv_semantics.py); bit-exactness to OpenCV itself is pinned only
+by tests/test_cv2_pin.py, which needs a real cv2):
     resize_linear_u8          cv2.resize(INTER_LINEAR), called by get_subwindow when original_sz != model_sz
     warp_perspective_u8       cv2.warpPerspective(INTER_LINEAR, BORDER_REPLICATE) of the full frame, hdn_tracker_proj_e2e.py:154
     warp_affine_cubic_u8      cv2.warpAffine(flags=2 = INTER_CUBIC, BORDER_REPLICATE), hdn/utils/transform.py:98-99

@@ -1,5 +1,6 @@
 """CPU tests of oracle/frame_oracle.py: the pinned part against fixtures produced by the reference's own get_subwindow* /
-get_search_info (tests/golden/frame.npz), the OpenCV restatements (parity unpinned) through properties."""
+get_search_info (tests/golden/frame.npz), the OpenCV restatements (parity unpinned) through properties.  Their conventions
+are held per pixel to an independent float64 statement in tests/test_opencv_semantics.py."""
 import numpy as np
 
 from conftest import load_golden
