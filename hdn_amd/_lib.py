@@ -76,6 +76,9 @@ SIGNATURES = {
     "hdn_pack_head_conv3x3_f32": (_i, [ctypes.c_void_p, _i, _i, ctypes.c_void_p, ctypes.c_longlong]),
     "hdn_pack_head_tail_bytes": (ctypes.c_longlong, [_i, _i]),
     "hdn_pack_head_tail_f32": (_i, [_c_float_p, _i, _i, ctypes.c_void_p, ctypes.c_longlong]),
+    "hdn_pack_conv1x1_bytes": (ctypes.c_longlong, [_i, _i]),
+    "hdn_pack_conv1x1_f32": (_i, [_c_float_p, _i, _i, ctypes.c_void_p, ctypes.c_longlong]),
+    "hdn_conv1x1_f32": (_i, [_c_float_p, ctypes.c_void_p] + [_c_float_p] * 3 + [_i] * 7 + [ctypes.c_void_p]),
     "hdn_ubench_copy_f32": (_i, [_c_float_p] * 2 + [ctypes.c_longlong, ctypes.c_void_p]),
     "hdn_conv3x3_pack_info": (_i, [_i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "hdn_conv3x3_workspace_bytes": (ctypes.c_longlong, [_i, _i, _i, _i]),

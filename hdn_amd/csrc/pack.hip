@@ -12,6 +12,7 @@
 //   hdn_pack_stem_mfma_f32      -> wfrag of hdn_trunk_stem_mfma_f32                                    (Conv2d(2, 64, 7, 2, 3))
 //   hdn_pack_head_conv3x3_f32   -> w_packed of hdn_head_conv3x3_f32                                    (n x Conv2d(256, CO, 3))
 //   hdn_pack_head_tail_f32      -> w1_packed of hdn_head_tail_f32                                      (G x [H, H] 1x1 convolutions)
+//   hdn_pack_conv1x1_f32        -> wpacked of hdn_conv1x1_f32                                          (Conv2d(CI, CO, 1, s) of a Bottleneck)
 //
 // All pointers are HOST pointers.  Every stream is 2 pieces x 2 bytes per (padded) weight: v = p0 + 2^-11 p1, p0 = fp16(v),
 // p1 = fp16((v - p0) 2^11), round-to-nearest-even each (csrc/mfma_split.h; weights are NOT pre-scaled, only activations are).
@@ -196,5 +197,24 @@ extern "C" int hdn_pack_head_tail_f32(const float* w1, int G, int H, void* out, 
         const long long tail = 2LL * 32 * 8, in = (static_cast<long long>(kh) * 32 + r) * 8 + j;
         s.put((o + 0) * tail + in, (o + 1) * tail + in, w1[(static_cast<long long>(g) * H + row) * H + k]);
       }
+  return s.ok ? HDN_OK : HDN_E_LIMIT;
+}
+
+extern "C" long long hdn_pack_conv1x1_bytes(int CO, int CI) { return (CO > 0 && CI > 0 && CO % 32 == 0 && CI % 32 == 0) ? 2LL * 2 * CO * CI : HDN_E_SHAPE; }
+
+// w [CO][CI] -> [CO / 32 n tiles][CI / 32 chunks][2 k steps t][piece][k half g][32 n][8]: element e of lane (g, n) = w[32 tile + n][32 chunk + 16 g + 8 t + e]
+// (conv1x1.hip: lane (pixel, g) reads channels [16 g, 16 g + 16) of a chunk and feeds 16 g + 8 t + [0, 8) to k step t)
+extern "C" int hdn_pack_conv1x1_f32(const float* w, int CO, int CI, void* out, long long out_bytes) {
+  if (!w || !out) return HDN_E_NULL;
+  if (hdn_pack_conv1x1_bytes(CO, CI) < 0 || out_bytes != hdn_pack_conv1x1_bytes(CO, CI)) return HDN_E_SHAPE;
+  const int chunks = CI / 32;
+  Sink s{static_cast<uint16_t*>(out)};
+  for (int co = 0; co < CO; ++co)
+    for (int ci = 0; ci < CI; ++ci) {
+      const int nt = co / 32, n = co & 31, chunk = ci / 32, g = (ci / 16) & 1, t = (ci / 8) & 1, e = ci & 7;
+      const long long o = ((static_cast<long long>(nt) * chunks + chunk) * 2 + t) * 2;
+      const long long tail = 2LL * 32 * 8, in = (static_cast<long long>(g) * 32 + n) * 8 + e;
+      s.put((o + 0) * tail + in, (o + 1) * tail + in, w[static_cast<long long>(co) * CI + ci]);
+    }
   return s.ok ? HDN_OK : HDN_E_LIMIT;
 }

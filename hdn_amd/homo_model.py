@@ -13,7 +13,7 @@ import torch.nn as nn
 
 from . import homography as G
 from .share_feature import PreShareFeature
-from .trunk import resnet34_homo
+from .trunk import ACT_SCALE_LOG2, resnet34_homo, resnet50_homo
 
 
 def avgpool_fc(x, fc, in_domain=0):
@@ -48,7 +48,9 @@ def _regress(net, feats):
             return avgpool_fc(fast.forward_scaled(inp).detach(), net.fc, in_domain=1)
         x = fast(inp)
         if tail:
-            return avgpool_fc(x.detach(), net.fc)
+            return avgpool_fc(x.detach(), net.fc, in_domain=dom)     # (dom: a folded trunk without forward_scaled, e.g. the reference's ResNet)
+        if dom and not hasattr(fast, "forward_scaled"):
+            x = x * float(1 << ACT_SCALE_LOG2)
     else:
         x = net.backbone(feats)
     x = net.avgpool(x)
@@ -62,8 +64,10 @@ def optimize_trunk(net, enable: bool = True, channels_last: bool = False, fused_
     Measured at B=64 on MI355X (tools/experiments/exp_trunk.py, fresh process each): as-is 2.92 ms, folded 2.47 ms; with
     torch.backends.cudnn.benchmark = True (MIOpen find mode, set before the first forward): 2.76 / 2.28 ms, and
     folded + channels_last 2.06 ms.  Without find mode channels_last does not pay (2.96 ms), hence the default."""
-    from .trunk import fold_for_inference
+    from .trunk import fold_for_inference, trunk_block_kinds
 
+    if enable:
+        trunk_block_kinds(net.backbone)        # BasicBlock / Bottleneck layouts only: ValueError for anything else
     on_gpu = next(net.backbone.parameters()).is_cuda
     if fused_stem is None:  # the fused first stage / block epilogues need the HIP library and weights on a GPU
         fused_stem = on_gpu
@@ -151,14 +155,17 @@ def track_proj_pair(net, template, search, h4p, patch_1, per_sample: bool = Fals
 class HomoModelBuilder(nn.Module):
     """Same sub-module names as the reference (ShareFeature, backbone, avgpool, fc) so snapshots load."""
 
-    def __init__(self, pretrained: bool = False):
+    def __init__(self, pretrained: bool = False, backbone: str = "resnet34"):
         super().__init__()
         # `pretrained` fetched ImageNet weights over the network in the reference (backbone/__init__.py:39-49);
         # there is no network here, weights come from the tracker snapshot (hdn/utils/model_load.py).
+        # `backbone`: cfg.BACKBONE_HOMO.TYPE of the reference (homo_model_builder.py:97-112), the two trunks it can build with a head
+        if backbone not in ("resnet34", "resnet50"):
+            raise ValueError(f"backbone must be 'resnet34' or 'resnet50', got {backbone!r}")
         self.ShareFeature = PreShareFeature()
-        self.backbone = resnet34_homo()
+        self.backbone = resnet34_homo() if backbone == "resnet34" else resnet50_homo()
         self.avgpool = nn.AdaptiveAvgPool2d(1)
-        self.fc = nn.Linear(512, 8)
+        self.fc = nn.Linear(512 if backbone == "resnet34" else 2048, 8)
 
     def track_proj(self, data, tmp_mask=None, cached_patch_1=None):
         return track_proj(self, data, tmp_mask, cached_patch_1)

@@ -1,4 +1,4 @@
-"""The homography regressor trunk: a 2-channel-input ResNet-34 kept on PyTorch-ROCm (MIOpen).
+"""The homography regressor trunk: a 2-channel-input ResNet-34 (or ResNet-50: Bottleneck, resnet50_homo) with BatchNorm folded and its blocks on HIP.
 
 Reference: homo_estimator/Deep_homography/Oneline_DLTv1/backbone/resnet.py:137-194 with
 BasicBlock x [3,4,6,3], conv1 = Conv2d(2,64,7,2,3), used_layers=[4] (returns layer4 only).
@@ -33,9 +33,36 @@ class BasicBlock(nn.Module):
         return self.relu(y)
 
 
-class HomoResNet(nn.Module):
-    def __init__(self, layers=(3, 4, 6, 3), in_channels=2):
+class Bottleneck(nn.Module):
+    """backbone/resnet.py:97-133: 1x1 -> 3x3 (stride here) -> 1x1 x 4 channels, the ResNet-50 block."""
+
+    expansion = 4
+
+    def __init__(self, inplanes, planes, stride=1, downsample=None):
         super().__init__()
+        self.conv1 = nn.Conv2d(inplanes, planes, 1, bias=False)
+        self.bn1 = nn.BatchNorm2d(planes)
+        self.conv2 = nn.Conv2d(planes, planes, 3, stride, 1, bias=False)
+        self.bn2 = nn.BatchNorm2d(planes)
+        self.conv3 = nn.Conv2d(planes, planes * 4, 1, bias=False)
+        self.bn3 = nn.BatchNorm2d(planes * 4)
+        self.relu = nn.ReLU(inplace=True)
+        self.downsample = downsample
+        self.stride = stride
+
+    def forward(self, x):
+        idt = x if self.downsample is None else self.downsample(x)
+        y = self.relu(self.bn1(self.conv1(x)))
+        y = self.relu(self.bn2(self.conv2(y)))
+        y = self.bn3(self.conv3(y))
+        y += idt
+        return self.relu(y)
+
+
+class HomoResNet(nn.Module):
+    def __init__(self, layers=(3, 4, 6, 3), in_channels=2, block=None):
+        super().__init__()
+        self.block = BasicBlock if block is None else block
         self.inplanes = 64
         self.conv1 = nn.Conv2d(in_channels, 64, 7, 2, 3, bias=False)
         self.bn1 = nn.BatchNorm2d(64)
@@ -53,12 +80,13 @@ class HomoResNet(nn.Module):
                 m.bias.data.zero_()
 
     def _stage(self, planes, blocks, stride):
+        blk, out = self.block, planes * self.block.expansion
         down = None
-        if stride != 1 or self.inplanes != planes:
-            down = nn.Sequential(nn.Conv2d(self.inplanes, planes, 1, stride, bias=False), nn.BatchNorm2d(planes))
-        mods = [BasicBlock(self.inplanes, planes, stride, down)]
-        self.inplanes = planes
-        mods += [BasicBlock(planes, planes) for _ in range(1, blocks)]
+        if stride != 1 or self.inplanes != out:
+            down = nn.Sequential(nn.Conv2d(self.inplanes, out, 1, stride, bias=False), nn.BatchNorm2d(out))
+        mods = [blk(self.inplanes, planes, stride, down)]
+        self.inplanes = out
+        mods += [blk(out, planes) for _ in range(1, blocks)]
         return nn.Sequential(*mods)
 
     act_domain = 0       # 1 on a folded copy whose stages all run in the scaled domain (fold_for_inference): activations are x * 2^-ACT_SCALE_LOG2 inside
@@ -82,6 +110,12 @@ ACT_SCALE_LOG2 = 8
 
 def resnet34_homo():
     return HomoResNet((3, 4, 6, 3))
+
+
+def resnet50_homo(layers=(3, 4, 6, 3)):
+    """backbone/resnet.py:223-231 with conv1 = Conv2d(2, 64, 7, 2, 3) (backbone/__init__.py:28-35): Bottleneck x [3, 4, 6, 3], a [B, 2048, 4, 4]
+    output at 127-px crops; the same parameter names as the reference (layerN.M.{conv1,bn1,conv2,bn2,conv3,bn3,downsample.0,downsample.1})."""
+    return HomoResNet(layers, block=Bottleneck)
 
 
 # hdn_trunk_stem_mfma_f32 from this batch on (measured, rocprofv3 kernel time, MI355X, matrix cores / vector pipe: B = 1 8.8 / 12.0 us with cold caches,
@@ -529,6 +563,131 @@ class FusedBasicBlock(nn.Module):
         return None
 
 
+def pack_conv1x1(weight):
+    """[CO, CI, 1, 1] (or [CO, CI]) fp32 weights, BatchNorm folded in -> the stream hdn_conv1x1_f32 takes (hdn_pack_conv1x1_f32)."""
+    from . import _lib
+
+    CO, CI = weight.shape[0], weight.shape[1]
+    if tuple(weight.shape) not in ((CO, CI), (CO, CI, 1, 1)):
+        raise ValueError(f"pack_conv1x1 takes [CO, CI, 1, 1] weights, got {tuple(weight.shape)}")
+    lib, w = _lib.load(), _host_f32(weight.reshape(CO, CI))
+    return _c_pack("pack_conv1x1", lib.hdn_pack_conv1x1_bytes(CO, CI), lambda o, n: lib.hdn_pack_conv1x1_f32(w.data_ptr(), CO, CI, o, n))
+
+
+def conv1x1(x, wpacked, bias, residual=None, stride=1, relu=True, act_domain=0):
+    """[relu](conv1x1/stride(x) + bias (+ residual)) through hdn_conv1x1_f32; x channels-last [B,CI,S,S] float32, residual / result channels-last
+    [B,CO,So,So], So = (S - 1) // stride + 1; `wpacked` from pack_conv1x1, on x's device.  act_domain as conv3x3_bias_relu's."""
+    import torch
+
+    from . import _lib
+
+    dev = _lib.require_device(x, bias) if residual is None else _lib.require_device(x, bias, residual)
+    cl = torch.channels_last
+    if x.dim() != 4 or x.dtype != torch.float32 or x.shape[2] != x.shape[3] or not x.is_contiguous(memory_format=cl):
+        raise ValueError("conv1x1: square channels-last float32 input [B,CI,S,S]")
+    B, CI, S, _ = x.shape
+    CO, So = bias.numel(), (S - 1) // stride + 1
+    if wpacked.dtype != torch.int16 or wpacked.device != dev or wpacked.numel() != SPLIT_PIECES * CO * CI:
+        raise ValueError("conv1x1: weights must come from pack_conv1x1 for this (CO, CI), on the input's device")
+    if residual is not None and (tuple(residual.shape) != (B, CO, So, So) or not residual.is_contiguous(memory_format=cl)):
+        raise ValueError(f"conv1x1: residual must be channels-last {(B, CO, So, So)}")
+    out = torch.empty((B, CO, So, So), dtype=torch.float32, device=dev, memory_format=cl)
+    with _lib.device_guard(dev):
+        rc = _lib.load().hdn_conv1x1_f32(_lib.ptr(x), _lib.ptr(wpacked), _lib.ptr(bias), _lib.ptr(residual) if residual is not None else None,
+                                         _lib.ptr(out), B, S, CI, CO, int(stride), int(bool(relu)), int(act_domain), _lib.stream_ptr(dev))
+    _lib.check(rc, "conv1x1")
+    return out
+
+
+class FusedBottleneck(nn.Module):
+    """Bottleneck.forward (backbone/resnet.py:113-133) of the BN-folded homography trunk: conv1 1x1 + bias + ReLU, conv2 3x3 + bias + ReLU,
+    conv3 1x1 + bias + residual + ReLU, the residual being the input or the folded downsample branch (1x1 / stride, bias, no ReLU).  The 1x1
+    convolutions are one hdn_conv1x1_f32 launch each (channels-last; an NCHW input is converted once).  conv2 runs on the split-fp16 matrix-core
+    kernel where it has one (stride 1, MATRIX_CORE_CHANNELS at their side: 13 of the 16 blocks of a ResNet-50); the three stride-2 ones run
+    bias-free on MIOpen followed by one hdn_bias_relu_f32 pass, as FusedBasicBlock does for shapes without a kernel.  GPU / eval only."""
+
+    def __init__(self, blk: "Bottleneck", matrix_core: bool = False, act_domain: int = 0):
+        super().__init__()
+        self.act_domain = int(act_domain)
+        convs = (blk.conv1, blk.conv2, blk.conv3) + ((blk.downsample,) if blk.downsample is not None else ())
+        for c in convs:
+            if not isinstance(c, nn.Conv2d) or c.bias is None:
+                raise ValueError("FusedBottleneck takes a block whose BatchNorms were folded into biased convolutions")
+        dev = blk.conv1.weight.device
+        self.stride = blk.conv2.stride
+        self.w2 = nn.Parameter(blk.conv2.weight.detach().clone(), requires_grad=False)
+        # packed weights are buffers: .to() / .cuda() move them with the module, no host round trip inside a forward (or a stream capture);
+        # non-persistent, like FusedBasicBlock's large-batch streams
+        self.register_buffer("p1", pack_conv1x1(blk.conv1.weight).to(dev), persistent=False)
+        self.register_buffer("p3", pack_conv1x1(blk.conv3.weight).to(dev), persistent=False)
+        self.register_buffer("pd", pack_conv1x1(blk.downsample.weight).to(dev) if blk.downsample is not None else None, persistent=False)
+        self.ds_stride = blk.downsample.stride[0] if blk.downsample is not None else 1
+        planes = self.w2.shape[0]
+        use2 = matrix_core and self.stride == (1, 1) and self.w2.shape[1] == planes and planes in MATRIX_CORE_CHANNELS
+        self.register_buffer("p2", pack_conv3x3(self.w2).to(dev) if use2 else None, persistent=False)
+        self.register_buffer("p2v2", pack_conv3x3_v2(self.w2).to(dev) if use2 else None, persistent=False)
+        for name, c in (("b1", blk.conv1), ("b2", blk.conv2), ("b3", blk.conv3), ("bd", blk.downsample)):
+            b = c.bias.detach().clone() if c is not None else None
+            self.register_buffer(name, b)
+            if self.act_domain:       # the biases of the scaled domain (exact: a power of two); b1 .. bd stay the real ones
+                self.register_buffer(name + "d", b * 2.0 ** -ACT_SCALE_LOG2 if b is not None else None, persistent=False)
+
+    def forward(self, x):
+        import torch
+        import torch.nn.functional as F
+
+        cl = torch.channels_last
+        dom = self.act_domain
+        b1, b2, b3, bd = (self.b1d, self.b2d, self.b3d, self.bdd) if dom else (self.b1, self.b2, self.b3, self.bd)
+        if isinstance(x, LazyAct):
+            x = x.finish()
+        if not x.is_contiguous(memory_format=cl):
+            x = x.contiguous(memory_format=cl)
+        y = conv1x1(x, self.p1, b1, relu=True, act_domain=dom)
+        C, S = y.shape[1], y.shape[2]
+        if self.p2 is not None and S == y.shape[3] == _MC_SIDE.get(C, -1):
+            v2 = self.p2v2 if (y.shape[0] >= V2_MIN_BATCH and not FusedBasicBlock.v2_disabled) else None
+            y = conv3x3_bias_relu(y, self.p2, b2, wpacked_v2=v2, act_domain=dom)
+        else:
+            y = bias_relu_(F.conv2d(y, self.w2, None, self.stride, 1).contiguous(memory_format=cl), b2)   # (linear + ReLU: either domain, its bias)
+        idt = x if self.pd is None else conv1x1(x, self.pd, bd, stride=self.ds_stride, relu=False, act_domain=dom)
+        return conv1x1(y, self.p3, b3, residual=idt, relu=True, act_domain=dom)
+
+
+def _is_conv(m, k):
+    return isinstance(m, nn.Conv2d) and m.kernel_size == (k, k) and m.groups == 1 and m.dilation == (1, 1)
+
+
+def block_kind(blk) -> str:
+    """"basic" (BasicBlock: conv1 / bn1 / conv2 / bn2, both 3x3) or "bottleneck" (conv1 1x1 / conv2 3x3 / conv3 1x1 with bn1 .. bn3), matched by
+    attribute layout (so the reference's own classes pass); the downsample branch is None or Sequential(Conv2d 1x1, BatchNorm2d).  Anything else:
+    ValueError (the fold and the fused blocks would silently drop what they do not know)."""
+    bn = lambda m: isinstance(m, nn.BatchNorm2d)
+    ds = getattr(blk, "downsample", None)
+    ds_ok = ds is None or (isinstance(ds, nn.Sequential) and len(ds) == 2 and _is_conv(ds[0], 1) and ds[0].padding == (0, 0) and bn(ds[1]))
+    names = {n for n, _ in blk.named_children()}
+    known = {"conv1", "bn1", "conv2", "bn2", "relu", "downsample"}
+    if (ds_ok and names <= known | {"conv3", "bn3"} and _is_conv(getattr(blk, "conv1", None), 3) and _is_conv(getattr(blk, "conv2", None), 3)
+            and bn(getattr(blk, "bn1", None)) and bn(getattr(blk, "bn2", None)) and getattr(blk, "conv3", None) is None and getattr(blk, "bn3", None) is None):
+        return "basic"
+    if (ds_ok and names <= known | {"conv3", "bn3"} and _is_conv(getattr(blk, "conv1", None), 1) and _is_conv(getattr(blk, "conv2", None), 3)
+            and _is_conv(getattr(blk, "conv3", None), 1) and all(bn(getattr(blk, n, None)) for n in ("bn1", "bn2", "bn3"))
+            and blk.conv1.stride == (1, 1) and blk.conv3.stride == (1, 1)):
+        return "bottleneck"
+    raise ValueError(f"{type(blk).__name__}: neither a BasicBlock nor a Bottleneck by its attributes ({sorted(names)}); the trunk fold does not take it")
+
+
+def trunk_block_kinds(net) -> list:
+    """block_kind of every block of layer1 .. layer4 (ValueError for a trunk without them or with an unknown block)."""
+    kinds = []
+    for name in ("layer1", "layer2", "layer3", "layer4"):
+        layer = getattr(net, name, None)
+        if not isinstance(layer, nn.Sequential):
+            raise ValueError(f"trunk has no {name} Sequential")
+        kinds += [block_kind(blk) for blk in layer]
+    return kinds
+
+
 def fold_for_inference(net: HomoResNet, channels_last: bool = True, fused_stem: bool = False, fused_epilogue: bool = False,
                        matrix_core: bool = None) -> nn.Module:
     """A copy of `net` with every eval-mode BatchNorm folded into the preceding convolution (weights scaled in
@@ -536,13 +695,15 @@ def fold_for_inference(net: HomoResNet, channels_last: bool = True, fused_stem: 
     B=64: 2.92 ms (as-is) -> 2.47 ms (folded) -> 2.11 ms (folded + NHWC); outputs agree with the un-folded CPU
     trunk to ~1.5e-6 relative either way (tools/experiments/exp_trunk.py).  The copy does not track later weight changes.
     fused_stem: replace conv1 / relu / maxpool by FusedStem (GPU only, W <= 128).
-    fused_epilogue: replace every BasicBlock by FusedBasicBlock (GPU only): 83 elementwise launches per forward -> 32.
+    fused_epilogue: replace every BasicBlock by FusedBasicBlock (GPU only): 83 elementwise launches per forward -> 32; every Bottleneck by
+    FusedBottleneck (its 1x1 convolutions on hdn_conv1x1_f32).  A block that is neither (block_kind) raises ValueError.
     matrix_core (default: fused_epilogue and channels_last): the stride-1 3x3 convolutions of MATRIX_CORE_CHANNELS as one launch of
     the split-fp16 matrix-core kernel each, epilogue included."""
     import copy
 
     import torch
 
+    trunk_block_kinds(net)
     net = copy.deepcopy(net).eval()
 
     def fuse(conv, bn):
@@ -558,6 +719,8 @@ def fold_for_inference(net: HomoResNet, channels_last: bool = True, fused_stem: 
         for blk in layer:
             blk.conv1, blk.bn1 = fuse(blk.conv1, blk.bn1), nn.Identity()
             blk.conv2, blk.bn2 = fuse(blk.conv2, blk.bn2), nn.Identity()
+            if hasattr(blk, "conv3"):                                       # a Bottleneck (trunk_block_kinds above)
+                blk.conv3, blk.bn3 = fuse(blk.conv3, blk.bn3), nn.Identity()
             if blk.downsample is not None:
                 blk.downsample = fuse(blk.downsample[0], blk.downsample[1])
     for p in net.parameters():
@@ -570,7 +733,8 @@ def fold_for_inference(net: HomoResNet, channels_last: bool = True, fused_stem: 
     dom = 1 if (fused_epilogue and fused_stem and mc and channels_last and os.environ.get("HDN_TRUNK_SCALED_DOMAIN", "1") not in ("", "0")) else 0
     if fused_epilogue:
         for name in ("layer1", "layer2", "layer3", "layer4"):
-            setattr(net, name, nn.Sequential(*[FusedBasicBlock(blk, mc, act_domain=dom) for blk in getattr(net, name)]))
+            setattr(net, name, nn.Sequential(*[(FusedBottleneck if hasattr(blk, "conv3") else FusedBasicBlock)(blk, mc, act_domain=dom)
+                                               for blk in getattr(net, name)]))
         if channels_last:
             import torch as _t
             net = net.to(memory_format=_t.channels_last)

@@ -431,7 +431,7 @@ int hdn_head_conv3x3_f32(const float* const* xs, const void* w_packed, const flo
  * addition and hdn_bias_relu_f32 / hdn_conv3x3_finish_f32 are the same in either domain (they are positively homogeneous / linear with the scaled bias).
  *
  * Range guard of the two-fp16-piece kernels (ABI 6): hdn_conv3x3_bias_relu_f32, hdn_conv3x3s2_ds_f32, hdn_conv3x3_v2_f32,
- * hdn_conv3x3_chain_f32 (activation inputs), hdn_trunk_stem_mfma_f32, hdn_head_conv3x3_f32 and hdn_head_tail_f32 are finite and fp32-accurate
+ * hdn_conv3x3_chain_f32 (activation inputs), hdn_trunk_stem_mfma_f32, hdn_head_conv3x3_f32, hdn_head_tail_f32 and hdn_conv1x1_f32 are finite and fp32-accurate
  * for |x| < 1.67e7 on their fp32 INPUTS by default (since ABI 9; 65,504 before).  Beyond that the first fp16 piece is inf and the result NaN,
  * where the reference's fp32 convolution stays finite up to 3.4e38.  With HDN_CHECK_RANGE=1 in the environment, or after hdn_set_check_range(1)
  * (returns the previous setting), each of those entry points first reduces max |x| over its input and returns HDN_E_LIMIT when it is
@@ -464,6 +464,7 @@ int hdn_xcorr_north_launch_events(void* start_event, void* stop_event);
  *   hdn_pack_stem_mfma_f32     w [64][2][7][7]                         -> hdn_trunk_stem_mfma_f32 (backbone/resnet.py:141-147)
  *   hdn_pack_head_conv3x3_f32  ws[n] -> [CO][256][3][3]                -> hdn_head_conv3x3_f32 (hdn/models/head/ban.py:55-59)
  *   hdn_pack_head_tail_f32     w1 [G][H][H]                            -> hdn_head_tail_f32 (ban.py:60-66)
+ *   hdn_pack_conv1x1_f32       w [CO][CI]                              -> hdn_conv1x1_f32 (backbone/resnet.py:97-133, 162-176), CO, CI multiples of 32
  */
 long long hdn_pack_conv3x3_bytes(int C);
 int hdn_pack_conv3x3_f32(const float* w, int C, void* out, long long out_bytes);
@@ -479,6 +480,8 @@ long long hdn_pack_head_conv3x3_bytes(int n, int CO);
 int hdn_pack_head_conv3x3_f32(const float* const* ws, int n, int CO, void* out, long long out_bytes);
 long long hdn_pack_head_tail_bytes(int G, int H);
 int hdn_pack_head_tail_f32(const float* w1, int G, int H, void* out, long long out_bytes);
+long long hdn_pack_conv1x1_bytes(int CO, int CI);
+int hdn_pack_conv1x1_f32(const float* w, int CO, int CI, void* out, long long out_bytes);
 
 int hdn_conv3x3_pack_info(int S, int CI, int stride, int* block_n, int* k_steps);
 long long hdn_conv3x3_workspace_bytes(int B, int S, int CI, int stride);
@@ -516,6 +519,21 @@ int hdn_conv3x3_v2_f32(const float* x, const void* wpacked, const float* bias, c
  * backbone/resnet.py:78-94.
  */
 int hdn_conv3x3s2_v2_f32(const float* x, const void* wpacked, const float* bias, float* out, float* out_ds, int B, int S, int CI, int act_domain, void* stream);
+
+/*
+ * 1x1 convolution of the ResNet-50 (Bottleneck) homography trunk with its epilogue fused (conv1x1.hip; added in ABI 10):
+ *   out[B,So,So,CO] = [relu]( conv1x1/stride(x, w) + bias[co] [+ residual[B,So,So,CO]] ),   x [B,S,S,CI], So = (S - 1) / stride + 1, channels-last,
+ * stride 1 or 2 (2: even rows and columns, the downsample branch of a stage's first block), relu 0 / 1, CI and CO multiples of 32, any B >= 1
+ * (else HDN_E_SHAPE; more than 2^31 - 1 elements in x or out, or CO > 65,536: HDN_E_LIMIT).  `residual` may be NULL; `out` may overlap neither `x`
+ * nor `residual` (HDN_E_ALIAS).  x, out, residual and wpacked 16-byte aligned (HDN_E_LIMIT).  act_domain as above ("Activation domain"): 1 = x,
+ * residual and out are x_real 2^-8 in memory and `bias` is bias 2^-8.  fp32 carried as two fp16 pieces, three products, hi / lo fp32 accumulators: the
+ * error of an fp32 convolution; deterministic.  Takes part in the range guard (hdn_set_check_range) on `x`.  No workspace.
+ * wpacked: the stream hdn_pack_conv1x1_f32 wrote from w [CO][CI] (BatchNorm folded in by the caller).
+ * Replaces conv1 + bn1 + relu, conv3 + bn3 + the residual addition + relu and the downsample branch of
+ * homo_estimator/Deep_homography/Oneline_DLTv1/backbone/resnet.py:97-133 (Bottleneck), 162-176 (_make_layer's downsample), eval mode only.
+ */
+int hdn_conv1x1_f32(const float* x, const void* wpacked, const float* bias, const float* residual, float* out, int B, int S, int CI, int CO, int stride,
+                    int relu, int act_domain, void* stream);
 
 /*
  * The same convolutions chained (ABI 5, the tracker's B = 1, where every launch is a dependent step of ~5 us and the launches that only
