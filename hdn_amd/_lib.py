@@ -79,6 +79,11 @@ SIGNATURES = {
     "hdn_pack_conv1x1_bytes": (ctypes.c_longlong, [_i, _i]),
     "hdn_pack_conv1x1_f32": (_i, [_c_float_p, _i, _i, ctypes.c_void_p, ctypes.c_longlong]),
     "hdn_conv1x1_f32": (_i, [_c_float_p, ctypes.c_void_p] + [_c_float_p] * 3 + [_i] * 7 + [ctypes.c_void_p]),
+    "hdn_pack_conv3x3s2_bytes": (ctypes.c_longlong, [_i]),
+    "hdn_pack_conv3x3s2_f32": (_i, [_c_float_p, _i, ctypes.c_void_p, ctypes.c_longlong]),
+    "hdn_conv3x3s2_workspace_bytes": (ctypes.c_longlong, [_i, _i, _i]),
+    "hdn_conv3x3s2_f32": (_i, [_c_float_p, ctypes.c_void_p] + [_c_float_p] * 3 + [ctypes.c_longlong] + [_i] * 4 + [ctypes.c_void_p]),
+    "hdn_act_scale_log2": (_i, []),
     "hdn_ubench_copy_f32": (_i, [_c_float_p] * 2 + [ctypes.c_longlong, ctypes.c_void_p]),
     "hdn_conv3x3_pack_info": (_i, [_i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "hdn_conv3x3_workspace_bytes": (ctypes.c_longlong, [_i, _i, _i, _i]),

@@ -224,9 +224,10 @@ class BatchedDeviceTracker(BatchedHomoTracker):
     """n x DeviceTrackerHomo in lock step: `model` is the reference's ModelBuilder (hm_net = the homography estimator; template /
     track_new / track_new_lp = the similarity branch, called at batch n — the reference's own forward code is batch-general, its heads
     correlate sample b with template b).  Backbone / necks BatchNorm-folded, MIOpen find mode around this tracker's calls, one hipGraph
-    per step (graph=False or HDN_TRACKER_GRAPH=0: eager), exactly as DeviceTrackerHomo does for one sequence."""
+    per step (graph=False or HDN_TRACKER_GRAPH=0: eager), exactly as DeviceTrackerHomo does for one sequence; `hip_trunk` as there."""
 
-    def __init__(self, model, n: int, graph: bool = None, iterations: int = 1, cfg: TrackerConfig = None, fold_backbone: bool = None):
+    def __init__(self, model, n: int, graph: bool = None, iterations: int = 1, cfg: TrackerConfig = None, fold_backbone: bool = None,
+                 hip_trunk: bool = None):
         if cfg is None:
             cfg = TrackerConfig()
             try:
@@ -241,6 +242,8 @@ class BatchedDeviceTracker(BatchedHomoTracker):
         self.miopen_find = os.environ.get("HDN_MIOPEN_FIND", "1") not in ("", "0") and next(model.parameters()).is_cuda
         from . import backbone as BB
         self.folded = BB.optimize_similarity_model(model) if (BB.enabled() if fold_backbone is None else fold_backbone) else []
+        from .tracker import attach_hip_trunk
+        self.hip_trunk = attach_hip_trunk(model, hip_trunk)
         super().__init__(model.hm_net, n, iterations=iterations, similarity=DeviceSimilarity(model, cfg), graph=graph, cfg=cfg)
 
     def _find_mode(self):

@@ -168,11 +168,6 @@ static int dispatch(int M, int CI, int CO, F&& f) {
   return f(Cfg<2, 4, 1, 1>{});
 }
 
-static bool overlap(const void* a, long long na, const void* b, long long nb) {
-  const char *pa = static_cast<const char*>(a), *pb = static_cast<const char*>(b);
-  return pa < pb + nb * 4 && pb < pa + na * 4;
-}
-
 }  // namespace c1
 }  // namespace hdn
 
@@ -185,7 +180,7 @@ extern "C" int hdn_conv1x1_f32(const float* x, const void* wpacked, const float*
   const long long So = (S - 1) / stride + 1;
   const long long nx = (long long)B * S * S * CI, nout = (long long)B * So * So * CO;
   if (nx > INT_MAX || nout > INT_MAX || CO > 65536) return HDN_E_LIMIT;
-  if (hdn::c1::overlap(out, nout, x, nx) || (residual && hdn::c1::overlap(out, nout, residual, nout))) return HDN_E_ALIAS;
+  if (hdn::bytes_overlap(out, nout * 4, x, nx * 4) || (residual && hdn::bytes_overlap(out, nout * 4, residual, nout * 4))) return HDN_E_ALIAS;
   if (!hdn::aligned16(x) || !hdn::aligned16(wpacked) || !hdn::aligned16(out) || (residual && !hdn::aligned16(residual))) return HDN_E_LIMIT;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (const int rr = hdn::check_fp16_range(x, nx, s, act_domain)) return rr;

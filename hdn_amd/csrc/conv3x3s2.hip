@@ -315,3 +315,279 @@ extern "C" int hdn_conv3x3s2_v2_f32(const float* x, const void* wpacked, const f
   if (S == 4 && CI == 256) return go(hdn::cvs::CfgS<4, 256>{});
   return HDN_E_LIMIT;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+// hdn_conv3x3s2_f32 — the stride-2 3x3 convolution of a Bottleneck (the first block of layer2 / 3 / 4 of the ResNet-50 trunk), C -> C channels:
+//   out[B,S,S,C] = relu(conv3x3/s2/p1(x[B,2S,2S,C], W) + bias[c]),   (S, C) = (16, 128), (8, 256), (4, 512)
+// Reference: Bottleneck.forward conv2 + bn2 + relu, homo_estimator/Deep_homography/Oneline_DLTv1/backbone/resnet.py:97-133 (BatchNorm folded by the caller).
+//
+// The LDS image of the kernel above (a chunk of 32 input channels of the workgroup's (2R + 1) x (2S + 1) input patch as two fp16 pieces, even padded
+// columns before odd ones, so that every tap is a constant offset and 16 consecutive lanes read consecutive 16-byte slots) without its producer /
+// consumer split: 4 waves stage the chunk together, then each owns a 32 pixel x 32 channel corner of the 64 x 64 output tile and walks the chunk's nine
+// taps x two k steps (54 MFMAs per chunk, one barrier pair per chunk; the next chunk's pixels are in flight in registers meanwhile, and two
+// workgroups share a CU: 192-202 VGPRs + 32 AGPRs per lane, no scratch, 39-48 KB of LDS each).  Weights go L2 -> registers in fragment order, one kernel row (3 taps) ahead.  The tile leaves through
+// the LDS as 16-byte stores.
+// K slices: when the output tiles alone give fewer than FILL workgroups (the tracker's B = 1: 8 / 4 / 8 tiles; S = 8 / 4 even at B = 64) grid.z splits K —
+// first by chunks, then by kernel row — each slice writes its raw partial tile to `workspace` [z][M][C] and conv3x3s2_finish_kernel adds the slices
+// in slice order with the bias and the ReLU: a fixed summation order, no atomics.
+// FILL = two workgroups for each of the 256 CUs (what the registers allow to be resident).  Measured with it, rocprofv3 kernel time: docs/KERNELS.md "conv3x3s2".
+#ifndef HDN_S2_FILL
+#define HDN_S2_FILL 512
+#endif
+
+namespace hdn {
+namespace cb {
+using namespace hdn::mc;
+
+template <int SO_, int C_>
+struct CfgB {
+  static constexpr int SO = SO_, C = C_, SI = 2 * SO_;
+  static constexpr int BM = 64, BN = 64, KS = 2;
+  static_assert((SO == 16 && C == 128) || (SO == 8 && C == 256) || (SO == 4 && C == 512), "the three stride-2 Bottlenecks of the trunk");
+  static constexpr int IMGS = BM > SO * SO ? BM / (SO * SO) : 1;     // images per tile (4 x 4 outputs: four)
+  static constexpr int R = BM / (SO * IMGS);                         // output rows of an image in the tile
+  static constexpr int PH = 2 * R + 1;                               // padded input rows (one row of padding above, none needed below)
+  static constexpr int NE = SO + 1, NO = SO, PWH = NE;               // even / odd padded columns of a row; slot of the first odd one
+  static constexpr int PW = SO == 16 ? 33 : SO == 8 ? 20 : 10;       // row pitch in slots (bank groups: CfgS above)
+  static_assert(PW >= NE + NO, "row pitch");
+  static constexpr int IPITCH = PH * PW, LPV = IMGS * IPITCH;
+  static constexpr int LP = LPV + (4 - LPV % 16 + 16) % 16;          // = 4 mod 16: the four k groups of a pixel land on distinct banks
+  static constexpr int KG_BYTES = LP * 16, KSTEP_BYTES = 2 * KG_BYTES, PIECE_BYTES = KS * KSTEP_BYTES, A_BYTES = 2 * PIECE_BYTES;
+  static constexpr int NCHUNK = C / (16 * KS), NB = C / BN;
+  static constexpr int WTAP = 2 * KS * 2 * 64;                       // 16-byte words of one (channel block, chunk, tap): [n tile][k step][piece][lane]
+  static constexpr int EPI_STRIDE = BN + 4;
+  static constexpr int RED_BYTES = BM * EPI_STRIDE * 4;
+  static constexpr int LDS_BYTES = A_BYTES > RED_BYTES ? A_BYTES : RED_BYTES;
+  static_assert(LDS_BYTES <= 64 * 1024, "static LDS");
+  static constexpr int AITEMS = LPV * 2 * KS, AITER = cdiv(AITEMS, HDN_BLOCK);
+  static constexpr int EITER = BM * (BN / 4) / HDN_BLOCK;
+};
+
+// the K slices of a problem: ZC slices of the chunks x ZT (1 or 3) of the kernel rows
+struct Slices {
+  int zc, zt;
+  int z() const { return zc * zt; }
+};
+template <class Cf>
+static Slices slices_for(long long M) {
+  const long long tiles = (M + Cf::BM - 1) / Cf::BM * Cf::NB;
+  Slices s{1, 1};
+  while (tiles * s.zc < HDN_S2_FILL && s.zc < Cf::NCHUNK) s.zc *= 2;
+  if (tiles * s.zc < HDN_S2_FILL) s.zt = 3;
+  return s;
+}
+
+template <class Cf, bool SD, bool FUSED>
+__global__ __launch_bounds__(HDN_BLOCK) void conv3x3s2_kernel(const float* __restrict__ x, const u32x4* __restrict__ wp, const float* __restrict__ bias,
+                                                             float* __restrict__ dst, int B, int ZC, int ZT) {
+  constexpr int SO = Cf::SO, SI = Cf::SI, C = Cf::C, BM = Cf::BM, BN = Cf::BN, KS = Cf::KS;
+  __shared__ __attribute__((aligned(16))) unsigned char smem[Cf::LDS_BYTES];
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int li = lane & 31, g = lane >> 5, wm = wave >> 1, wn = wave & 1;
+  const int nb = blockIdx.x;                                  // output-channel block, fastest: neighbours share the input patch in L2
+  const long long M = (long long)B * SO * SO;
+  const long long m0 = (long long)blockIdx.y * BM;
+  const int b0 = (int)(m0 / (SO * SO)), y0 = (int)((m0 % (SO * SO)) / SO);
+  const int z = blockIdx.z, zc = z / ZT, zt = z - zc * ZT;
+  const int cpz = Cf::NCHUNK / ZC, c0 = zc * cpz;             // this slice's chunks [c0, c0 + cpz) and kernel rows [ky0, ky1)
+  const int ky0 = ZT == 3 ? zt : 0, ky1 = ZT == 3 ? zt + 1 : 3;
+
+  // an item = (pixel slot, 8-channel group of the chunk): source offset, validity and LDS address do not depend on the chunk
+  uint32_t a_src[Cf::AITER], a_dst[Cf::AITER];
+  bool a_ok[Cf::AITER];
+#pragma unroll
+  for (int q = 0; q < Cf::AITER; ++q) {
+    const int item = tid + q * HDN_BLOCK;
+    const int px = min(item / (2 * KS), Cf::LPV - 1), sub = item % (2 * KS);
+    const int img = px / Cf::IPITCH, ry = (px % Cf::IPITCH) / Cf::PW, sl = px % Cf::IPITCH % Cf::PW;
+    const int pc = sl < Cf::NE ? 2 * sl : 2 * (sl - Cf::NE) + 1;                 // padded column of the slot
+    const int b = b0 + img, y = 2 * y0 + ry - 1, xx = pc - 1;
+    a_ok[q] = item < Cf::AITEMS && sl < Cf::NE + Cf::NO && b < B && y >= 0 && y < SI && xx >= 0 && xx < SI;
+    a_src[q] = a_ok[q] ? (uint32_t)(((b * SI + y) * SI + xx) * C + sub * 8) : 0u;          // (floats; the whole input is < 2^31 of them)
+    a_dst[q] = (uint32_t)(sub * Cf::KG_BYTES + px * 16);
+  }
+  f4 av[Cf::AITER][2];
+  auto load_a = [&](int chunk) {
+#pragma unroll
+    for (int q = 0; q < Cf::AITER; ++q) {
+      const f4* src = reinterpret_cast<const f4*>(x + a_src[q] + chunk * (16 * KS));
+      av[q][0] = a_ok[q] ? src[0] : f4{0.f, 0.f, 0.f, 0.f};
+      av[q][1] = a_ok[q] ? src[1] : f4{0.f, 0.f, 0.f, 0.f};
+    }
+  };
+  auto store_a = [&]() {
+#pragma unroll
+    for (int q = 0; q < Cf::AITER; ++q) {
+      if (tid + q * HDN_BLOCK < Cf::AITEMS) {
+        unsigned q0[4], q1[4];
+        split2x2<SD>(av[q][0].x, av[q][0].y, q0[0], q1[0]);
+        split2x2<SD>(av[q][0].z, av[q][0].w, q0[1], q1[1]);
+        split2x2<SD>(av[q][1].x, av[q][1].y, q0[2], q1[2]);
+        split2x2<SD>(av[q][1].z, av[q][1].w, q0[3], q1[3]);
+        unsigned char* d = smem + a_dst[q];
+        *reinterpret_cast<u32x4*>(d) = u32x4{q0[0], q0[1], q0[2], q0[3]};
+        *reinterpret_cast<u32x4*>(d + Cf::PIECE_BYTES) = u32x4{q1[0], q1[1], q1[2], q1[3]};
+      }
+    }
+  };
+
+  // this lane's A row: pixel wm * 32 + li of the tile; tap (0, 0) = padded (2 yy, 2 xx)
+  int aoff;
+  {
+    const int p = wm * 32 + li;
+    const int img = p / (Cf::R * SO), yy = (p / SO) % Cf::R, xx = p % SO;
+    aoff = g * Cf::KG_BYTES + (img * Cf::IPITCH + 2 * yy * Cf::PW + xx) * 16;
+  }
+  // this wave's weight stream: [channel block][chunk][tap][n tile][k step][piece][lane] x 16 B
+  const u32x4* const wbase = wp + (size_t)nb * Cf::NCHUNK * 9 * Cf::WTAP + wn * (Cf::WTAP / 2) + lane;
+  u32x4 wnx[3][KS][2];
+  auto load_w = [&](int chunk, int ky) {
+    const u32x4* p = wbase + ((size_t)chunk * 9 + ky * 3) * Cf::WTAP;
+#pragma unroll
+    for (int kx = 0; kx < 3; ++kx)
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+        for (int pc = 0; pc < 2; ++pc) wnx[kx][ks][pc] = p[kx * Cf::WTAP + (ks * 2 + pc) * 64];
+  };
+
+  f32x16 hi, lo;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) hi[r] = lo[r] = 0.f;
+
+  load_a(c0);
+  load_w(c0, ky0);
+  for (int c = 0; c < cpz; ++c) {
+    store_a();
+    __syncthreads();                                          // chunk c is staged
+    if (c + 1 < cpz) load_a(c0 + c + 1);
+    for (int ky = ky0; ky < ky1; ++ky) {
+      u32x4 wv[3][KS][2];
+#pragma unroll
+      for (int kx = 0; kx < 3; ++kx)
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+          for (int pc = 0; pc < 2; ++pc) wv[kx][ks][pc] = wnx[kx][ks][pc];
+      if (ky + 1 < ky1) load_w(c0 + c, ky + 1);
+      else if (c + 1 < cpz) load_w(c0 + c + 1, ky0);
+      const unsigned char* arow = smem + aoff + ky * Cf::PW * 16;
+#pragma unroll
+      for (int kx = 0; kx < 3; ++kx) {
+        const int off = (kx == 0 ? 0 : kx == 1 ? Cf::PWH : 1) * 16;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+          const u32x4 a0 = *reinterpret_cast<const u32x4*>(arow + off + ks * Cf::KSTEP_BYTES);
+          const u32x4 a1 = *reinterpret_cast<const u32x4*>(arow + off + ks * Cf::KSTEP_BYTES + Cf::PIECE_BYTES);
+          hi = mfma(a0, wv[kx][ks][0], hi);
+          lo = mfma(a0, wv[kx][ks][1], lo);
+          lo = mfma(a1, wv[kx][ks][0], lo);
+        }
+      }
+    }
+    __syncthreads();                                          // every wave has read chunk c's image
+  }
+
+  // the tile -> LDS (over the dead image).  C/D layout of v_mfma_f32_32x32x16_f16: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+  float* const red = reinterpret_cast<float*>(smem);
+#pragma unroll
+  for (int r = 0; r < 16; ++r) red[(wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * g) * Cf::EPI_STRIDE + wn * 32 + li] = join<SD>(hi[r], lo[r]);
+  __syncthreads();
+  float* const o = FUSED ? dst : dst + (size_t)z * (size_t)M * C;
+#pragma unroll
+  for (int q = 0; q < Cf::EITER; ++q) {
+    const int idx = tid + q * HDN_BLOCK, px = idx / (BN / 4), c4 = idx % (BN / 4);
+    const long long m = m0 + px;
+    if (m < M) {
+      f4 v = *reinterpret_cast<const f4*>(red + px * Cf::EPI_STRIDE + c4 * 4);
+      if constexpr (FUSED) {
+        v = v + *reinterpret_cast<const f4*>(bias + nb * BN + c4 * 4);
+        v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+      }
+      *reinterpret_cast<f4*>(o + m * C + nb * BN + c4 * 4) = v;
+    }
+  }
+}
+
+// out = relu(slice 0 + slice 1 + ... + bias), in slice order; n4 = M C / 4 (16-byte items), C a multiple of 4
+__global__ __launch_bounds__(HDN_BLOCK) void conv3x3s2_finish_kernel(const f4* __restrict__ ws, const float* __restrict__ bias, f4* __restrict__ out,
+                                                                    long long n4, int C, int Z) {
+  const long long i = (long long)blockIdx.x * HDN_BLOCK + threadIdx.x;
+  if (i >= n4) return;
+  f4 v = ws[i];
+  for (int z = 1; z < Z; ++z) v = v + ws[(long long)z * n4 + i];
+  v = v + *reinterpret_cast<const f4*>(bias + (int)((i * 4) % C));
+  v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+  out[i] = v;
+}
+
+template <class Cf>
+static long long workspace_bytes(int B) {
+  const long long M = (long long)B * Cf::SO * Cf::SO;
+  const int z = slices_for<Cf>(M).z();
+  return z > 1 ? (long long)z * M * Cf::C * 4 : 0;
+}
+
+template <class Cf, bool SD>
+static int launch(const float* x, const void* wp, const float* bias, float* out, float* ws, int B, hipStream_t stream) {   // (ws: checked by the entry)
+  const long long M = (long long)B * Cf::SO * Cf::SO, tm = (M + Cf::BM - 1) / Cf::BM;
+  const Slices sl = slices_for<Cf>(M);
+  if (tm > 65535) return HDN_E_LIMIT;                              // grid.y
+  const dim3 grid(Cf::NB, (unsigned)tm, (unsigned)sl.z()), blk(HDN_BLOCK);
+  const u32x4* w = static_cast<const u32x4*>(wp);
+  if (sl.z() == 1) {
+    hipLaunchKernelGGL((conv3x3s2_kernel<Cf, SD, true>), grid, blk, 0, stream, x, w, bias, out, B, 1, 1);
+    return launch_status();
+  }
+  hipLaunchKernelGGL((conv3x3s2_kernel<Cf, SD, false>), grid, blk, 0, stream, x, w, bias, ws, B, sl.zc, sl.zt);
+  if (const int rc = launch_status()) return rc;
+  const long long n4 = M * Cf::C / 4;
+  hipLaunchKernelGGL(conv3x3s2_finish_kernel, dim3((unsigned)((n4 + HDN_BLOCK - 1) / HDN_BLOCK)), blk, 0, stream, reinterpret_cast<const f4*>(ws), bias,
+                     reinterpret_cast<f4*>(out), n4, Cf::C, sl.z());
+  return launch_status();
+}
+
+// f(CfgB<...>{}) for a supported (S, C), HDN_E_LIMIT otherwise
+template <class F>
+static long long with_cfg(int S, int C, F&& f) {
+  if (S == 16 && C == 128) return f(CfgB<16, 128>{});
+  if (S == 8 && C == 256) return f(CfgB<8, 256>{});
+  if (S == 4 && C == 512) return f(CfgB<4, 512>{});
+  return HDN_E_LIMIT;
+}
+
+}  // namespace cb
+}  // namespace hdn
+
+extern "C" long long hdn_conv3x3s2_workspace_bytes(int B, int S, int C) {
+  if (B <= 0) return HDN_E_SHAPE;
+  if ((long long)B * S * S * 4 * C > 0x7fffffffLL) return HDN_E_LIMIT;
+  return hdn::cb::with_cfg(S, C, [&](auto cfg) { return hdn::cb::workspace_bytes<decltype(cfg)>(B); });
+}
+
+// wpacked (hdn_pack_conv3x3s2_f32): [C / 64][C / 32 chunks][9 taps][2 n tiles][2 k steps][2 pieces][k half g][32 n][8] fp16; element e of lane (g, n) =
+// piece of w[co = 64 nb + 32 nt + n][ci = 32 chunk + 16 k step + 8 g + e][tap t = 3 ky + kx]
+extern "C" int hdn_conv3x3s2_f32(const float* x, const void* wpacked, const float* bias, float* out, float* workspace, long long workspace_bytes, int B,
+                                 int S, int C, int act_domain, void* stream) {
+  if (!x || !wpacked || !bias || !out) return HDN_E_NULL;
+  if (B <= 0 || S <= 0 || C <= 0 || (act_domain != 0 && act_domain != 1)) return HDN_E_SHAPE;
+  if (hdn::cb::with_cfg(S, C, [](auto) { return 0; }) != 0) return HDN_E_LIMIT;
+  const long long n_out = (long long)B * S * S * C, n_in = 4 * n_out;
+  if (n_in > 0x7fffffffLL) return HDN_E_LIMIT;
+  if (hdn::bytes_overlap(out, n_out * 4, x, n_in * 4)) return HDN_E_ALIAS;
+  for (const void* p : {(const void*)x, wpacked, (const void*)bias, (const void*)out})
+    if (!hdn::aligned16(p)) return HDN_E_LIMIT;
+  const long long need = hdn_conv3x3s2_workspace_bytes(B, S, C);
+  if (need > 0) {
+    if (!workspace) return HDN_E_NULL;
+    if (!hdn::aligned16(workspace) || workspace_bytes < need) return HDN_E_LIMIT;
+    if (hdn::bytes_overlap(workspace, need, x, n_in * 4) || hdn::bytes_overlap(workspace, need, out, n_out * 4)) return HDN_E_ALIAS;
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (const int rr = hdn::check_fp16_range(x, n_in, s, act_domain)) return rr;
+  return (int)hdn::cb::with_cfg(S, C, [&](auto cfg) -> long long {
+    using Cf = decltype(cfg);
+    return act_domain ? hdn::cb::launch<Cf, true>(x, wpacked, bias, out, workspace, B, s)
+                      : hdn::cb::launch<Cf, false>(x, wpacked, bias, out, workspace, B, s);
+  });
+}

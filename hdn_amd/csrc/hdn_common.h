@@ -138,6 +138,12 @@ __device__ __forceinline__ float rn_div(float a, float b) { return a / b; }  // 
 
 __host__ __device__ __forceinline__ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// do the byte ranges [a, a + na) and [b, b + nb) intersect? (the entry points' HDN_E_ALIAS checks)
+inline bool bytes_overlap(const void* a, long long na, const void* b, long long nb) {
+  const char *pa = static_cast<const char*>(a), *pb = static_cast<const char*>(b);
+  return pa < pb + nb && pb < pa + na;
+}
+
 typedef float float2v __attribute__((ext_vector_type(2)));
 
 // LDS byte address of a __shared__ pointer (low 32 bits of the flat address are the LDS offset).

@@ -13,6 +13,7 @@
 //   hdn_pack_head_conv3x3_f32   -> w_packed of hdn_head_conv3x3_f32                                    (n x Conv2d(256, CO, 3))
 //   hdn_pack_head_tail_f32      -> w1_packed of hdn_head_tail_f32                                      (G x [H, H] 1x1 convolutions)
 //   hdn_pack_conv1x1_f32        -> wpacked of hdn_conv1x1_f32                                          (Conv2d(CI, CO, 1, s) of a Bottleneck)
+//   hdn_pack_conv3x3s2_f32      -> wpacked of hdn_conv3x3s2_f32                                        (Conv2d(C, C, 3, 2, 1) of a Bottleneck)
 //
 // All pointers are HOST pointers.  Every stream is 2 pieces x 2 bytes per (padded) weight: v = p0 + 2^-11 p1, p0 = fp16(v),
 // p1 = fp16((v - p0) 2^11), round-to-nearest-even each (csrc/mfma_split.h; weights are NOT pre-scaled, only activations are).
@@ -216,5 +217,26 @@ extern "C" int hdn_pack_conv1x1_f32(const float* w, int CO, int CI, void* out, l
       const long long tail = 2LL * 32 * 8, in = (static_cast<long long>(g) * 32 + n) * 8 + e;
       s.put((o + 0) * tail + in, (o + 1) * tail + in, w[static_cast<long long>(co) * CI + ci]);
     }
+  return s.ok ? HDN_OK : HDN_E_LIMIT;
+}
+
+extern "C" long long hdn_pack_conv3x3s2_bytes(int C) { return (C == 128 || C == 256 || C == 512) ? 2LL * 2 * C * C * 9 : HDN_E_SHAPE; }
+
+// w [C][C][3][3] -> [C / 64][C / 32 chunks][9 taps][2 n tiles][2 k steps][piece][k half g][32 n][8]: element e of lane (g, n) =
+// w[64 nb + 32 nt + n][32 chunk + 16 k step + 8 g + e][tap] (conv3x3s2.hip, conv3x3s2_kernel: a wave reads its n tile's 4 KB of a tap in one run)
+extern "C" int hdn_pack_conv3x3s2_f32(const float* w, int C, void* out, long long out_bytes) {
+  if (!w || !out) return HDN_E_NULL;
+  if (hdn_pack_conv3x3s2_bytes(C) < 0) return HDN_E_SHAPE;
+  if (out_bytes != hdn_pack_conv3x3s2_bytes(C)) return HDN_E_SHAPE;
+  const int chunks = C / 32;
+  Sink s{static_cast<uint16_t*>(out)};
+  for (int co = 0; co < C; ++co)
+    for (int ci = 0; ci < C; ++ci)
+      for (int tap = 0; tap < 9; ++tap) {
+        const int nb = co / 64, nt = (co / 32) & 1, n = co & 31, chunk = ci / 32, ks = (ci / 16) & 1, g = (ci / 8) & 1, e = ci & 7;
+        const long long o = ((((static_cast<long long>(nb) * chunks + chunk) * 9 + tap) * 2 + nt) * 2 + ks) * 2;
+        const long long tail = 2LL * 32 * 8, in = (static_cast<long long>(g) * 32 + n) * 8 + e;
+        s.put((o + 0) * tail + in, (o + 1) * tail + in, w[(static_cast<long long>(co) * C + ci) * 9 + tap]);
+      }
   return s.ok ? HDN_OK : HDN_E_LIMIT;
 }

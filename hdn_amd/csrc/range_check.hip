@@ -9,6 +9,7 @@
 #include <cstring>
 
 #include "hdn_common.h"
+#include "mfma_split.h"
 
 namespace hdn {
 namespace {
@@ -70,3 +71,6 @@ extern "C" int hdn_set_check_range(int on) {
   hdn::g_check.store(on ? 1 : 0, std::memory_order_relaxed);
   return prev;
 }
+
+// the exponent the two-fp16-piece kernels of this build scale activations by (mfma_split.h): hdn_amd.trunk checks it before it hands over pre-scaled biases
+extern "C" int hdn_act_scale_log2(void) { return HDN_ACT_SCALE_LOG2; }

@@ -58,12 +58,40 @@ def _regress(net, feats):
     return net.fc(x)
 
 
+_TRUNK_HOOK, _TRUNK_ARGS = "_hdn_trunk_reload_hook", "_hdn_trunk_fold_args"
+
+
+def _refold_trunk(net, incompatible_keys=None):
+    """load_state_dict post-hook of optimize_trunk: the folded trunk is rebuilt from the module's new weights and copied INTO the tensors of the
+    attached copy (same storage: a captured hipGraph keeps pointing at them); a copy whose tensors no longer match is replaced instead."""
+    from .trunk import fold_for_inference
+
+    args, old = net.__dict__.get(_TRUNK_ARGS), net.__dict__.get("_hdn_fast_trunk")
+    if args is None or old is None:
+        return
+    with torch.no_grad():
+        fresh = fold_for_inference(net.backbone, *args)
+        dst = dict(list(old.named_parameters()) + list(old.named_buffers()))
+        src = dict(list(fresh.named_parameters()) + list(fresh.named_buffers()))
+        if dst.keys() == src.keys() and all(dst[k].shape == v.shape and dst[k].dtype == v.dtype for k, v in src.items()):
+            for k, v in src.items():
+                dst[k].copy_(v)
+        else:
+            object.__setattr__(net, "_hdn_fast_trunk", fresh)
+
+
 def optimize_trunk(net, enable: bool = True, channels_last: bool = False, fused_stem: bool = None, fused_epilogue: bool = None):
     """Attach the BN-folded trunk to any module with a `.backbone` (also the reference's HomoModelBuilder).
 
     Measured at B=64 on MI355X (tools/experiments/exp_trunk.py, fresh process each): as-is 2.92 ms, folded 2.47 ms; with
     torch.backends.cudnn.benchmark = True (MIOpen find mode, set before the first forward): 2.76 / 2.28 ms, and
-    folded + channels_last 2.06 ms.  Without find mode channels_last does not pay (2.96 ms), hence the default."""
+    folded + channels_last 2.06 ms.  Without find mode channels_last does not pay (2.96 ms), hence the default.
+
+    The folded copy is a snapshot, so a load_state_dict post-hook is registered on `net` (once; enable=False removes it): after
+    `net.load_state_dict(...)`, or a load_state_dict of a module that contains `net`, the trunk is folded again and written into the attached
+    copy's own tensors, so the next forward sees the new weights and a hipGraph captured before the reload stays valid.  Only when the new fold
+    has other tensors (another architecture under the same attribute) is the copy replaced; a graph captured before that must be captured again.
+    Weights edited in place (`.data`) are not seen: call optimize_trunk again."""
     from .trunk import fold_for_inference, trunk_block_kinds
 
     if enable:
@@ -76,6 +104,16 @@ def optimize_trunk(net, enable: bool = True, channels_last: bool = False, fused_
     object.__setattr__(net, "_hdn_fast_trunk", fold_for_inference(net.backbone, channels_last, fused_stem, fused_epilogue) if enable else None)
     # the fused stem reads NCHW and writes the layout the rest of the trunk runs in: no input conversion then
     object.__setattr__(net, "_hdn_fast_nhwc", bool(enable and channels_last and not fused_stem))
+    hook = net.__dict__.get(_TRUNK_HOOK)
+    if enable:
+        object.__setattr__(net, _TRUNK_ARGS, (channels_last, fused_stem, fused_epilogue))
+        if hook is None:
+            object.__setattr__(net, _TRUNK_HOOK, net.register_load_state_dict_post_hook(_refold_trunk))
+    else:
+        if hook is not None:
+            hook.remove()
+        net.__dict__.pop(_TRUNK_HOOK, None)
+        net.__dict__.pop(_TRUNK_ARGS, None)
 
 
 def _share(net, x):

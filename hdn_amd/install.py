@@ -12,7 +12,8 @@ attribute the reference resolves at call time:
     ...models.homo_model_builder.{DLT_solve,transform}   homo_model_builder.py:13
     hdn.models.model_builder_e2e_unconstrained_v2.{DLT_solve,Homo_STN}   :29-30
     ...preprocess.head['PreShareFeature']                registry used by get_pre(), preprocess/__init__.py:18-26
-    ModelBuilder.track_proj                              replaced by the fused version
+    ModelBuilder.track_proj                              replaced by the fused version (install(trunk=True): which also attaches the folded HIP trunk
+                                                         to self.hm_net at its first eval-mode call on a GPU)
     hdn.models.logpolar.STN_Polar (+ its from-import in model_builder…:24)   device-resident log-polar sampler
     MultiBAN.forward / MultiCircBAN.forward              one correlation launch per head + cached template branch
     ModelBuilder.track_new_lp                            same ops, the zero `polar` argument cached on the device (:145: a pageable
@@ -24,6 +25,7 @@ from __future__ import annotations
 
 import importlib
 import types
+import weakref
 
 import torch
 
@@ -55,6 +57,33 @@ REBINDINGS = (
 
 def _track_proj_method(self, data, tmp_mask):
     """ModelBuilder.track_proj with the fused stages; self.hm_net supplies ShareFeature/backbone/avgpool/fc."""
+    return homo_model.track_proj(self.hm_net, data, tmp_mask)
+
+
+_trunk_nets = []   # weak references to the hm_nets _track_proj_trunk_method attached a folded trunk to; uninstall() detaches them
+
+
+def _maybe_attach_trunk(net) -> bool:
+    """Attach the folded HIP trunk to `net` (hm_net) if it has none, is in eval mode and holds CUDA float32 weights; was it attached now?"""
+    if getattr(net, "_hdn_fast_trunk", None) is not None or net.training or getattr(net, "_hdn_trunk_refused", False):
+        return False
+    p = next(net.backbone.parameters())
+    if not p.is_cuda or p.dtype != torch.float32:
+        return False
+    try:
+        homo_model.optimize_trunk(net, channels_last=True)
+    except ValueError as e:          # a trunk the fold does not know: say so once, keep the model's own backbone
+        import warnings
+        warnings.warn(f"hdn_amd: install(trunk=True) leaves hm_net.backbone as it is ({e})")
+        object.__setattr__(net, "_hdn_trunk_refused", True)
+        return False
+    _trunk_nets.append(weakref.ref(net))
+    return True
+
+
+def _track_proj_trunk_method(self, data, tmp_mask):
+    """_track_proj_method of install(trunk=True): the folded HIP trunk is attached to self.hm_net at the first call that can use it."""
+    _maybe_attach_trunk(self.hm_net)
     return homo_model.track_proj(self.hm_net, data, tmp_mask)
 
 
@@ -99,8 +128,13 @@ def _rebind(owner, attr, value, item=False):
 
 def uninstall() -> int:
     """Undo every rebinding install() made (most recent first): the reference runs on its own PyTorch ops again, e.g.
-    for training, which the HIP drop-ins (inference only, no autograd) do not support.  Returns the number undone."""
+    for training, which the HIP drop-ins (inference only, no autograd) do not support.  Folded trunks that install(trunk=True) attached are
+    detached (optimize_trunk(net, enable=False)).  Returns the number of rebindings undone."""
     n = 0
+    while _trunk_nets:
+        net = _trunk_nets.pop()()
+        if net is not None:
+            homo_model.optimize_trunk(net, enable=False)
     while _saved:
         owner, attr, orig, item = _saved.pop()
         if item:
@@ -119,12 +153,14 @@ def uninstall() -> int:
     return n
 
 
-def install(strict: bool = False, modules: dict = None, tracker: bool = False) -> list:
+def install(strict: bool = False, modules: dict = None, tracker: bool = False, trunk: bool = False) -> list:
     """Apply the rebindings.  tracker=True also registers hdn_amd.tracker.DeviceTrackerHomo under
     TRACKS['hdnTrackerHomoProje2e'] (hdn/tracker/tracker_builder.py:12-19), so build_tracker(model) of tools/test.py:72 /
     tools/demo.py returns the device-resident loop (frames uploaded once, crops / warps / decodes as kernels, one host read per
     frame) instead of the host-side one.  `modules` (name -> module) lets tests supply stand-in modules; by default the
-    real reference modules are imported.  Returns the list of (module, attribute) pairs that were rebound;
+    real reference modules are imported.  trunk=True: the rebound ModelBuilder.track_proj attaches the BatchNorm-folded HIP trunk
+    (hdn_amd.homo_model.optimize_trunk(self.hm_net, channels_last=True)) at its first eval-mode call with CUDA float32 weights, for users of the
+    rebindings without the device tracker; off by default.  Returns the list of (module, attribute) pairs that were rebound;
     with strict=True a site that cannot be imported raises instead of being skipped.  uninstall() reverses it."""
     done = []
 
@@ -164,7 +200,7 @@ def install(strict: bool = False, modules: dict = None, tracker: bool = False) -
 
     mb = get("hdn.models.model_builder_e2e_unconstrained_v2")
     if mb is not None and hasattr(mb, "ModelBuilder"):
-        _rebind(mb.ModelBuilder, "track_proj", _track_proj_method)
+        _rebind(mb.ModelBuilder, "track_proj", _track_proj_trunk_method if trunk else _track_proj_method)
         done.append(("hdn.models.model_builder_e2e_unconstrained_v2", "ModelBuilder.track_proj"))
         if "track_new_lp" in mb.ModelBuilder.__dict__:
             _rebind(mb.ModelBuilder, "track_new_lp", _track_new_lp_method)

@@ -81,7 +81,8 @@ def main(argv=None):
     from hdn_amd import _lib, install
 
     _lib.load()  # fail now, loudly, rather than at the first frame
-    done = install.install(strict=strict, tracker=dev_tracker)
+    from .tracker import hip_trunk_enabled
+    done = install.install(strict=strict, tracker=dev_tracker, trunk=hip_trunk_enabled())      # (HDN_HIP_TRUNK=1: also without the device tracker)
     print(f"[hdn_amd.run] {len(done)} hot-path sites rebound to libhdn_hip.so; running {script}", file=sys.stderr, flush=True)
 
     sys.argv = [script] + argv[1:]

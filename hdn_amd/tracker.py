@@ -205,6 +205,20 @@ class HomoTracker:
         return f
 
 
+def hip_trunk_enabled() -> bool:
+    """HDN_HIP_TRUNK (default 0): do the device trackers attach the folded HIP trunk to model.hm_net when `hip_trunk` is not given?"""
+    return os.environ.get("HDN_HIP_TRUNK", "0") not in ("", "0")
+
+
+def attach_hip_trunk(model, hip_trunk) -> bool:
+    """optimize_trunk(model.hm_net, channels_last=True) when `hip_trunk` (None: HDN_HIP_TRUNK) is on and the model is on a GPU; was it attached?"""
+    if not (hip_trunk_enabled() if hip_trunk is None else hip_trunk) or not next(model.hm_net.parameters()).is_cuda:
+        return False
+    from .homo_model import optimize_trunk
+    optimize_trunk(model.hm_net, channels_last=True)
+    return True
+
+
 class DeviceTrackerHomo(HomoTracker):
     """Drop-in for hdnTrackerHomo (hdn_tracker_proj_e2e.py:22-285) behind build_tracker(model)
     (hdn/tracker/tracker_builder.py:18-19): same constructor argument, same init / track_new signatures and result keys.
@@ -212,9 +226,11 @@ class DeviceTrackerHomo(HomoTracker):
     similarity branch).  Each frame is replayed as ONE hipGraph, captured at a sequence's first frame (2.9 against 5.3 ms per frame with the
     production-shaped model: at B = 1 the loop is launch-bound; a body that cannot be captured falls back to eager launches with a warning;
     graph=False or HDN_TRACKER_GRAPH=0: eager).  The model's backbone and necks are switched to their
-    BatchNorm-folded, epilogue-fused form (hdn_amd.backbone; fold_backbone=False or HDN_FOLD_BACKBONE=0: left as they are)."""
+    BatchNorm-folded, epilogue-fused form (hdn_amd.backbone; fold_backbone=False or HDN_FOLD_BACKBONE=0: left as they are).
+    hip_trunk=True (None: HDN_HIP_TRUNK, default 0): model.hm_net's homography trunk (cfg.BACKBONE_HOMO.TYPE resnet34 or resnet50) gets its
+    BatchNorm-folded HIP form attached (hdn_amd.homo_model.optimize_trunk(model.hm_net, channels_last=True); enable=False there undoes it)."""
 
-    def __init__(self, model, graph: bool = None, iterations: int = 1, cfg: TrackerConfig = None, fold_backbone: bool = None):
+    def __init__(self, model, graph: bool = None, iterations: int = 1, cfg: TrackerConfig = None, fold_backbone: bool = None, hip_trunk: bool = None):
         if cfg is None:
             cfg = TrackerConfig()
             try:
@@ -235,14 +251,17 @@ class DeviceTrackerHomo(HomoTracker):
         # backbone + necks stay PyTorch-ROCm's convolutions; their BatchNorm / ReLU / add launches (a third of the B = 1 frame) are folded away
         from . import backbone as BB
         self.folded = BB.optimize_similarity_model(model) if (BB.enabled() if fold_backbone is None else fold_backbone) else []
+        self.hip_trunk = attach_hip_trunk(model, hip_trunk)
         super().__init__(model.hm_net, iterations=iterations, similarity=DeviceSimilarity(model, cfg), graph=graph, cfg=cfg)
-        if (self.folded or self.miopen_find) and not DeviceTrackerHomo._announced:
+        if (self.folded or self.miopen_find or self.hip_trunk) and not DeviceTrackerHomo._announced:
             import sys
             DeviceTrackerHomo._announced = True      # once per process
             print("hdn_amd: DeviceTrackerHomo" +
                   (" switched %s of the model it was given to their BatchNorm-folded form (parameters / state_dict unchanged; "
                    "hdn_amd.backbone.restore_similarity_model(model) or HDN_FOLD_BACKBONE=0 undoes it)" % " / ".join(self.folded) if self.folded else "") +
-                  (" and" if self.folded and self.miopen_find else "") +
+                  ((" and" if self.folded else "") + " attached the folded HIP homography trunk to model.hm_net (hip_trunk / HDN_HIP_TRUNK; "
+                   "hdn_amd.homo_model.optimize_trunk(model.hm_net, enable=False) undoes it)" if self.hip_trunk else "") +
+                  (" and" if (self.folded or self.hip_trunk) and self.miopen_find else "") +
                   (" runs its networks under MIOpen find mode (torch.backends.cudnn.benchmark, raised around this tracker's calls only; "
                    "HDN_MIOPEN_FIND=0: torch's setting as it is)" if self.miopen_find else ""), file=sys.stderr)
 

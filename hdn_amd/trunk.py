@@ -108,6 +108,24 @@ class HomoResNet(nn.Module):
 ACT_SCALE_LOG2 = 8
 
 
+_scale_checked = False
+
+
+def check_act_scale():
+    """The library's compile-time activation scale (hdn_act_scale_log2) against ACT_SCALE_LOG2, until it has matched once: a library built with
+    another HDN_ACT_SCALE_LOG2 would take this module's pre-scaled biases and give wrong offsets with no error.  RuntimeError on a mismatch."""
+    global _scale_checked
+    if _scale_checked:
+        return
+    from . import _lib
+
+    got = int(_lib.load().hdn_act_scale_log2())
+    if got != ACT_SCALE_LOG2:
+        raise RuntimeError(f"libhdn_hip.so was built with HDN_ACT_SCALE_LOG2 = {got}, hdn_amd.trunk scales activations by 2^-{ACT_SCALE_LOG2}: "
+                           "rebuild the library, or fold with HDN_TRUNK_SCALED_DOMAIN=0")
+    _scale_checked = True
+
+
 def resnet34_homo():
     return HomoResNet((3, 4, 6, 3))
 
@@ -323,6 +341,7 @@ def conv3x3_bias_relu(x, wpacked, bias, residual=None, wpacked_v2=None, act_doma
 # B = 64, profiles/round3_conv3x3.txt: the kernel is kept only where it wins)
 MATRIX_CORE_CHANNELS = (64, 128, 256, 512)
 _MC_SIDE = {64: 32, 128: 16, 256: 8, 512: 4}
+S2_CHANNELS = (128, 256, 512)       # ... whose stride-2 C -> C convolutions (a Bottleneck's conv2) run on hdn_conv3x3s2_f32, input side 2 * _MC_SIDE[C]
 
 
 def conv3x3s2_ds(x, wpacked, bias, wpacked_v2=None, act_domain=0):
@@ -599,12 +618,54 @@ def conv1x1(x, wpacked, bias, residual=None, stride=1, relu=True, act_domain=0):
     return out
 
 
+def pack_conv3x3s2(weight):
+    """[C, C, 3, 3] fp32 weights of a Bottleneck's stride-2 convolution, BatchNorm folded in, C = 128 / 256 / 512 -> the stream hdn_conv3x3s2_f32
+    takes (hdn_pack_conv3x3s2_f32)."""
+    from . import _lib
+
+    C = weight.shape[0]
+    if tuple(weight.shape) != (C, C, 3, 3):
+        raise ValueError(f"pack_conv3x3s2 takes [C, C, 3, 3] weights, got {tuple(weight.shape)}")
+    lib, w = _lib.load(), _host_f32(weight)
+    return _c_pack("pack_conv3x3s2", lib.hdn_pack_conv3x3s2_bytes(C), lambda o, n: lib.hdn_pack_conv3x3s2_f32(w.data_ptr(), C, o, n))
+
+
+def conv3x3s2(x, wpacked, bias, act_domain=0):
+    """relu(conv3x3 / stride 2 / padding 1 (x) + bias) through hdn_conv3x3s2_f32; x channels-last [B,C,2S,2S] float32 with (S, C) = (16, 128),
+    (8, 256) or (4, 512) -> channels-last [B,C,S,S]; `wpacked` from pack_conv3x3s2, on x's device.  act_domain as conv3x3_bias_relu's."""
+    import torch
+
+    from . import _lib
+
+    dev = _lib.require_device(x, bias)
+    cl = torch.channels_last
+    if x.dim() != 4 or x.shape[2] != x.shape[3] or x.shape[2] % 2 or not x.is_contiguous(memory_format=cl):
+        raise ValueError("conv3x3s2: square, even-sided channels-last float32 input [B,C,2S,2S]")
+    B, C, H, _ = x.shape
+    S = H // 2
+    if wpacked.dtype != torch.int16 or wpacked.device != dev or wpacked.numel() != 9 * SPLIT_PIECES * C * C or bias.numel() != C:
+        raise ValueError("conv3x3s2: weights must come from pack_conv3x3s2 for this channel count, on the input's device")
+    lib = _lib.load()
+    nws = lib.hdn_conv3x3s2_workspace_bytes(B, S, C)
+    if nws < 0:
+        _lib.check(int(nws), "conv3x3s2")
+    out = torch.empty((B, C, S, S), dtype=torch.float32, device=dev, memory_format=cl)
+    ws = torch.empty(nws // 4, dtype=torch.float32, device=dev) if nws else None   # (from torch's caching allocator: no sync, graph-safe)
+    with _lib.device_guard(dev):
+        rc = lib.hdn_conv3x3s2_f32(_lib.ptr(x), _lib.ptr(wpacked), _lib.ptr(bias), _lib.ptr(out), _lib.ptr(ws) if ws is not None else None, nws,
+                                   B, S, C, int(act_domain), _lib.stream_ptr(dev))
+    _lib.check(rc, "conv3x3s2")
+    return out
+
+
 class FusedBottleneck(nn.Module):
     """Bottleneck.forward (backbone/resnet.py:113-133) of the BN-folded homography trunk: conv1 1x1 + bias + ReLU, conv2 3x3 + bias + ReLU,
     conv3 1x1 + bias + residual + ReLU, the residual being the input or the folded downsample branch (1x1 / stride, bias, no ReLU).  The 1x1
     convolutions are one hdn_conv1x1_f32 launch each (channels-last; an NCHW input is converted once).  conv2 runs on the split-fp16 matrix-core
-    kernel where it has one (stride 1, MATRIX_CORE_CHANNELS at their side: 13 of the 16 blocks of a ResNet-50); the three stride-2 ones run
-    bias-free on MIOpen followed by one hdn_bias_relu_f32 pass, as FusedBasicBlock does for shapes without a kernel.  GPU / eval only."""
+    kernels where it has one: hdn_conv3x3_bias_relu_f32 for stride 1 (MATRIX_CORE_CHANNELS at their side: 13 of the 16 blocks of a ResNet-50) and
+    hdn_conv3x3s2_f32 for stride 2 / padding 1 (S2_CHANNELS at twice their side: the first block of layer2 / 3 / 4), so a folded ResNet-50 trunk at
+    127-px crops makes no MIOpen call.  Any other conv2 runs bias-free on MIOpen followed by one hdn_bias_relu_f32 pass, as FusedBasicBlock does for
+    shapes without a kernel.  GPU / eval only."""
 
     def __init__(self, blk: "Bottleneck", matrix_core: bool = False, act_domain: int = 0):
         super().__init__()
@@ -626,6 +687,8 @@ class FusedBottleneck(nn.Module):
         use2 = matrix_core and self.stride == (1, 1) and self.w2.shape[1] == planes and planes in MATRIX_CORE_CHANNELS
         self.register_buffer("p2", pack_conv3x3(self.w2).to(dev) if use2 else None, persistent=False)
         self.register_buffer("p2v2", pack_conv3x3_v2(self.w2).to(dev) if use2 else None, persistent=False)
+        use_s2 = matrix_core and self.stride == (2, 2) and blk.conv2.padding == (1, 1) and self.w2.shape[1] == planes and planes in S2_CHANNELS
+        self.register_buffer("p2s2", pack_conv3x3s2(self.w2).to(dev) if use_s2 else None, persistent=False)
         for name, c in (("b1", blk.conv1), ("b2", blk.conv2), ("b3", blk.conv3), ("bd", blk.downsample)):
             b = c.bias.detach().clone() if c is not None else None
             self.register_buffer(name, b)
@@ -648,6 +711,8 @@ class FusedBottleneck(nn.Module):
         if self.p2 is not None and S == y.shape[3] == _MC_SIDE.get(C, -1):
             v2 = self.p2v2 if (y.shape[0] >= V2_MIN_BATCH and not FusedBasicBlock.v2_disabled) else None
             y = conv3x3_bias_relu(y, self.p2, b2, wpacked_v2=v2, act_domain=dom)
+        elif self.p2s2 is not None and S == y.shape[3] == 2 * _MC_SIDE[C]:
+            y = conv3x3s2(y, self.p2s2, b2, act_domain=dom)
         else:
             y = bias_relu_(F.conv2d(y, self.w2, None, self.stride, 1).contiguous(memory_format=cl), b2)   # (linear + ReLU: either domain, its bias)
         idt = x if self.pd is None else conv1x1(x, self.pd, bd, stride=self.ds_stride, relu=False, act_domain=dom)
@@ -698,7 +763,8 @@ def fold_for_inference(net: HomoResNet, channels_last: bool = True, fused_stem: 
     fused_epilogue: replace every BasicBlock by FusedBasicBlock (GPU only): 83 elementwise launches per forward -> 32; every Bottleneck by
     FusedBottleneck (its 1x1 convolutions on hdn_conv1x1_f32).  A block that is neither (block_kind) raises ValueError.
     matrix_core (default: fused_epilogue and channels_last): the stride-1 3x3 convolutions of MATRIX_CORE_CHANNELS as one launch of
-    the split-fp16 matrix-core kernel each, epilogue included."""
+    the split-fp16 matrix-core kernel each, epilogue included (and a Bottleneck's stride-2 ones: hdn_conv3x3s2_f32).
+    With every stage fused the interior runs in the scaled activation domain; the library's scale constant is checked first (check_act_scale)."""
     import copy
 
     import torch
@@ -731,6 +797,8 @@ def fold_for_inference(net: HomoResNet, channels_last: bool = True, fused_stem: 
     mc = bool(channels_last) if matrix_core is None else bool(matrix_core)
     # every stage fused and on the matrix cores: the interior runs in the scaled activation domain (ACT_SCALE_LOG2 above)
     dom = 1 if (fused_epilogue and fused_stem and mc and channels_last and os.environ.get("HDN_TRUNK_SCALED_DOMAIN", "1") not in ("", "0")) else 0
+    if dom:
+        check_act_scale()
     if fused_epilogue:
         for name in ("layer1", "layer2", "layer3", "layer4"):
             setattr(net, name, nn.Sequential(*[(FusedBottleneck if hasattr(blk, "conv3") else FusedBasicBlock)(blk, mc, act_domain=dom)

@@ -431,7 +431,7 @@ int hdn_head_conv3x3_f32(const float* const* xs, const void* w_packed, const flo
  * addition and hdn_bias_relu_f32 / hdn_conv3x3_finish_f32 are the same in either domain (they are positively homogeneous / linear with the scaled bias).
  *
  * Range guard of the two-fp16-piece kernels (ABI 6): hdn_conv3x3_bias_relu_f32, hdn_conv3x3s2_ds_f32, hdn_conv3x3_v2_f32,
- * hdn_conv3x3_chain_f32 (activation inputs), hdn_trunk_stem_mfma_f32, hdn_head_conv3x3_f32, hdn_head_tail_f32 and hdn_conv1x1_f32 are finite and fp32-accurate
+ * hdn_conv3x3_chain_f32 (activation inputs), hdn_trunk_stem_mfma_f32, hdn_head_conv3x3_f32, hdn_head_tail_f32, hdn_conv1x1_f32 and hdn_conv3x3s2_f32 are finite and fp32-accurate
  * for |x| < 1.67e7 on their fp32 INPUTS by default (since ABI 9; 65,504 before).  Beyond that the first fp16 piece is inf and the result NaN,
  * where the reference's fp32 convolution stays finite up to 3.4e38.  With HDN_CHECK_RANGE=1 in the environment, or after hdn_set_check_range(1)
  * (returns the previous setting), each of those entry points first reduces max |x| over its input and returns HDN_E_LIMIT when it is
@@ -465,6 +465,7 @@ int hdn_xcorr_north_launch_events(void* start_event, void* stop_event);
  *   hdn_pack_head_conv3x3_f32  ws[n] -> [CO][256][3][3]                -> hdn_head_conv3x3_f32 (hdn/models/head/ban.py:55-59)
  *   hdn_pack_head_tail_f32     w1 [G][H][H]                            -> hdn_head_tail_f32 (ban.py:60-66)
  *   hdn_pack_conv1x1_f32       w [CO][CI]                              -> hdn_conv1x1_f32 (backbone/resnet.py:97-133, 162-176), CO, CI multiples of 32
+ *   hdn_pack_conv3x3s2_f32     w [C][C][3][3]                          -> hdn_conv3x3s2_f32 (backbone/resnet.py:97-133 conv2 at stride 2), C = 128 / 256 / 512
  */
 long long hdn_pack_conv3x3_bytes(int C);
 int hdn_pack_conv3x3_f32(const float* w, int C, void* out, long long out_bytes);
@@ -482,6 +483,8 @@ long long hdn_pack_head_tail_bytes(int G, int H);
 int hdn_pack_head_tail_f32(const float* w1, int G, int H, void* out, long long out_bytes);
 long long hdn_pack_conv1x1_bytes(int CO, int CI);
 int hdn_pack_conv1x1_f32(const float* w, int CO, int CI, void* out, long long out_bytes);
+long long hdn_pack_conv3x3s2_bytes(int C);
+int hdn_pack_conv3x3s2_f32(const float* w, int C, void* out, long long out_bytes);
 
 int hdn_conv3x3_pack_info(int S, int CI, int stride, int* block_n, int* k_steps);
 long long hdn_conv3x3_workspace_bytes(int B, int S, int CI, int stride);
@@ -534,6 +537,29 @@ int hdn_conv3x3s2_v2_f32(const float* x, const void* wpacked, const float* bias,
  */
 int hdn_conv1x1_f32(const float* x, const void* wpacked, const float* bias, const float* residual, float* out, int B, int S, int CI, int CO, int stride,
                     int relu, int act_domain, void* stream);
+
+/*
+ * Stride-2 3x3 convolution of a Bottleneck, bias and ReLU fused (conv3x3s2.hip; added in ABI 10): conv2 + bn2 + relu of the first block of layer2 / 3 / 4
+ * of the ResNet-50 homography trunk,
+ *   out[B,S,S,C] = relu( conv3x3 / stride 2 / padding 1 (x[B,2S,2S,C], w[C][C][3][3]) + bias[c] ),   channels-last fp32,
+ * (S, C) = (16, 128), (8, 256), (4, 512), any B >= 1 (B <= 0 or act_domain outside {0, 1}: HDN_E_SHAPE; another (S, C), more than 2^31 - 1 elements in x,
+ * a pointer that is not 16-byte aligned or a workspace that is too small: HDN_E_LIMIT).  `out` and `workspace` may not overlap `x` (HDN_E_ALIAS).
+ * act_domain as above ("Activation domain").  fp32 carried as two fp16 pieces, three products, hi / lo fp32 accumulators: the error of an fp32
+ * convolution.  Deterministic: inside a workgroup the sum runs over chunks of 32 input channels, the nine taps of a chunk, the two 16-channel k steps of a
+ * tap; where the output tiles alone do not fill the chip (small B, and S = 8 / 4 at any B) K is split over workgroups - by chunks, then by kernel row -
+ * the slices' partial sums go to `workspace` and a second launch adds them in slice order with the bias and the ReLU.  No atomics.
+ * hdn_conv3x3s2_workspace_bytes(B, S, C): bytes needed, 0 = none (workspace may be NULL then), negative = HDN_E_*.
+ * Takes part in the range guard (hdn_set_check_range) on `x`.  Asynchronous on `stream`; allocates nothing.
+ * wpacked: the stream hdn_pack_conv3x3s2_f32 wrote from the BatchNorm-folded w (opaque).
+ * Replaces conv2 + bn2 + relu of homo_estimator/Deep_homography/Oneline_DLTv1/backbone/resnet.py:97-133 where the block's stride is 2 (eval mode only).
+ */
+long long hdn_conv3x3s2_workspace_bytes(int B, int S, int C);
+int hdn_conv3x3s2_f32(const float* x, const void* wpacked, const float* bias, float* out, float* workspace, long long workspace_bytes, int B, int S, int C,
+                      int act_domain, void* stream);
+
+/* The compile-time exponent of the activation scale (csrc/mfma_split.h, HDN_ACT_SCALE_LOG2; 8): callers that hand over pre-scaled biases in
+ * act_domain = 1 check it against the value they scale with (hdn_amd.trunk.ACT_SCALE_LOG2). */
+int hdn_act_scale_log2(void);
 
 /*
  * The same convolutions chained (ABI 5, the tracker's B = 1, where every launch is a dependent step of ~5 us and the launches that only

@@ -6,7 +6,8 @@
 fused_epilogue=False), still MIOpen; (c) "hip": fold_for_inference(channels_last=True, fused_stem=True, fused_epilogue=True), the HIP trunk.
 ms per trunk forward: warmed, HIP-event timed per forward, median of --iters.  All three in one process, on the same seeded weights and input.
 For resnet50 it also lists every hdn_conv1x1_f32 launch of one forward: shape, algorithmic bytes (x + out + residual + packed weights), its own
-event-timed median, and its floor = max(bytes / the measured copy rate, MFMA work at the dense fp16 peak x 3 piece products).
+event-timed median, and its floor = max(bytes / the measured copy rate, MFMA work at the dense fp16 peak x 3 piece products); and the same table
+("conv3x3s2") for the three hdn_conv3x3s2_f32 launches (bytes = x + out + packed weights; K-slice workspace traffic is the kernel's own cost, not in the floor).
 """
 from __future__ import annotations
 
@@ -109,6 +110,17 @@ def main():
                 rows.append({"CI": CI, "CO": CO, "S": S, "stride": s, "residual": has_res, "bytes": nbytes, "us": round(us, 2),
                              "floor_us": round(floor, 2), "x_floor": round(us / floor, 2)})
             res["conv1x1"] = rows
+            rows = []
+            for S, C in ((16, 128), (8, 256), (4, 512)):        # conv2 of the first block of layer2 / 3 / 4
+                B = args.batch
+                xi = torch.rand(B, C, 2 * S, 2 * S, device=dev).contiguous(memory_format=cl)
+                wp = T.pack_conv3x3s2(torch.randn(C, C, 3, 3) * 0.02).to(dev)
+                bias = torch.zeros(C, device=dev)
+                nbytes = 4 * (B * 4 * S * S * C + B * S * S * C + 9 * C * C)
+                us = 1e3 * timed(lambda: T.conv3x3s2(xi, wp, bias), args.iters, args.warmup)
+                floor = max(nbytes / rate, 3 * 2.0 * B * S * S * 9 * C * C / MFMA_F16_PEAK) * 1e6
+                rows.append({"S": S, "C": C, "bytes": nbytes, "us": round(us, 2), "floor_us": round(floor, 2), "x_floor": round(us / floor, 2)})
+            res["conv3x3s2"] = rows
     print(json.dumps(res), flush=True)
 
 
