@@ -79,6 +79,7 @@ SIGNATURES = {
     "hdn_pack_conv1x1_bytes": (ctypes.c_longlong, [_i, _i]),
     "hdn_pack_conv1x1_f32": (_i, [_c_float_p, _i, _i, ctypes.c_void_p, ctypes.c_longlong]),
     "hdn_conv1x1_f32": (_i, [_c_float_p, ctypes.c_void_p] + [_c_float_p] * 3 + [_i] * 7 + [ctypes.c_void_p]),
+    "hdn_conv1x1_form": (_i, [_i] * 5),
     "hdn_pack_conv3x3s2_bytes": (ctypes.c_longlong, [_i]),
     "hdn_pack_conv3x3s2_f32": (_i, [_c_float_p, _i, ctypes.c_void_p, ctypes.c_longlong]),
     "hdn_conv3x3s2_workspace_bytes": (ctypes.c_longlong, [_i, _i, _i]),

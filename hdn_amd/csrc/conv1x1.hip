@@ -171,6 +171,18 @@ static int dispatch(int M, int CI, int CO, F&& f) {
 }  // namespace c1
 }  // namespace hdn
 
+// the launch form dispatch() picks for a problem, for tests and profiles: NT | WM << 8 | WN << 16 | KW << 24.  Host only: nothing is launched.
+extern "C" int hdn_conv1x1_form(int B, int S, int CI, int CO, int stride) {
+  if (B <= 0 || S <= 0 || CI <= 0 || CO <= 0 || CI % 32 || CO % 32 || (stride != 1 && stride != 2)) return HDN_E_SHAPE;
+  const long long So = (S - 1) / stride + 1;
+  const long long nx = (long long)B * S * S * CI, nout = (long long)B * So * So * CO;
+  if (nx > INT_MAX || nout > INT_MAX || CO > 65536) return HDN_E_LIMIT;
+  return hdn::c1::dispatch((int)(B * So * So), CI, CO, [](auto cfg) {
+    using C = decltype(cfg);
+    return C::NT | C::WM << 8 | C::WN << 16 | C::KW << 24;
+  });
+}
+
 extern "C" int hdn_conv1x1_f32(const float* x, const void* wpacked, const float* bias, const float* residual, float* out, int B, int S, int CI, int CO,
                                int stride, int relu, int act_domain, void* stream) {
   if (!x || !wpacked || !bias || !out) return HDN_E_NULL;

@@ -537,6 +537,11 @@ int hdn_conv3x3s2_v2_f32(const float* x, const void* wpacked, const float* bias,
  */
 int hdn_conv1x1_f32(const float* x, const void* wpacked, const float* bias, const float* residual, float* out, int B, int S, int CI, int CO, int stride,
                     int relu, int act_domain, void* stream);
+/* The launch form hdn_conv1x1_f32 picks for a problem (conv1x1.hip, Cfg<NT, WM, WN, KW>: 32-channel output tiles per wave, pixel tiles x
+ * output-channel groups x K slices of the four waves of a workgroup), as NT | WM << 8 | WN << 16 | KW << 24, or HDN_E_SHAPE / HDN_E_LIMIT as the
+ * entry point answers for these arguments.  Asked of the rule the launch itself goes through; host only, nothing is launched.  For tests (which
+ * prove with it that they run every form) and profiles; the forms themselves are no part of the ABI. */
+int hdn_conv1x1_form(int B, int S, int CI, int CO, int stride);
 
 /*
  * Stride-2 3x3 convolution of a Bottleneck, bias and ReLU fused (conv3x3s2.hip; added in ABI 10): conv2 + bn2 + relu of the first block of layer2 / 3 / 4

@@ -85,10 +85,16 @@ def test_conv3x3s2_argument_errors(dev):
     lib = _lib.load()
     cl = torch.channels_last
     B, S, C = 2, 16, 128
-    x = torch.rand(B, C, 2 * S, 2 * S, device=dev).contiguous(memory_format=cl)
+    # x and out are cut from ONE allocation, 256 bytes apart: wherever the caching allocator puts things after the tests that ran before this one,
+    # `x + 1 float` below overlaps nothing (with two allocations `out` can lie right behind `x`, and the entry point then rightly answers HDN_E_ALIAS
+    # before it looks at the alignment)
+    n_x, n_out, gap = B * C * 4 * S * S, B * C * S * S, 64
+    arena = torch.empty(n_x + gap + n_out, device=dev)
+    x = arena[:n_x].view(B, 2 * S, 2 * S, C).permute(0, 3, 1, 2).copy_(torch.rand(B, C, 2 * S, 2 * S, device=dev))
+    out = arena[n_x + gap:].view(B, S, S, C).permute(0, 3, 1, 2)
+    assert x.is_contiguous(memory_format=cl) and out.is_contiguous(memory_format=cl) and out.data_ptr() - x.data_ptr() == (n_x + gap) * 4
     wp = pack_conv3x3s2(torch.randn(C, C, 3, 3) * 0.03).to(dev)
     b = torch.zeros(C, device=dev)
-    out = torch.empty(B, C, S, S, device=dev).contiguous(memory_format=cl)
     nws = lib.hdn_conv3x3s2_workspace_bytes(B, S, C)
     assert nws > 0
     ws = torch.empty(nws // 4, device=dev)
