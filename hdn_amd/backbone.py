@@ -22,6 +22,13 @@ captured around them sees the new weights too); weights edited in place some oth
 module deep-copies and moves like any other, but pickling the MODULE object (torch.save(model), not state_dict) needs
 restore_similarity_model first, because the subclass exists only in this process.
 hdn_amd.tracker.DeviceTrackerHomo applies it to the model it is given (HDN_FOLD_BACKBONE=0 keeps the modules as they are).
+
+    optimize_similarity_model(model, hip=True)      # or HDN_HIP_BACKBONE=1 (default off)
+
+puts the convolutions themselves on the library's two-fp16-piece matrix-core kernels where it has one (HipBottleneck, HipAtrousResNet, hip_necks below):
+every 1x1 convolution on hdn_conv1x1_f32, every stride-1 3x3 convolution with padding == dilation in {1, 2, 4} on hdn_conv3x3d_f32, channels-last between
+the maxpool and the necks' outputs.  Convolutions without a kernel (the 7x7 stem; the stride-2, padding-0 first block of layer2 with its strided 3x3 skip)
+stay on MIOpen as above.  hip_plan(net) names the kernel of every convolution without building anything.
 """
 from __future__ import annotations
 
@@ -125,6 +132,8 @@ class FusedAtrousResNet(nn.Module):
     """ResNet.forward (resnet_atrous.py:186-199) with folded BatchNorms and FusedBottleneck blocks: conv1 -> shift + ReLU -> maxpool
     -> layer1..4 -> the `used_layers` selection ([stem, p1, p2, p3, p4]; a single level is returned bare, as the reference does)."""
 
+    block = FusedBottleneck
+
     def __init__(self, net):
         super().__init__()
         for name in ("conv1", "bn1", "maxpool", "layer1", "layer2", "used_layers"):
@@ -136,7 +145,7 @@ class FusedAtrousResNet(nn.Module):
         for name in ("layer1", "layer2", "layer3", "layer4"):
             layer = getattr(net, name, None)
             if isinstance(layer, nn.Sequential):
-                self.layers.append(nn.Sequential(*[FusedBottleneck(b) for b in layer]))
+                self.layers.append(nn.Sequential(*[self.block(b) for b in layer]))
             elif layer is None or callable(layer):
                 self.layers.append(nn.Identity())       # (`lambda x: x` for an unused stage, resnet_atrous.py:134-141)
             else:
@@ -154,9 +163,10 @@ class FusedAtrousResNet(nn.Module):
         return out[0] if len(out) == 1 else out
 
 
-def fold_sequentials(module: nn.Module) -> nn.Module:
+def fold_sequentials(module: nn.Module, hip: bool = False) -> nn.Module:
     """A deep copy of `module` in which every `Sequential(Conv2d, BatchNorm2d)` is one biased convolution (the necks: AdjustLayer.downsample,
-    neck.py:14-17); everything else — the crop of AdjustLayer.forward, the level loop of AdjustAllLayer.forward — stays the module's own."""
+    neck.py:14-17); everything else — the crop of AdjustLayer.forward, the level loop of AdjustAllLayer.forward — stays the module's own.
+    hip: levels with a kernel become _HipConv (hip_necks)."""
     import copy
 
     m = copy.deepcopy(module)
@@ -165,12 +175,159 @@ def fold_sequentials(module: nn.Module) -> nn.Module:
         for name, child in list(parent.named_children()):
             pair = _conv_bn_pair(child)
             if pair is not None:
-                setattr(parent, name, _FoldedConv(*pair))
+                setattr(parent, name, (_HipConv if hip and hip_conv_kind(pair[0]) != "miopen" else _FoldedConv)(*pair))
             else:
                 walk(child)
 
     walk(m)
     return m
+
+
+# --------------------------------------------------------------------------------------------------------- the opt-in HIP form (hip=True)
+def hip_conv_kind(conv) -> str:
+    """The kernel a folded convolution of the backbone / necks runs on in the HIP form: "conv1x1" (hdn_conv1x1_f32: 1x1, stride 1 or 2, no padding),
+    "conv3x3d" (hdn_conv3x3d_f32: 3x3, stride 1, padding == dilation in {1, 2, 4}) — both with channel counts that are multiples of 32 — or "miopen"
+    (F.conv2d + hdn_bias_relu_f32, as in the folded form)."""
+    if not isinstance(conv, nn.Conv2d) or conv.groups != 1 or conv.in_channels % 32 or conv.out_channels % 32 or conv.padding_mode != "zeros":
+        return "miopen"
+    k, st, pad, dil = conv.kernel_size, conv.stride, conv.padding, conv.dilation
+    if k == (1, 1) and st in ((1, 1), (2, 2)) and pad == (0, 0):
+        return "conv1x1"
+    if k == (3, 3) and st == (1, 1) and dil in ((1, 1), (2, 2), (4, 4)) and pad == dil:
+        return "conv3x3d"
+    return "miopen"
+
+
+def hip_plan(net) -> dict:
+    """{"layerN.M.conv1" / ".conv2" / ".conv3" / ".downsample": hip_conv_kind} for every block of a network of the reference's ResNet layout (reads
+    the structure only: no weights are folded or packed, no device is needed)."""
+    plan = {}
+    for name in ("layer1", "layer2", "layer3", "layer4"):
+        layer = getattr(net, name, None)
+        if not isinstance(layer, nn.Sequential):
+            continue
+        for i, blk in enumerate(layer):
+            for cn in ("conv1", "conv2", "conv3"):
+                plan[f"{name}.{i}.{cn}"] = hip_conv_kind(getattr(blk, cn, None))
+            pair = _conv_bn_pair(getattr(blk, "downsample", None))
+            if pair is not None:
+                plan[f"{name}.{i}.downsample"] = hip_conv_kind(pair[0])
+    return plan
+
+
+class _HipConv(nn.Module):
+    """A convolution with a BatchNorm folded in, on the kernel hip_conv_kind names: the packed stream (a non-persistent buffer, so it moves with .to()
+    and a reload re-packs into the same storage) instead of the fp32 weights; a "miopen" one keeps the folded weights and F.conv2d.  Channels-last in
+    and out.  run(x, bias, residual, relu): [relu](conv(x) [+ bias] [+ residual])."""
+
+    def __init__(self, conv, bn):
+        super().__init__()
+        from . import trunk as T
+
+        w, b = fold_conv_bn(conv, bn)
+        self.kind = hip_conv_kind(conv)
+        self.stride, self.padding, self.dilation = conv.stride, conv.padding, conv.dilation
+        self.register_buffer("bias", b)
+        if self.kind == "miopen":
+            self.register_buffer("weight", w.contiguous(memory_format=torch.channels_last))
+            self.register_buffer("packed", None, persistent=False)
+        else:
+            self.register_buffer("weight", None)
+            self.register_buffer("packed", (T.pack_conv1x1 if self.kind == "conv1x1" else T.pack_conv3x3d)(w).to(w.device), persistent=False)
+
+    def run(self, x, bias=None, residual=None, relu=True):
+        from . import trunk as T
+
+        if self.kind == "conv1x1":
+            return T.conv1x1(x, self.packed, self.bias if bias is None else bias, residual, stride=self.stride[0], relu=relu)
+        if self.kind == "conv3x3d" and residual is None:
+            return T.conv3x3d(x, self.packed, bias, dilation=self.dilation[0], relu=relu)
+        if self.kind != "miopen":
+            raise ValueError("hdn_conv3x3d_f32 takes no residual")
+        y = F.conv2d(x, self.weight, None, self.stride, self.padding, self.dilation).contiguous(memory_format=torch.channels_last)
+        if relu:
+            return T.bias_relu_(y, bias, residual)
+        if residual is not None:
+            raise ValueError("a residual without the ReLU has no fused pass")
+        return y if bias is None else y.add_(bias.view(1, -1, 1, 1))
+
+    def forward(self, x):
+        """conv + shift, NCHW-agnostic in, channels-last out (a neck level)."""
+        if not x.is_contiguous(memory_format=torch.channels_last):
+            x = x.contiguous(memory_format=torch.channels_last)
+        return self.run(x, self.bias, relu=False)
+
+
+class HipBottleneck(nn.Module):
+    """Bottleneck.forward (resnet_atrous.py:87-108) of a block whose BatchNorms are folded, channels-last inside: conv1 + shift + ReLU and conv3 + shift +
+    residual + ReLU as one hdn_conv1x1_f32 launch each (as hdn_amd.trunk.FusedBottleneck fuses them), conv2 + shift + ReLU as one hdn_conv3x3d_f32 launch;
+    a 1x1 downsample branch is a hdn_conv1x1_f32 launch with its own shift, a 3x3 one a bias-free hdn_conv3x3d_f32 launch whose shift rides in the last
+    bias (b3).  A convolution without a kernel (hip_conv_kind: "miopen") runs bias-free on F.conv2d with one hdn_bias_relu_f32 pass behind it."""
+
+    def __init__(self, blk):
+        super().__init__()
+        for name in ("conv1", "bn1", "conv2", "bn2", "conv3", "bn3"):
+            if not hasattr(blk, name):
+                raise ValueError(f"not a Bottleneck: no {name}")
+        self.c1, self.c2, self.c3 = _HipConv(blk.conv1, blk.bn1), _HipConv(blk.conv2, blk.bn2), _HipConv(blk.conv3, blk.bn3)
+        down = getattr(blk, "downsample", None)
+        if down is None:
+            self.cd = None
+            self.register_buffer("b3", self.c3.bias.clone())
+        else:
+            pair = _conv_bn_pair(down)
+            if pair is None:
+                raise ValueError("Bottleneck.downsample is not Sequential(Conv2d, BatchNorm2d)")
+            self.cd = _HipConv(*pair)
+            # a 1x1 branch adds its own shift in its launch; any other hands it to the last pass: (b3 + b_downsample) once
+            self.register_buffer("b3", self.c3.bias.clone() if self.cd.kind == "conv1x1" else self.c3.bias + self.cd.bias)
+
+    def forward(self, x):
+        y = self.c2.run(self.c1.run(x, self.c1.bias), self.c2.bias)
+        if self.cd is None:
+            idt = x
+        elif self.cd.kind == "conv1x1":
+            idt = self.cd.run(x, self.cd.bias, relu=False)
+        else:
+            idt = self.cd.run(x, None, relu=False)
+        return self.c3.run(y, self.b3, idt)
+
+
+class HipAtrousResNet(FusedAtrousResNet):
+    """FusedAtrousResNet with HipBottleneck blocks: the 7x7 stem and the maxpool as there (MIOpen + hdn_bias_relu_f32), the activation converted to
+    channels-last once behind the maxpool; the feature levels come out channels-last (the necks take them as they are)."""
+
+    block = HipBottleneck
+
+    def forward(self, x):
+        x_ = self.c1.act(x)
+        p1 = self.layers[0](self.maxpool(x_).contiguous(memory_format=torch.channels_last))
+        p2 = self.layers[1](p1)
+        p3 = self.layers[2](p2)
+        p4 = self.layers[3](p3)
+        out = [x_, p1, p2, p3, p4]
+        out = [out[i] for i in self.used_layers]
+        return out[0] if len(out) == 1 else out
+
+
+class _HipNeck(nn.Module):
+    """A neck whose Sequential(Conv2d, BatchNorm2d) levels are _HipConv (hdn_conv1x1_f32, relu = 0); what the module's own forward returns (after
+    its crop) is made NCHW-contiguous, so that everything downstream sees the layout it sees without the switch."""
+
+    def __init__(self, inner):
+        super().__init__()
+        self.inner = inner
+
+    def forward(self, feats):
+        out = self.inner(feats)
+        if torch.is_tensor(out):
+            return out.contiguous()
+        return type(out)(o.contiguous() if torch.is_tensor(o) else o for o in out)
+
+
+def hip_necks(module: nn.Module) -> nn.Module:
+    """fold_sequentials with the folded levels on hdn_conv1x1_f32 (a level whose convolution has no kernel stays a _FoldedConv)."""
+    return _HipNeck(fold_sequentials(module, hip=True))
 
 
 # ---------------------------------------------------------------------------------------------------------------- in-place switch
@@ -237,26 +394,32 @@ def _original_view(mod):
     return m
 
 
-def _build_backbone(mod):
+def _build_backbone(mod, hip=False):
     dev = next(mod.parameters()).device
-    return FusedAtrousResNet(_original_view(mod)).to(dev)
+    return (HipAtrousResNet if hip else FusedAtrousResNet)(_original_view(mod)).to(dev)
 
 
-def _build_neck(mod):
-    return fold_sequentials(_original_view(mod))
+def _build_neck(mod, hip=False):
+    return hip_necks(_original_view(mod)) if hip else fold_sequentials(_original_view(mod))
 
 
-def optimize_similarity_model(model, strict: bool = False) -> list:
+def optimize_similarity_model(model, strict: bool = False, hip: bool = None) -> list:
     """Fold / fuse model.backbone, model.neck, model.neck_lp (the reference's ModelBuilder attributes, model_builder…v2.py:44-60) where
     their structure is the reference's; returns the names that were switched.  strict: raise where the structure is not recognised
-    instead of leaving that module as it is.  Eval mode only (BatchNorm statistics are frozen into the weights)."""
+    instead of leaving that module as it is.  Eval mode only (BatchNorm statistics are frozen into the weights).
+    hip (None: HDN_HIP_BACKBONE, default off): the convolutions on hdn_conv1x1_f32 / hdn_conv3x3d_f32 where they have a kernel (HipAtrousResNet,
+    hip_necks); the reload hook re-packs into the same buffers."""
+    import functools
+
+    hip = hip_enabled() if hip is None else bool(hip)
+    build_bb, build_nk = functools.partial(_build_backbone, hip=hip), functools.partial(_build_neck, hip=hip)
     done = []
     with torch.no_grad():
         bb = getattr(model, "backbone", None)
         if isinstance(bb, nn.Module):
             try:
                 _detach(bb)
-                _attach(bb, FusedAtrousResNet(bb), build=_build_backbone)
+                _attach(bb, (HipAtrousResNet if hip else FusedAtrousResNet)(bb), build=build_bb)
                 done.append("backbone")
             except ValueError:
                 if strict:
@@ -265,9 +428,9 @@ def optimize_similarity_model(model, strict: bool = False) -> list:
             nk = getattr(model, name, None)
             if isinstance(nk, nn.Module):
                 _detach(nk)
-                folded = fold_sequentials(nk)
-                if any(isinstance(m, _FoldedConv) for m in folded.modules()):
-                    _attach(nk, folded, build=_build_neck)
+                folded = hip_necks(nk) if hip else fold_sequentials(nk)
+                if any(isinstance(m, (_FoldedConv, _HipConv)) for m in folded.modules()):
+                    _attach(nk, folded, build=build_nk)
                     done.append(name)
                 elif strict:
                     raise ValueError(f"{name}: no Sequential(Conv2d, BatchNorm2d) found")
@@ -283,3 +446,8 @@ def restore_similarity_model(model):
 
 def enabled() -> bool:
     return os.environ.get("HDN_FOLD_BACKBONE", "1") not in ("", "0")
+
+
+def hip_enabled() -> bool:
+    """HDN_HIP_BACKBONE (default off): optimize_similarity_model's `hip` when the caller does not say."""
+    return os.environ.get("HDN_HIP_BACKBONE", "0") not in ("", "0")

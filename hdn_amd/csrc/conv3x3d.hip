@@ -1,0 +1,263 @@
+// conv3x3d.hip — the dilated 3x3 convolutions of the similarity branch's ResNet-50 (stride 8, atrous), bias / ReLU fused, on the matrix cores.
+//
+//   out[B,S,S,CO] = epilogue( conv3x3(x[B,S,S,CI]; stride 1, dilation d, zero padding d) ),   channels-last fp32 in and out, d = 1 / 2 / 4
+//   epilogue: (+ bias[co]) (ReLU)
+//
+// Replaces conv2 + bn2 + relu of a Bottleneck and the 3x3 downsample branches (Conv2d(CI, CO, 3, padding = dilation) + BatchNorm2d) of
+// hdn/models/backbone/resnet_atrous.py:62-110, 152-183 (eval mode, BatchNorm folded by the caller).
+//
+// conv1x1.hip's implicit GEMM run over nine taps: M = B S^2 pixels, N = CO, K = 9 CI, fp32 carried as two fp16 pieces on v_mfma_f32_32x32x16_f16
+// (mfma_split.h: three piece products into "hi" / "lo" accumulators).  D = A . B with A = activations (row = pixel, one lane per (pixel, k half)) and
+// B = packed weights (column = output channel): a lane's accumulator column is ONE output channel.  K walks in STEPS of one tap x 32 input channels,
+// tap-major (step = tap * CI / 32 + chunk, tap = 3 ky + kx); in a step lane (pixel, g) reads the 16 channels [16 g, 16 g + 16) of the pixel at
+// ((ky - 1) d, (kx - 1) d) from its own — under a predicate: a tap that leaves the image loads nothing and contributes zeros (S <= d: only the centre
+// tap is ever in bounds) — and feeds channels 16 g + 8 t + [0, 8) to k step t; the packer (csrc/pack.hip, hdn_pack_conv3x3d_f32) lays the weights out
+// in that order, so they stream L2 -> registers in fragment order, 16 bytes per lane.  The next step's loads are issued before the current step's MFMAs.
+//
+// Workgroup = 4 waves = WM x WN waves of MT x NT 32 x 32 tiles each; every form covers 128 pixels, so at M = 961 (B = 1, side 31) the weights are
+// read 8 times, not 31.  The weight stream is the big operand (1024 -> 2048: 75 MB): the grid is one-dimensional with the PIXEL tile running fastest —
+// workgroups that share a weight tile are neighbours — and remapped so that neighbours share an XCD (and with it an L2) instead of being dealt out
+// round-robin over the eight.  Forms (dispatch()):
+//   A  Cfg<1, 1, 4, 1>   128 pixels x  32 channels   CO not a multiple of 64
+//   B  Cfg<1, 2, 4, 1>   128 pixels x  64 channels   problems that would not give form C one workgroup per CU
+//   C  Cfg<2, 2, 2, 2>   128 pixels x 128 channels   CO a multiple of 128 and at least FILL such workgroups (64 x 64 per wave: half the loads per MFMA)
+// A and B with fewer than FILL workgroups (the tracker's B = 1) split K over grid.y into Z slices of whole steps; every slice writes its joined partial
+// tile to `workspace` [z][M][CO] and conv3x3d_finish_kernel adds the slices in slice order with the bias and the ReLU: deterministic, no atomics.
+#include <climits>
+
+#include "hdn_common.h"
+#include "mfma_split.h"
+
+namespace hdn {
+namespace c3d {
+using namespace hdn::mc;
+
+constexpr int FILL = 256;       // workgroups below which K is split (one per CU)
+constexpr int MAX_Z = 16;       // most K slices
+constexpr int MIN_STEPS = 4;    // fewest K steps worth a slice
+constexpr int NXCD = 8;
+
+template <int MT_, int NT_, int WM_, int WN_>
+struct Cfg {
+  static constexpr int MT = MT_, NT = NT_, WM = WM_, WN = WN_;
+  static constexpr int BM = 32 * MT * WM, BN = 32 * NT * WN;
+  static_assert(WM * WN == 4, "four waves per workgroup");
+};
+
+// FINAL: the whole of K in this workgroup, epilogue here; otherwise slice blockIdx.y of K, raw joined sums to dst = workspace [z][M][CO]
+template <class C, bool SD, bool FINAL>
+__global__ __launch_bounds__(256) void conv3x3d_kernel(const float* __restrict__ x, const u32x4* __restrict__ wp, const float* __restrict__ bias,
+                                                       float* __restrict__ dst, int M, int S, int d, int CI, int CO, int relu, int tm, int sps) {
+  constexpr int MT = C::MT, NT = C::NT, WN = C::WN;
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wn = wave % WN, wm = wave / WN;
+  const int li = lane & 31, g = lane >> 5;
+  // consecutive workgroup ids go to consecutive XCDs: give every XCD a contiguous run of tiles instead (bijective for any grid size)
+  const int nwg = gridDim.x, orig = blockIdx.x, xcd = orig % NXCD, q = nwg / NXCD, r = nwg % NXCD;
+  const int id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + orig / NXCD;
+  const int pm = id % tm, pn = id / tm;                                     // pixel tile fastest: neighbours share the weight tile
+  const int m0 = (pm * C::WM + wm) * (32 * MT);
+  const int nt0 = (pn * WN + wn) * NT;                                      // the wave's first 32-channel output tile
+
+  // this lane's A rows: pixels m0 + 32 i + li (clamped to the last pixel: loaded, never stored)
+  const float* xr[MT];
+  int oy[MT], ox[MT];
+#pragma unroll
+  for (int i = 0; i < MT; ++i) {
+    const int m = min(m0 + 32 * i + li, M - 1), s2 = S * S;
+    const int b = m / s2, rm = m - b * s2;
+    oy[i] = rm / S;
+    ox[i] = rm - oy[i] * S;
+    xr[i] = x + (size_t)m * CI + 16 * g;
+  }
+  const int chunks = CI >> 5, steps = 9 * chunks;
+  const int s0 = FINAL ? 0 : (int)blockIdx.y * sps, s1 = FINAL ? steps : min(steps, s0 + sps);
+  const size_t wtile = (size_t)steps * 4 * 64;                              // u32x4 per 32-channel output tile: [tap][chunk][k step][piece][lane]
+  const u32x4* wl = wp + (size_t)nt0 * wtile + lane;
+
+  f32x16 hi[MT][NT], lo[MT][NT];
+#pragma unroll
+  for (int i = 0; i < MT; ++i)
+#pragma unroll
+    for (int j = 0; j < NT; ++j)
+#pragma unroll
+      for (int rr = 0; rr < 16; ++rr) hi[i][j][rr] = lo[i][j][rr] = 0.f;
+
+  f4 xa[MT][4];
+  u32x4 wa[NT][4];
+  int tap = s0 / chunks, c = s0 - tap * chunks;                             // of the next step to load
+  auto load = [&](int s) {
+    const int ky = tap / 3, kx = tap - 3 * ky, dy = (ky - 1) * d, dx = (kx - 1) * d;
+    const ptrdiff_t off = ((ptrdiff_t)dy * S + dx) * CI + c * 32;
+#pragma unroll
+    for (int i = 0; i < MT; ++i) {
+      const bool in = (unsigned)(oy[i] + dy) < (unsigned)S && (unsigned)(ox[i] + dx) < (unsigned)S;
+      const f4* xs = reinterpret_cast<const f4*>(xr[i] + off);
+#pragma unroll
+      for (int qq = 0; qq < 4; ++qq) xa[i][qq] = in ? xs[qq] : f4{0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int j = 0; j < NT; ++j)
+#pragma unroll
+      for (int qq = 0; qq < 4; ++qq) wa[j][qq] = wl[(size_t)j * wtile + ((size_t)s * 4 + qq) * 64];
+    if (++c == chunks) { c = 0; ++tap; }
+  };
+  load(s0);
+  for (int s = s0; s < s1; ++s) {
+    f4 xv[MT][4];
+    u32x4 wv[NT][4];
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+      for (int qq = 0; qq < 4; ++qq) xv[i][qq] = xa[i][qq];
+#pragma unroll
+    for (int j = 0; j < NT; ++j)
+#pragma unroll
+      for (int qq = 0; qq < 4; ++qq) wv[j][qq] = wa[j][qq];
+    if (s + 1 < s1) load(s + 1);
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int i = 0; i < MT; ++i) {
+        unsigned q0[4], q1[4];                                              // the two pieces of channels 16 g + 8 t + [0, 8)
+        const f4 u = xv[i][2 * t], v = xv[i][2 * t + 1];
+        split2<SD>(f2{u.x, u.y}, q0[0], q1[0]);
+        split2<SD>(f2{u.z, u.w}, q0[1], q1[1]);
+        split2<SD>(f2{v.x, v.y}, q0[2], q1[2]);
+        split2<SD>(f2{v.z, v.w}, q0[3], q1[3]);
+        const u32x4 a0{q0[0], q0[1], q0[2], q0[3]}, a1{q1[0], q1[1], q1[2], q1[3]};
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+          hi[i][j] = mfma(a0, wv[j][2 * t], hi[i][j]);
+          lo[i][j] = mfma(a0, wv[j][2 * t + 1], lo[i][j]);
+          lo[i][j] = mfma(a1, wv[j][2 * t], lo[i][j]);
+        }
+      }
+  }
+
+  // epilogue: register r of a lane is pixel m0 + 32 i + (r & 3) + 8 (r >> 2) + 4 g, output channel 32 (nt0 + j) + li
+  float* o = FINAL ? dst : dst + (size_t)blockIdx.y * M * CO;
+#pragma unroll
+  for (int j = 0; j < NT; ++j) {
+    const int co = (nt0 + j) * 32 + li;
+    const float bv = (FINAL && bias) ? bias[co] : 0.f;
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+      for (int rr = 0; rr < 16; ++rr) {
+        const int mm = m0 + 32 * i + (rr & 3) + 8 * (rr >> 2) + 4 * g;
+        if (mm < M) {
+          float v = join<SD>(hi[i][j][rr], lo[i][j][rr]);
+          if (FINAL) {
+            v += bv;
+            if (relu) v = fmaxf(v, 0.f);
+          }
+          o[(size_t)mm * CO + co] = v;
+        }
+      }
+  }
+}
+
+// out = [relu](slice 0 + slice 1 + ... (+ bias)), in slice order; n4 = M CO / 4 (16-byte items), CO a multiple of 4
+__global__ __launch_bounds__(HDN_BLOCK) void conv3x3d_finish_kernel(const f4* __restrict__ ws, const float* __restrict__ bias, f4* __restrict__ out,
+                                                                   long long n4, int CO, int Z, int relu) {
+  const long long i = (long long)blockIdx.x * HDN_BLOCK + threadIdx.x;
+  if (i >= n4) return;
+  f4 v = ws[i];
+  for (int z = 1; z < Z; ++z) v = v + ws[(long long)z * n4 + i];
+  if (bias) v = v + *reinterpret_cast<const f4*>(bias + (int)((i * 4) % CO));
+  if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+  out[i] = v;
+}
+
+// K steps per slice for a form that gives `wgs` workgroups over `steps` K steps (steps: one slice, no workspace)
+static int steps_per_slice(long long wgs, int steps) {
+  if (wgs >= FILL) return steps;
+  long long z = (FILL + wgs - 1) / wgs;
+  if (z > MAX_Z) z = MAX_Z;
+  if (z > steps / MIN_STEPS) z = steps / MIN_STEPS;
+  if (z < 1) z = 1;
+  return (steps + (int)z - 1) / (int)z;
+}
+
+// the schedule for a problem: f(Cfg<...>{}, K steps per slice) with the form chosen as described at the top
+template <class F>
+static long long dispatch(long long M, int CI, int CO, F&& f) {
+  const int steps = 9 * (CI / 32);
+  const long long tm = (M + 127) / 128;
+  if (CO % 64) return f(Cfg<1, 1, 4, 1>{}, steps_per_slice(tm * (CO / 32), steps));
+  if (CO % 128 == 0 && tm * (CO / 128) >= FILL) return f(Cfg<2, 2, 2, 2>{}, steps);
+  return f(Cfg<1, 2, 4, 1>{}, steps_per_slice(tm * (CO / 64), steps));
+}
+
+template <class C, bool SD>
+static int launch(const float* x, const void* wp, const float* bias, float* out, float* ws, int M, int S, int d, int CI, int CO, int relu, int sps,
+                  hipStream_t s) {
+  const int steps = 9 * (CI / 32), Z = cdiv(steps, sps), tm = cdiv(M, C::BM);
+  const dim3 grid((unsigned)((long long)tm * (CO / C::BN)), (unsigned)Z);
+  const u32x4* w = static_cast<const u32x4*>(wp);
+  if (Z == 1) {
+    hipLaunchKernelGGL((conv3x3d_kernel<C, SD, true>), grid, dim3(256), 0, s, x, w, bias, out, M, S, d, CI, CO, relu, tm, sps);
+    return launch_status();
+  }
+  hipLaunchKernelGGL((conv3x3d_kernel<C, SD, false>), grid, dim3(256), 0, s, x, w, bias, ws, M, S, d, CI, CO, relu, tm, sps);
+  if (const int rc = launch_status()) return rc;
+  const long long n4 = (long long)M * CO / 4;
+  hipLaunchKernelGGL(conv3x3d_finish_kernel, dim3((unsigned)((n4 + HDN_BLOCK - 1) / HDN_BLOCK)), dim3(HDN_BLOCK), 0, s, reinterpret_cast<const f4*>(ws),
+                     bias, reinterpret_cast<f4*>(out), n4, CO, Z, relu);
+  return launch_status();
+}
+
+// HDN_OK, or what the entry point answers for a shape it does not take
+static int check_shape(int B, int S, int CI, int CO, int d) {
+  if (B <= 0 || S <= 0 || CI <= 0 || CO <= 0 || CI % 32 || CO % 32 || (d != 1 && d != 2 && d != 4)) return HDN_E_SHAPE;
+  const long long m = (long long)B * S * S;
+  if (m * CI > INT_MAX || m * CO > INT_MAX || 9LL * CI * CO > INT_MAX) return HDN_E_LIMIT;
+  return HDN_OK;
+}
+
+}  // namespace c3d
+}  // namespace hdn
+
+// the launch form dispatch() picks for a problem, for tests and profiles: MT | NT << 4 | WM << 8 | WN << 12 | (K slices Z) << 16.  Host only.
+extern "C" int hdn_conv3x3d_form(int B, int S, int CI, int CO, int dilation) {
+  if (const int rc = hdn::c3d::check_shape(B, S, CI, CO, dilation)) return rc;
+  return (int)hdn::c3d::dispatch((long long)B * S * S, CI, CO, [&](auto cfg, int sps) -> long long {
+    using C = decltype(cfg);
+    return C::MT | C::NT << 4 | C::WM << 8 | C::WN << 12 | hdn::cdiv(9 * (CI / 32), sps) << 16;
+  });
+}
+
+extern "C" long long hdn_conv3x3d_workspace_bytes(int B, int S, int CI, int CO, int dilation) {
+  if (const int rc = hdn::c3d::check_shape(B, S, CI, CO, dilation)) return rc;
+  const long long M = (long long)B * S * S;
+  return hdn::c3d::dispatch(M, CI, CO, [&](auto, int sps) -> long long {
+    const int Z = hdn::cdiv(9 * (CI / 32), sps);
+    return Z > 1 ? Z * M * CO * 4 : 0;
+  });
+}
+
+// wpacked (hdn_pack_conv3x3d_f32): [CO / 32 n tiles][9 taps][CI / 32 chunks][2 k steps t][2 pieces][k half g][32 n][8] fp16; element e of lane (g, n) =
+// piece of w[co = 32 tile + n][ci = 32 chunk + 16 g + 8 t + e][tap = 3 ky + kx]
+extern "C" int hdn_conv3x3d_f32(const float* x, const void* wpacked, const float* bias, float* out, void* ws, long long ws_bytes, int B, int S, int CI,
+                                int CO, int dilation, int relu, int act_domain, void* stream) {
+  if (!x || !wpacked || !out) return HDN_E_NULL;
+  if ((relu != 0 && relu != 1) || (act_domain != 0 && act_domain != 1)) return HDN_E_SHAPE;
+  if (const int rc = hdn::c3d::check_shape(B, S, CI, CO, dilation)) return rc;
+  const long long M = (long long)B * S * S, nx = M * CI, nout = M * CO;
+  if (hdn::bytes_overlap(out, nout * 4, x, nx * 4)) return HDN_E_ALIAS;
+  if (!hdn::aligned16(x) || !hdn::aligned16(wpacked) || !hdn::aligned16(out) || (bias && !hdn::aligned16(bias))) return HDN_E_LIMIT;
+  const long long need = hdn_conv3x3d_workspace_bytes(B, S, CI, CO, dilation);
+  if (need > 0) {
+    if (!ws) return HDN_E_NULL;
+    if (!hdn::aligned16(ws) || ws_bytes < need) return HDN_E_LIMIT;
+    if (hdn::bytes_overlap(ws, need, x, nx * 4) || hdn::bytes_overlap(ws, need, out, nout * 4)) return HDN_E_ALIAS;
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (const int rr = hdn::check_fp16_range(x, nx, s, act_domain)) return rr;
+  return (int)hdn::c3d::dispatch(M, CI, CO, [&](auto cfg, int sps) -> long long {
+    using C = decltype(cfg);
+    return act_domain ? hdn::c3d::launch<C, true>(x, wpacked, bias, out, static_cast<float*>(ws), (int)M, S, dilation, CI, CO, relu, sps, s)
+                      : hdn::c3d::launch<C, false>(x, wpacked, bias, out, static_cast<float*>(ws), (int)M, S, dilation, CI, CO, relu, sps, s);
+  });
+}

@@ -14,6 +14,7 @@
 //   hdn_pack_head_tail_f32      -> w1_packed of hdn_head_tail_f32                                      (G x [H, H] 1x1 convolutions)
 //   hdn_pack_conv1x1_f32        -> wpacked of hdn_conv1x1_f32                                          (Conv2d(CI, CO, 1, s) of a Bottleneck)
 //   hdn_pack_conv3x3s2_f32      -> wpacked of hdn_conv3x3s2_f32                                        (Conv2d(C, C, 3, 2, 1) of a Bottleneck)
+//   hdn_pack_conv3x3d_f32       -> wpacked of hdn_conv3x3d_f32                                         (Conv2d(CI, CO, 3, 1, d, d) of the atrous backbone)
 //
 // All pointers are HOST pointers.  Every stream is 2 pieces x 2 bytes per (padded) weight: v = p0 + 2^-11 p1, p0 = fp16(v),
 // p1 = fp16((v - p0) 2^11), round-to-nearest-even each (csrc/mfma_split.h; weights are NOT pre-scaled, only activations are).
@@ -237,6 +238,29 @@ extern "C" int hdn_pack_conv3x3s2_f32(const float* w, int C, void* out, long lon
         const long long o = ((((static_cast<long long>(nb) * chunks + chunk) * 9 + tap) * 2 + nt) * 2 + ks) * 2;
         const long long tail = 2LL * 32 * 8, in = (static_cast<long long>(g) * 32 + n) * 8 + e;
         s.put((o + 0) * tail + in, (o + 1) * tail + in, w[(static_cast<long long>(co) * C + ci) * 9 + tap]);
+      }
+  return s.ok ? HDN_OK : HDN_E_LIMIT;
+}
+
+extern "C" long long hdn_pack_conv3x3d_bytes(int CO, int CI) {
+  return (CO > 0 && CI > 0 && CO % 32 == 0 && CI % 32 == 0 && 9LL * CO * CI <= 0x7fffffffLL) ? 2LL * 2 * 9 * CO * CI : HDN_E_SHAPE;
+}
+
+// w [CO][CI][3][3] -> [CO / 32 n tiles][9 taps][CI / 32 chunks][2 k steps t][piece][k half g][32 n][8]: element e of lane (g, n) =
+// w[32 tile + n][32 chunk + 16 g + 8 t + e][tap = 3 ky + kx] — hdn_pack_conv1x1_f32's fragment order, tap-major inside an n tile (conv3x3d.hip: a K step
+// is one tap x 32 input channels, step = tap * CI / 32 + chunk; the dilation is the kernel's argument, not the stream's)
+extern "C" int hdn_pack_conv3x3d_f32(const float* w, int CO, int CI, void* out, long long out_bytes) {
+  if (!w || !out) return HDN_E_NULL;
+  if (hdn_pack_conv3x3d_bytes(CO, CI) < 0 || out_bytes != hdn_pack_conv3x3d_bytes(CO, CI)) return HDN_E_SHAPE;
+  const int chunks = CI / 32;
+  Sink s{static_cast<uint16_t*>(out)};
+  for (int co = 0; co < CO; ++co)
+    for (int ci = 0; ci < CI; ++ci)
+      for (int tap = 0; tap < 9; ++tap) {
+        const int nt = co / 32, n = co & 31, chunk = ci / 32, g = (ci / 16) & 1, t = (ci / 8) & 1, e = ci & 7;
+        const long long o = (((static_cast<long long>(nt) * 9 + tap) * chunks + chunk) * 2 + t) * 2;
+        const long long tail = 2LL * 32 * 8, in = (static_cast<long long>(g) * 32 + n) * 8 + e;
+        s.put((o + 0) * tail + in, (o + 1) * tail + in, w[(static_cast<long long>(co) * CI + ci) * 9 + tap]);
       }
   return s.ok ? HDN_OK : HDN_E_LIMIT;
 }

@@ -658,6 +658,47 @@ def conv3x3s2(x, wpacked, bias, act_domain=0):
     return out
 
 
+def pack_conv3x3d(weight):
+    """[CO, CI, 3, 3] fp32 weights of a stride-1 convolution with padding == dilation (any of 1 / 2 / 4: the stream is the same), BatchNorm folded in,
+    CO and CI multiples of 32 -> the stream hdn_conv3x3d_f32 takes (hdn_pack_conv3x3d_f32)."""
+    from . import _lib
+
+    CO, CI = weight.shape[0], weight.shape[1]
+    if tuple(weight.shape) != (CO, CI, 3, 3):
+        raise ValueError(f"pack_conv3x3d takes [CO, CI, 3, 3] weights, got {tuple(weight.shape)}")
+    lib, w = _lib.load(), _host_f32(weight)
+    return _c_pack("pack_conv3x3d", lib.hdn_pack_conv3x3d_bytes(CO, CI), lambda o, n: lib.hdn_pack_conv3x3d_f32(w.data_ptr(), CO, CI, o, n))
+
+
+def conv3x3d(x, wpacked, bias, dilation=1, relu=True, act_domain=0):
+    """[relu](conv3x3 / stride 1 / dilation / padding = dilation (x) [+ bias]) through hdn_conv3x3d_f32; x channels-last [B,CI,S,S] float32 -> channels-last
+    [B,CO,S,S]; `wpacked` from pack_conv3x3d, on x's device (CO is read off its size); bias [CO] or None (zero).  act_domain as conv3x3_bias_relu's."""
+    import torch
+
+    from . import _lib
+
+    dev = _lib.require_device(x) if bias is None else _lib.require_device(x, bias)
+    cl = torch.channels_last
+    if x.dim() != 4 or x.dtype != torch.float32 or x.shape[2] != x.shape[3] or not x.is_contiguous(memory_format=cl):
+        raise ValueError("conv3x3d: square channels-last float32 input [B,CI,S,S]")
+    B, CI, S, _ = x.shape
+    CO = wpacked.numel() // (9 * SPLIT_PIECES * CI) if CI else 0
+    if wpacked.dtype != torch.int16 or wpacked.device != dev or CO <= 0 or wpacked.numel() != 9 * SPLIT_PIECES * CO * CI or (bias is not None and bias.numel() != CO):
+        raise ValueError("conv3x3d: weights must come from pack_conv3x3d for this CI (and the bias's CO), on the input's device")
+    lib = _lib.load()
+    nws = lib.hdn_conv3x3d_workspace_bytes(B, S, CI, CO, int(dilation))
+    if nws < 0:
+        _lib.check(int(nws), "conv3x3d")
+    out = torch.empty((B, CO, S, S), dtype=torch.float32, device=dev, memory_format=cl)
+    ws = torch.empty(nws // 4, dtype=torch.float32, device=dev) if nws else None   # (from torch's caching allocator: no sync, graph-safe)
+    with _lib.device_guard(dev):
+        rc = lib.hdn_conv3x3d_f32(_lib.ptr(x), _lib.ptr(wpacked), _lib.ptr(bias) if bias is not None else None, _lib.ptr(out),
+                                  _lib.ptr(ws) if ws is not None else None, nws, B, S, CI, CO, int(dilation), int(bool(relu)), int(act_domain),
+                                  _lib.stream_ptr(dev))
+    _lib.check(rc, "conv3x3d")
+    return out
+
+
 class FusedBottleneck(nn.Module):
     """Bottleneck.forward (backbone/resnet.py:113-133) of the BN-folded homography trunk: conv1 1x1 + bias + ReLU, conv2 3x3 + bias + ReLU,
     conv3 1x1 + bias + residual + ReLU, the residual being the input or the folded downsample branch (1x1 / stride, bias, no ReLU).  The 1x1

@@ -431,7 +431,7 @@ int hdn_head_conv3x3_f32(const float* const* xs, const void* w_packed, const flo
  * addition and hdn_bias_relu_f32 / hdn_conv3x3_finish_f32 are the same in either domain (they are positively homogeneous / linear with the scaled bias).
  *
  * Range guard of the two-fp16-piece kernels (ABI 6): hdn_conv3x3_bias_relu_f32, hdn_conv3x3s2_ds_f32, hdn_conv3x3_v2_f32,
- * hdn_conv3x3_chain_f32 (activation inputs), hdn_trunk_stem_mfma_f32, hdn_head_conv3x3_f32, hdn_head_tail_f32, hdn_conv1x1_f32 and hdn_conv3x3s2_f32 are finite and fp32-accurate
+ * hdn_conv3x3_chain_f32 (activation inputs), hdn_trunk_stem_mfma_f32, hdn_head_conv3x3_f32, hdn_head_tail_f32, hdn_conv1x1_f32, hdn_conv3x3s2_f32 and hdn_conv3x3d_f32 are finite and fp32-accurate
  * for |x| < 1.67e7 on their fp32 INPUTS by default (since ABI 9; 65,504 before).  Beyond that the first fp16 piece is inf and the result NaN,
  * where the reference's fp32 convolution stays finite up to 3.4e38.  With HDN_CHECK_RANGE=1 in the environment, or after hdn_set_check_range(1)
  * (returns the previous setting), each of those entry points first reduces max |x| over its input and returns HDN_E_LIMIT when it is
@@ -466,6 +466,7 @@ int hdn_xcorr_north_launch_events(void* start_event, void* stop_event);
  *   hdn_pack_head_tail_f32     w1 [G][H][H]                            -> hdn_head_tail_f32 (ban.py:60-66)
  *   hdn_pack_conv1x1_f32       w [CO][CI]                              -> hdn_conv1x1_f32 (backbone/resnet.py:97-133, 162-176), CO, CI multiples of 32
  *   hdn_pack_conv3x3s2_f32     w [C][C][3][3]                          -> hdn_conv3x3s2_f32 (backbone/resnet.py:97-133 conv2 at stride 2), C = 128 / 256 / 512
+ *   hdn_pack_conv3x3d_f32      w [CO][CI][3][3]                        -> hdn_conv3x3d_f32 (hdn/models/backbone/resnet_atrous.py:62-110, 152-183), CO, CI multiples of 32
  */
 long long hdn_pack_conv3x3_bytes(int C);
 int hdn_pack_conv3x3_f32(const float* w, int C, void* out, long long out_bytes);
@@ -485,6 +486,8 @@ long long hdn_pack_conv1x1_bytes(int CO, int CI);
 int hdn_pack_conv1x1_f32(const float* w, int CO, int CI, void* out, long long out_bytes);
 long long hdn_pack_conv3x3s2_bytes(int C);
 int hdn_pack_conv3x3s2_f32(const float* w, int C, void* out, long long out_bytes);
+long long hdn_pack_conv3x3d_bytes(int CO, int CI);                                              /* resnet_atrous.py:62-110, 152-183 */
+int hdn_pack_conv3x3d_f32(const float* w, int CO, int CI, void* out, long long out_bytes);      /* resnet_atrous.py:62-110, 152-183 */
 
 int hdn_conv3x3_pack_info(int S, int CI, int stride, int* block_n, int* k_steps);
 long long hdn_conv3x3_workspace_bytes(int B, int S, int CI, int stride);
@@ -561,6 +564,28 @@ int hdn_conv1x1_form(int B, int S, int CI, int CO, int stride);
 long long hdn_conv3x3s2_workspace_bytes(int B, int S, int C);
 int hdn_conv3x3s2_f32(const float* x, const void* wpacked, const float* bias, float* out, float* workspace, long long workspace_bytes, int B, int S, int C,
                       int act_domain, void* stream);
+
+/*
+ * Dilated 3x3 convolution of the similarity branch's atrous ResNet-50, bias and ReLU fused (conv3x3d.hip; added in ABI 10):
+ *   out[B,S,S,CO] = [relu]( conv3x3 / stride 1 / dilation d / zero padding d (x[B,S,S,CI], w[CO][CI][3][3]) [+ bias[co]] ),   channels-last fp32,
+ * d = 1 / 2 / 4, CI and CO multiples of 32, any B >= 1 and S >= 1 (S <= d: only the centre tap is in bounds), relu and act_domain 0 / 1 (else
+ * HDN_E_SHAPE); more than 2^31 - 1 elements in x or out, a pointer that is not 16-byte aligned or a workspace that is too small: HDN_E_LIMIT.  `bias` may
+ * be NULL (zero: a downsample branch, whose shift rides in the block's last bias).  `out` may overlap neither `x` nor `ws`, `ws` not `x` (HDN_E_ALIAS).
+ * act_domain as above ("Activation domain").  fp32 carried as two fp16 pieces, three products, hi / lo fp32 accumulators: the error of an fp32
+ * convolution.  Deterministic: K runs tap-major (tap = 3 ky + kx, inside a tap chunks of 32 input channels, the two 16-channel k steps of a chunk); where
+ * the output tiles do not fill the chip K is split over workgroups into slices of whole (tap, chunk) steps, the slices' partial sums go to `ws` and a second
+ * launch adds them in slice order with the bias and the ReLU.  No atomics.
+ * hdn_conv3x3d_workspace_bytes: bytes needed, 0 = none (ws may be NULL then), negative = HDN_E_*.
+ * hdn_conv3x3d_form: the launch form for a problem, MT | NT << 4 | WM << 8 | WN << 12 | (K slices) << 16 (conv3x3d.hip, Cfg<MT, NT, WM, WN>: 32 x 32 tiles per
+ * wave, waves per workgroup), or HDN_E_* as the entry point answers; host only, nothing is launched; for tests and profiles, no part of the ABI.
+ * Takes part in the range guard (hdn_set_check_range) on `x`.  Asynchronous on `stream`; allocates nothing.
+ * wpacked: the stream hdn_pack_conv3x3d_f32 wrote from the BatchNorm-folded w (opaque; the same stream serves every dilation).
+ * Replaces conv2 + bn2 + relu of a Bottleneck and the 3x3 downsample branches of hdn/models/backbone/resnet_atrous.py:62-110, 152-183 (eval mode only).
+ */
+long long hdn_conv3x3d_workspace_bytes(int B, int S, int CI, int CO, int dilation);             /* resnet_atrous.py:62-110, 152-183 */
+int hdn_conv3x3d_form(int B, int S, int CI, int CO, int dilation);                              /* resnet_atrous.py:62-110, 152-183 */
+int hdn_conv3x3d_f32(const float* x, const void* wpacked, const float* bias, float* out, void* ws, long long ws_bytes, int B, int S, int CI, int CO,
+                     int dilation, int relu, int act_domain, void* stream);                     /* resnet_atrous.py:62-110, 152-183 */
 
 /* The compile-time exponent of the activation scale (csrc/mfma_split.h, HDN_ACT_SCALE_LOG2; 8): callers that hand over pre-scaled biases in
  * act_domain = 1 check it against the value they scale with (hdn_amd.trunk.ACT_SCALE_LOG2). */
