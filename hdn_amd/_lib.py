@@ -88,6 +88,12 @@ SIGNATURES = {
     "hdn_conv3x3d_workspace_bytes": (ctypes.c_longlong, [_i] * 5),
     "hdn_conv3x3d_form": (_i, [_i] * 5),
     "hdn_conv3x3d_f32": (_i, [_c_float_p, ctypes.c_void_p, _c_float_p, _c_float_p, ctypes.c_void_p, ctypes.c_longlong] + [_i] * 7 + [ctypes.c_void_p]),
+    "hdn_conv3x3v_workspace_bytes": (ctypes.c_longlong, [_i] * 5),
+    "hdn_conv3x3v_form": (_i, [_i] * 5),
+    "hdn_conv3x3v_f32": (_i, [_c_float_p, ctypes.c_void_p, _c_float_p, _c_float_p, ctypes.c_void_p, ctypes.c_longlong] + [_i] * 7 + [ctypes.c_void_p]),
+    "hdn_pack_simi_stem_bytes": (ctypes.c_longlong, []),
+    "hdn_pack_simi_stem_f32": (_i, [_c_float_p, ctypes.c_void_p, ctypes.c_longlong]),
+    "hdn_simi_stem_f32": (_i, [_c_float_p, ctypes.c_void_p, _c_float_p, _c_float_p] + [_i] * 3 + [ctypes.c_void_p]),
     "hdn_conv3x3s2_f32": (_i, [_c_float_p, ctypes.c_void_p] + [_c_float_p] * 3 + [ctypes.c_longlong] + [_i] * 4 + [ctypes.c_void_p]),
     "hdn_act_scale_log2": (_i, []),
     "hdn_ubench_copy_f32": (_i, [_c_float_p] * 2 + [ctypes.c_longlong, ctypes.c_void_p]),

@@ -29,6 +29,11 @@ puts the convolutions themselves on the library's two-fp16-piece matrix-core ker
 every 1x1 convolution on hdn_conv1x1_f32, every stride-1 3x3 convolution with padding == dilation in {1, 2, 4} on hdn_conv3x3d_f32, channels-last between
 the maxpool and the necks' outputs.  Convolutions without a kernel (the 7x7 stem; the stride-2, padding-0 first block of layer2 with its strided 3x3 skip)
 stay on MIOpen as above.  hip_plan(net) names the kernel of every convolution without building anything.
+
+    optimize_similarity_model(model, hip=2)         # or HDN_HIP_BACKBONE=2 (default off)
+
+is level 2 of the same form, with no library convolution left: the two padding-0 3x3 convolutions of layer2's first block on hdn_conv3x3v_f32 and
+conv1 + bn1 + ReLU + maxpool as ONE launch of hdn_simi_stem_f32 (HipAtrousResNetFull).  Level 1 is unchanged by it.
 """
 from __future__ import annotations
 
@@ -184,10 +189,10 @@ def fold_sequentials(module: nn.Module, hip: bool = False) -> nn.Module:
 
 
 # --------------------------------------------------------------------------------------------------------- the opt-in HIP form (hip=True)
-def hip_conv_kind(conv) -> str:
+def hip_conv_kind(conv, level: int = 1) -> str:
     """The kernel a folded convolution of the backbone / necks runs on in the HIP form: "conv1x1" (hdn_conv1x1_f32: 1x1, stride 1 or 2, no padding),
     "conv3x3d" (hdn_conv3x3d_f32: 3x3, stride 1, padding == dilation in {1, 2, 4}) — both with channel counts that are multiples of 32 — or "miopen"
-    (F.conv2d + hdn_bias_relu_f32, as in the folded form)."""
+    (F.conv2d + hdn_bias_relu_f32, as in the folded form).  level 2 adds "conv3x3v" (hdn_conv3x3v_f32: 3x3, stride 1 or 2, padding 0, dilation 1)."""
     if not isinstance(conv, nn.Conv2d) or conv.groups != 1 or conv.in_channels % 32 or conv.out_channels % 32 or conv.padding_mode != "zeros":
         return "miopen"
     k, st, pad, dil = conv.kernel_size, conv.stride, conv.padding, conv.dilation
@@ -195,37 +200,58 @@ def hip_conv_kind(conv) -> str:
         return "conv1x1"
     if k == (3, 3) and st == (1, 1) and dil in ((1, 1), (2, 2), (4, 4)) and pad == dil:
         return "conv3x3d"
+    if level >= 2 and k == (3, 3) and st in ((1, 1), (2, 2)) and dil == (1, 1) and pad == (0, 0):
+        return "conv3x3v"
     return "miopen"
 
 
-def hip_plan(net) -> dict:
+def _pair(v):
+    return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+
+
+def simi_stem_ok(net) -> bool:
+    """Does hdn_simi_stem_f32 serve this network's first stage?  conv1 = Conv2d(3, 64, 7, stride 2, padding 0, groups 1), maxpool = MaxPool2d(3, 2, 1)
+    without dilation or ceil mode, and the stem's own output is not returned (0 not in used_layers)."""
+    c, mp = getattr(net, "conv1", None), getattr(net, "maxpool", None)
+    if not isinstance(c, nn.Conv2d) or not isinstance(mp, nn.MaxPool2d) or 0 in list(getattr(net, "used_layers", [0])):
+        return False
+    conv_ok = (c.in_channels == 3 and c.out_channels == 64 and c.kernel_size == (7, 7) and c.stride == (2, 2) and c.padding == (0, 0)
+               and c.dilation == (1, 1) and c.groups == 1 and c.padding_mode == "zeros")
+    pool_ok = (_pair(mp.kernel_size) == (3, 3) and _pair(mp.stride) == (2, 2) and _pair(mp.padding) == (1, 1) and _pair(mp.dilation) == (1, 1)
+               and not mp.ceil_mode and not mp.return_indices)
+    return conv_ok and pool_ok
+
+
+def hip_plan(net, level: int = 1) -> dict:
     """{"layerN.M.conv1" / ".conv2" / ".conv3" / ".downsample": hip_conv_kind} for every block of a network of the reference's ResNet layout (reads
-    the structure only: no weights are folded or packed, no device is needed)."""
+    the structure only: no weights are folded or packed, no device is needed).  level 2 adds "stem": "simi_stem" (hdn_simi_stem_f32) or "miopen"."""
     plan = {}
+    if level >= 2:
+        plan["stem"] = "simi_stem" if simi_stem_ok(net) else "miopen"
     for name in ("layer1", "layer2", "layer3", "layer4"):
         layer = getattr(net, name, None)
         if not isinstance(layer, nn.Sequential):
             continue
         for i, blk in enumerate(layer):
             for cn in ("conv1", "conv2", "conv3"):
-                plan[f"{name}.{i}.{cn}"] = hip_conv_kind(getattr(blk, cn, None))
+                plan[f"{name}.{i}.{cn}"] = hip_conv_kind(getattr(blk, cn, None), level)
             pair = _conv_bn_pair(getattr(blk, "downsample", None))
             if pair is not None:
-                plan[f"{name}.{i}.downsample"] = hip_conv_kind(pair[0])
+                plan[f"{name}.{i}.downsample"] = hip_conv_kind(pair[0], level)
     return plan
 
 
 class _HipConv(nn.Module):
     """A convolution with a BatchNorm folded in, on the kernel hip_conv_kind names: the packed stream (a non-persistent buffer, so it moves with .to()
     and a reload re-packs into the same storage) instead of the fp32 weights; a "miopen" one keeps the folded weights and F.conv2d.  Channels-last in
-    and out.  run(x, bias, residual, relu): [relu](conv(x) [+ bias] [+ residual])."""
+    and out.  run(x, bias, residual, relu): [relu](conv(x) [+ bias] [+ residual]).  level: hip_conv_kind's (2: "conv3x3v", on the "conv3x3d" stream)."""
 
-    def __init__(self, conv, bn):
+    def __init__(self, conv, bn, level=1):
         super().__init__()
         from . import trunk as T
 
         w, b = fold_conv_bn(conv, bn)
-        self.kind = hip_conv_kind(conv)
+        self.kind = hip_conv_kind(conv, level)
         self.stride, self.padding, self.dilation = conv.stride, conv.padding, conv.dilation
         self.register_buffer("bias", b)
         if self.kind == "miopen":
@@ -242,8 +268,10 @@ class _HipConv(nn.Module):
             return T.conv1x1(x, self.packed, self.bias if bias is None else bias, residual, stride=self.stride[0], relu=relu)
         if self.kind == "conv3x3d" and residual is None:
             return T.conv3x3d(x, self.packed, bias, dilation=self.dilation[0], relu=relu)
+        if self.kind == "conv3x3v" and residual is None:
+            return T.conv3x3v(x, self.packed, bias, stride=self.stride[0], relu=relu)
         if self.kind != "miopen":
-            raise ValueError("hdn_conv3x3d_f32 takes no residual")
+            raise ValueError("hdn_conv3x3d_f32 / hdn_conv3x3v_f32 take no residual")
         y = F.conv2d(x, self.weight, None, self.stride, self.padding, self.dilation).contiguous(memory_format=torch.channels_last)
         if relu:
             return T.bias_relu_(y, bias, residual)
@@ -262,14 +290,15 @@ class HipBottleneck(nn.Module):
     """Bottleneck.forward (resnet_atrous.py:87-108) of a block whose BatchNorms are folded, channels-last inside: conv1 + shift + ReLU and conv3 + shift +
     residual + ReLU as one hdn_conv1x1_f32 launch each (as hdn_amd.trunk.FusedBottleneck fuses them), conv2 + shift + ReLU as one hdn_conv3x3d_f32 launch;
     a 1x1 downsample branch is a hdn_conv1x1_f32 launch with its own shift, a 3x3 one a bias-free hdn_conv3x3d_f32 launch whose shift rides in the last
-    bias (b3).  A convolution without a kernel (hip_conv_kind: "miopen") runs bias-free on F.conv2d with one hdn_bias_relu_f32 pass behind it."""
+    bias (b3).  A convolution without a kernel (hip_conv_kind: "miopen") runs bias-free on F.conv2d with one hdn_bias_relu_f32 pass behind it.
+    level 2: a padding-0 3x3 conv2 / skip runs on hdn_conv3x3v_f32 the same way (conv2 with its shift and ReLU, the skip bias-free)."""
 
-    def __init__(self, blk):
+    def __init__(self, blk, level=1):
         super().__init__()
         for name in ("conv1", "bn1", "conv2", "bn2", "conv3", "bn3"):
             if not hasattr(blk, name):
                 raise ValueError(f"not a Bottleneck: no {name}")
-        self.c1, self.c2, self.c3 = _HipConv(blk.conv1, blk.bn1), _HipConv(blk.conv2, blk.bn2), _HipConv(blk.conv3, blk.bn3)
+        self.c1, self.c2, self.c3 = _HipConv(blk.conv1, blk.bn1, level), _HipConv(blk.conv2, blk.bn2, level), _HipConv(blk.conv3, blk.bn3, level)
         down = getattr(blk, "downsample", None)
         if down is None:
             self.cd = None
@@ -278,7 +307,7 @@ class HipBottleneck(nn.Module):
             pair = _conv_bn_pair(down)
             if pair is None:
                 raise ValueError("Bottleneck.downsample is not Sequential(Conv2d, BatchNorm2d)")
-            self.cd = _HipConv(*pair)
+            self.cd = _HipConv(*pair, level)
             # a 1x1 branch adds its own shift in its launch; any other hands it to the last pass: (b3 + b_downsample) once
             self.register_buffer("b3", self.c3.bias.clone() if self.cd.kind == "conv1x1" else self.c3.bias + self.cd.bias)
 
@@ -308,6 +337,42 @@ class HipAtrousResNet(FusedAtrousResNet):
         out = [x_, p1, p2, p3, p4]
         out = [out[i] for i in self.used_layers]
         return out[0] if len(out) == 1 else out
+
+
+def _bottleneck_level2(blk):
+    return HipBottleneck(blk, level=2)
+
+
+class HipAtrousResNetFull(HipAtrousResNet):
+    """Level 2 of the HIP form: HipBottleneck blocks at level 2 (no "miopen" convolution left in the reference's layout) and, where simi_stem_ok(net),
+    conv1 + shift + ReLU + maxpool as one hdn_simi_stem_f32 launch on the NCHW input, channels-last out: the packed stream is a non-persistent buffer
+    (`stem_packed`; state_dict keys unchanged, a reload re-packs into the same storage), the folded shift is c1.bias.  A network the fused stem does not
+    serve — and an input that is not square with a side of 7 .. trunk.SIMI_STEM_MAX_SIDE — runs the level-1 stem."""
+
+    block = staticmethod(_bottleneck_level2)
+
+    def __init__(self, net):
+        super().__init__(net)
+        from . import trunk as T
+
+        self.fused_stem = simi_stem_ok(net)
+        self.register_buffer("stem_packed", T.pack_simi_stem(self.c1.weight).to(self.c1.weight.device) if self.fused_stem else None, persistent=False)
+
+    def forward(self, x):
+        from . import trunk as T
+
+        if not (self.fused_stem and x.dim() == 4 and x.shape[2] == x.shape[3] and 7 <= x.shape[2] <= T.SIMI_STEM_MAX_SIDE):
+            return super().forward(x)
+        p1 = self.layers[0](T.simi_stem(x.contiguous(), self.stem_packed, self.c1.bias))
+        p2 = self.layers[1](p1)
+        p3 = self.layers[2](p2)
+        p4 = self.layers[3](p3)
+        out = [None, p1, p2, p3, p4]
+        out = [out[i] for i in self.used_layers]
+        return out[0] if len(out) == 1 else out
+
+
+_BACKBONE_FORMS = (FusedAtrousResNet, HipAtrousResNet, HipAtrousResNetFull)       # by level
 
 
 class _HipNeck(nn.Module):
@@ -396,22 +461,23 @@ def _original_view(mod):
 
 def _build_backbone(mod, hip=False):
     dev = next(mod.parameters()).device
-    return (HipAtrousResNet if hip else FusedAtrousResNet)(_original_view(mod)).to(dev)
+    return _BACKBONE_FORMS[int(hip)](_original_view(mod)).to(dev)
 
 
 def _build_neck(mod, hip=False):
     return hip_necks(_original_view(mod)) if hip else fold_sequentials(_original_view(mod))
 
 
-def optimize_similarity_model(model, strict: bool = False, hip: bool = None) -> list:
+def optimize_similarity_model(model, strict: bool = False, hip=None) -> list:
     """Fold / fuse model.backbone, model.neck, model.neck_lp (the reference's ModelBuilder attributes, model_builder…v2.py:44-60) where
     their structure is the reference's; returns the names that were switched.  strict: raise where the structure is not recognised
     instead of leaving that module as it is.  Eval mode only (BatchNorm statistics are frozen into the weights).
     hip (None: HDN_HIP_BACKBONE, default off): the convolutions on hdn_conv1x1_f32 / hdn_conv3x3d_f32 where they have a kernel (HipAtrousResNet,
-    hip_necks); the reload hook re-packs into the same buffers."""
+    hip_necks); the reload hook re-packs into the same buffers.  hip=2 (HDN_HIP_BACKBONE=2): level 2, the rest of the convolutions on hdn_conv3x3v_f32 and
+    the stem on hdn_simi_stem_f32 (HipAtrousResNetFull); True / 1 is level 1, False / 0 is off."""
     import functools
 
-    hip = hip_enabled() if hip is None else bool(hip)
+    hip = hip_level() if hip is None else (2 if (hip is not True and hip == 2) else int(bool(hip)))
     build_bb, build_nk = functools.partial(_build_backbone, hip=hip), functools.partial(_build_neck, hip=hip)
     done = []
     with torch.no_grad():
@@ -419,7 +485,7 @@ def optimize_similarity_model(model, strict: bool = False, hip: bool = None) -> 
         if isinstance(bb, nn.Module):
             try:
                 _detach(bb)
-                _attach(bb, (HipAtrousResNet if hip else FusedAtrousResNet)(bb), build=build_bb)
+                _attach(bb, _BACKBONE_FORMS[hip](bb), build=build_bb)
                 done.append("backbone")
             except ValueError:
                 if strict:
@@ -451,3 +517,9 @@ def enabled() -> bool:
 def hip_enabled() -> bool:
     """HDN_HIP_BACKBONE (default off): optimize_similarity_model's `hip` when the caller does not say."""
     return os.environ.get("HDN_HIP_BACKBONE", "0") not in ("", "0")
+
+
+def hip_level() -> int:
+    """HDN_HIP_BACKBONE as a level: 0 off (unset, "", "0"), 2 for "2", 1 for anything else."""
+    v = os.environ.get("HDN_HIP_BACKBONE", "0")
+    return 0 if v in ("", "0") else 2 if v.strip() == "2" else 1

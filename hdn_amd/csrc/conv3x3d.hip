@@ -23,6 +23,11 @@
 //   C  Cfg<2, 2, 2, 2>   128 pixels x 128 channels   CO a multiple of 128 and at least FILL such workgroups (64 x 64 per wave: half the loads per MFMA)
 // A and B with fewer than FILL workgroups (the tracker's B = 1) split K over grid.y into Z slices of whole steps; every slice writes its joined partial
 // tile to `workspace` [z][M][CO] and conv3x3d_finish_kernel adds the slices in slice order with the bias and the ReLU: deterministic, no atomics.
+//
+// hdn_conv3x3v_f32 (further down) is the same kernel with another pixel map (template parameter VALID): padding 0, stride s = 1 / 2,
+//   out[B,So,So,CO] = epilogue( conv3x3(x[B,S,S,CI]; stride s, dilation 1, no padding) ),   So = (S - 3) / s + 1,   M = B So^2
+// — conv2 and the 3x3 skip of layer2's first block (resnet_atrous.py:70-81 `padding = 2 - stride`, :162-174).  Output pixel (oy, ox) reads input pixel
+// (s oy + ky, s ox + kx): no tap ever leaves the image, so the predicate drops out; weights, K order, forms, K split and finish pass are the ones above.
 #include <climits>
 
 #include "hdn_common.h"
@@ -45,9 +50,10 @@ struct Cfg {
 };
 
 // FINAL: the whole of K in this workgroup, epilogue here; otherwise slice blockIdx.y of K, raw joined sums to dst = workspace [z][M][CO]
-template <class C, bool SD, bool FINAL>
+// VALID: the padding-0 pixel map — M = B So^2 output pixels, `d` is the STRIDE, a tap is never out of bounds; otherwise So == S and `d` is the dilation
+template <class C, bool SD, bool FINAL, bool VALID = false>
 __global__ __launch_bounds__(256) void conv3x3d_kernel(const float* __restrict__ x, const u32x4* __restrict__ wp, const float* __restrict__ bias,
-                                                       float* __restrict__ dst, int M, int S, int d, int CI, int CO, int relu, int tm, int sps) {
+                                                       float* __restrict__ dst, int M, int S, int So, int d, int CI, int CO, int relu, int tm, int sps) {
   constexpr int MT = C::MT, NT = C::NT, WN = C::WN;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wn = wave % WN, wm = wave / WN;
@@ -64,11 +70,12 @@ __global__ __launch_bounds__(256) void conv3x3d_kernel(const float* __restrict__
   int oy[MT], ox[MT];
 #pragma unroll
   for (int i = 0; i < MT; ++i) {
-    const int m = min(m0 + 32 * i + li, M - 1), s2 = S * S;
+    const int m = min(m0 + 32 * i + li, M - 1), s2 = So * So;
     const int b = m / s2, rm = m - b * s2;
-    oy[i] = rm / S;
-    ox[i] = rm - oy[i] * S;
-    xr[i] = x + (size_t)m * CI + 16 * g;
+    oy[i] = rm / So;
+    ox[i] = rm - oy[i] * So;
+    if constexpr (VALID) xr[i] = x + (((size_t)b * S + d * oy[i]) * S + d * ox[i]) * CI + 16 * g;      // the window's top-left pixel
+    else xr[i] = x + (size_t)m * CI + 16 * g;
   }
   const int chunks = CI >> 5, steps = 9 * chunks;
   const int s0 = FINAL ? 0 : (int)blockIdx.y * sps, s1 = FINAL ? steps : min(steps, s0 + sps);
@@ -87,11 +94,11 @@ __global__ __launch_bounds__(256) void conv3x3d_kernel(const float* __restrict__
   u32x4 wa[NT][4];
   int tap = s0 / chunks, c = s0 - tap * chunks;                             // of the next step to load
   auto load = [&](int s) {
-    const int ky = tap / 3, kx = tap - 3 * ky, dy = (ky - 1) * d, dx = (kx - 1) * d;
+    const int ky = tap / 3, kx = tap - 3 * ky, dy = VALID ? ky : (ky - 1) * d, dx = VALID ? kx : (kx - 1) * d;
     const ptrdiff_t off = ((ptrdiff_t)dy * S + dx) * CI + c * 32;
 #pragma unroll
     for (int i = 0; i < MT; ++i) {
-      const bool in = (unsigned)(oy[i] + dy) < (unsigned)S && (unsigned)(ox[i] + dx) < (unsigned)S;
+      const bool in = VALID || ((unsigned)(oy[i] + dy) < (unsigned)S && (unsigned)(ox[i] + dx) < (unsigned)S);
       const f4* xs = reinterpret_cast<const f4*>(xr[i] + off);
 #pragma unroll
       for (int qq = 0; qq < 4; ++qq) xa[i][qq] = in ? xs[qq] : f4{0.f, 0.f, 0.f, 0.f};
@@ -190,17 +197,17 @@ static long long dispatch(long long M, int CI, int CO, F&& f) {
   return f(Cfg<1, 2, 4, 1>{}, steps_per_slice(tm * (CO / 64), steps));
 }
 
-template <class C, bool SD>
-static int launch(const float* x, const void* wp, const float* bias, float* out, float* ws, int M, int S, int d, int CI, int CO, int relu, int sps,
+template <class C, bool SD, bool VALID = false>
+static int launch(const float* x, const void* wp, const float* bias, float* out, float* ws, int M, int S, int So, int d, int CI, int CO, int relu, int sps,
                   hipStream_t s) {
   const int steps = 9 * (CI / 32), Z = cdiv(steps, sps), tm = cdiv(M, C::BM);
   const dim3 grid((unsigned)((long long)tm * (CO / C::BN)), (unsigned)Z);
   const u32x4* w = static_cast<const u32x4*>(wp);
   if (Z == 1) {
-    hipLaunchKernelGGL((conv3x3d_kernel<C, SD, true>), grid, dim3(256), 0, s, x, w, bias, out, M, S, d, CI, CO, relu, tm, sps);
+    hipLaunchKernelGGL((conv3x3d_kernel<C, SD, true, VALID>), grid, dim3(256), 0, s, x, w, bias, out, M, S, So, d, CI, CO, relu, tm, sps);
     return launch_status();
   }
-  hipLaunchKernelGGL((conv3x3d_kernel<C, SD, false>), grid, dim3(256), 0, s, x, w, bias, ws, M, S, d, CI, CO, relu, tm, sps);
+  hipLaunchKernelGGL((conv3x3d_kernel<C, SD, false, VALID>), grid, dim3(256), 0, s, x, w, bias, ws, M, S, So, d, CI, CO, relu, tm, sps);
   if (const int rc = launch_status()) return rc;
   const long long n4 = (long long)M * CO / 4;
   hipLaunchKernelGGL(conv3x3d_finish_kernel, dim3((unsigned)((n4 + HDN_BLOCK - 1) / HDN_BLOCK)), dim3(HDN_BLOCK), 0, s, reinterpret_cast<const f4*>(ws),
@@ -213,6 +220,14 @@ static int check_shape(int B, int S, int CI, int CO, int d) {
   if (B <= 0 || S <= 0 || CI <= 0 || CO <= 0 || CI % 32 || CO % 32 || (d != 1 && d != 2 && d != 4)) return HDN_E_SHAPE;
   const long long m = (long long)B * S * S;
   if (m * CI > INT_MAX || m * CO > INT_MAX || 9LL * CI * CO > INT_MAX) return HDN_E_LIMIT;
+  return HDN_OK;
+}
+
+// the same for the padding-0 form; *So = the output side
+static int check_shape_valid(int B, int S, int CI, int CO, int stride, int* So) {
+  if (B <= 0 || S < 3 || CI <= 0 || CO <= 0 || CI % 32 || CO % 32 || (stride != 1 && stride != 2)) return HDN_E_SHAPE;
+  *So = (S - 3) / stride + 1;
+  if ((long long)B * S * S * CI > INT_MAX || (long long)B * *So * *So * CO > INT_MAX || 9LL * CI * CO > INT_MAX) return HDN_E_LIMIT;
   return HDN_OK;
 }
 
@@ -257,7 +272,52 @@ extern "C" int hdn_conv3x3d_f32(const float* x, const void* wpacked, const float
   if (const int rr = hdn::check_fp16_range(x, nx, s, act_domain)) return rr;
   return (int)hdn::c3d::dispatch(M, CI, CO, [&](auto cfg, int sps) -> long long {
     using C = decltype(cfg);
-    return act_domain ? hdn::c3d::launch<C, true>(x, wpacked, bias, out, static_cast<float*>(ws), (int)M, S, dilation, CI, CO, relu, sps, s)
-                      : hdn::c3d::launch<C, false>(x, wpacked, bias, out, static_cast<float*>(ws), (int)M, S, dilation, CI, CO, relu, sps, s);
+    return act_domain ? hdn::c3d::launch<C, true>(x, wpacked, bias, out, static_cast<float*>(ws), (int)M, S, S, dilation, CI, CO, relu, sps, s)
+                      : hdn::c3d::launch<C, false>(x, wpacked, bias, out, static_cast<float*>(ws), (int)M, S, S, dilation, CI, CO, relu, sps, s);
+  });
+}
+
+// ---------------------------------------------------------------------------------------------------- padding 0, stride 1 / 2 (hdn_conv3x3v_f32)
+extern "C" int hdn_conv3x3v_form(int B, int S, int CI, int CO, int stride) {
+  int So = 0;
+  if (const int rc = hdn::c3d::check_shape_valid(B, S, CI, CO, stride, &So)) return rc;
+  return (int)hdn::c3d::dispatch((long long)B * So * So, CI, CO, [&](auto cfg, int sps) -> long long {
+    using C = decltype(cfg);
+    return C::MT | C::NT << 4 | C::WM << 8 | C::WN << 12 | hdn::cdiv(9 * (CI / 32), sps) << 16;
+  });
+}
+
+extern "C" long long hdn_conv3x3v_workspace_bytes(int B, int S, int CI, int CO, int stride) {
+  int So = 0;
+  if (const int rc = hdn::c3d::check_shape_valid(B, S, CI, CO, stride, &So)) return rc;
+  const long long M = (long long)B * So * So;
+  return hdn::c3d::dispatch(M, CI, CO, [&](auto, int sps) -> long long {
+    const int Z = hdn::cdiv(9 * (CI / 32), sps);
+    return Z > 1 ? Z * M * CO * 4 : 0;
+  });
+}
+
+// wpacked: hdn_pack_conv3x3d_f32's stream (layout above)
+extern "C" int hdn_conv3x3v_f32(const float* x, const void* wpacked, const float* bias, float* out, void* ws, long long ws_bytes, int B, int S, int CI,
+                                int CO, int stride, int relu, int act_domain, void* stream) {
+  if (!x || !wpacked || !out) return HDN_E_NULL;
+  if ((relu != 0 && relu != 1) || (act_domain != 0 && act_domain != 1)) return HDN_E_SHAPE;
+  int So = 0;
+  if (const int rc = hdn::c3d::check_shape_valid(B, S, CI, CO, stride, &So)) return rc;
+  const long long M = (long long)B * So * So, nx = (long long)B * S * S * CI, nout = M * CO;
+  if (hdn::bytes_overlap(out, nout * 4, x, nx * 4)) return HDN_E_ALIAS;
+  if (!hdn::aligned16(x) || !hdn::aligned16(wpacked) || !hdn::aligned16(out) || (bias && !hdn::aligned16(bias))) return HDN_E_LIMIT;
+  const long long need = hdn_conv3x3v_workspace_bytes(B, S, CI, CO, stride);
+  if (need > 0) {
+    if (!ws) return HDN_E_NULL;
+    if (!hdn::aligned16(ws) || ws_bytes < need) return HDN_E_LIMIT;
+    if (hdn::bytes_overlap(ws, need, x, nx * 4) || hdn::bytes_overlap(ws, need, out, nout * 4)) return HDN_E_ALIAS;
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (const int rr = hdn::check_fp16_range(x, nx, s, act_domain)) return rr;
+  return (int)hdn::c3d::dispatch(M, CI, CO, [&](auto cfg, int sps) -> long long {
+    using C = decltype(cfg);
+    return act_domain ? hdn::c3d::launch<C, true, true>(x, wpacked, bias, out, static_cast<float*>(ws), (int)M, S, So, stride, CI, CO, relu, sps, s)
+                      : hdn::c3d::launch<C, false, true>(x, wpacked, bias, out, static_cast<float*>(ws), (int)M, S, So, stride, CI, CO, relu, sps, s);
   });
 }

@@ -14,7 +14,8 @@
 //   hdn_pack_head_tail_f32      -> w1_packed of hdn_head_tail_f32                                      (G x [H, H] 1x1 convolutions)
 //   hdn_pack_conv1x1_f32        -> wpacked of hdn_conv1x1_f32                                          (Conv2d(CI, CO, 1, s) of a Bottleneck)
 //   hdn_pack_conv3x3s2_f32      -> wpacked of hdn_conv3x3s2_f32                                        (Conv2d(C, C, 3, 2, 1) of a Bottleneck)
-//   hdn_pack_conv3x3d_f32       -> wpacked of hdn_conv3x3d_f32                                         (Conv2d(CI, CO, 3, 1, d, d) of the atrous backbone)
+//   hdn_pack_conv3x3d_f32       -> wpacked of hdn_conv3x3d_f32 / hdn_conv3x3v_f32                      (Conv2d(CI, CO, 3, 1, d, d) / (CI, CO, 3, s, 0) of the atrous backbone)
+//   hdn_pack_simi_stem_f32      -> wpacked of hdn_simi_stem_f32                                        (Conv2d(3, 64, 7, 2, 0))
 //
 // All pointers are HOST pointers.  Every stream is 2 pieces x 2 bytes per (padded) weight: v = p0 + 2^-11 p1, p0 = fp16(v),
 // p1 = fp16((v - p0) 2^11), round-to-nearest-even each (csrc/mfma_split.h; weights are NOT pre-scaled, only activations are).
@@ -154,6 +155,26 @@ extern "C" int hdn_pack_stem_mfma_f32(const float* w, void* out, long long out_b
     for (int r = 0; r < 14; ++r)
       for (int j = 0; j < 8; ++j) {
         const float v = j < 7 ? w[(static_cast<long long>(co) * 14 + r) * 7 + j] : 0.0f;
+        const int tile = co / 32, n = co & 31, step = r / 2, g = r & 1;
+        const long long o = (static_cast<long long>(step) * 2 + tile) * 2;
+        const long long tail = 2LL * 32 * 8, in = (static_cast<long long>(g) * 32 + n) * 8 + j;
+        s.put((o + 0) * tail + in, (o + 1) * tail + in, v);
+      }
+  return s.ok ? HDN_OK : HDN_E_LIMIT;
+}
+
+extern "C" long long hdn_pack_simi_stem_bytes(void) { return 2LL * 2 * 64 * 22 * 8; }
+
+// w [64][3][7][7] -> [11 k steps][2 n tiles][2 pieces][k half g][32 n][8]: element j = w[32 tile + n][ci][ky][kx = j], ci * 7 + ky = 2 step + g; zero at
+// j = 7 and at 2 step + g = 21 (the 22nd row of K pads the 11th k step)
+extern "C" int hdn_pack_simi_stem_f32(const float* w, void* out, long long out_bytes) {
+  if (!w || !out) return HDN_E_NULL;
+  if (out_bytes != hdn_pack_simi_stem_bytes()) return HDN_E_SHAPE;
+  Sink s{static_cast<uint16_t*>(out)};
+  for (int co = 0; co < 64; ++co)
+    for (int r = 0; r < 22; ++r)
+      for (int j = 0; j < 8; ++j) {
+        const float v = (r < 21 && j < 7) ? w[(static_cast<long long>(co) * 21 + r) * 7 + j] : 0.0f;
         const int tile = co / 32, n = co & 31, step = r / 2, g = r & 1;
         const long long o = (static_cast<long long>(step) * 2 + tile) * 2;
         const long long tail = 2LL * 32 * 8, in = (static_cast<long long>(g) * 32 + n) * 8 + j;

@@ -699,6 +699,74 @@ def conv3x3d(x, wpacked, bias, dilation=1, relu=True, act_domain=0):
     return out
 
 
+def conv3x3v(x, wpacked, bias, stride=2, relu=True, act_domain=0):
+    """[relu](conv3x3 / stride 1 or 2 / padding 0 (x) [+ bias]) through hdn_conv3x3v_f32; x channels-last [B,CI,S,S] float32, S >= 3 -> channels-last
+    [B,CO,So,So], So = (S - 3) // stride + 1; `wpacked` from pack_conv3x3d, on x's device (CO is read off its size); bias [CO] or None (zero).
+    act_domain as conv3x3_bias_relu's."""
+    import torch
+
+    from . import _lib
+
+    dev = _lib.require_device(x) if bias is None else _lib.require_device(x, bias)
+    cl = torch.channels_last
+    if x.dim() != 4 or x.dtype != torch.float32 or x.shape[2] != x.shape[3] or not x.is_contiguous(memory_format=cl):
+        raise ValueError("conv3x3v: square channels-last float32 input [B,CI,S,S]")
+    B, CI, S, _ = x.shape
+    CO = wpacked.numel() // (9 * SPLIT_PIECES * CI) if CI else 0
+    if wpacked.dtype != torch.int16 or wpacked.device != dev or CO <= 0 or wpacked.numel() != 9 * SPLIT_PIECES * CO * CI or (bias is not None and bias.numel() != CO):
+        raise ValueError("conv3x3v: weights must come from pack_conv3x3d for this CI (and the bias's CO), on the input's device")
+    lib = _lib.load()
+    nws = lib.hdn_conv3x3v_workspace_bytes(B, S, CI, CO, int(stride))
+    if nws < 0:
+        _lib.check(int(nws), "conv3x3v")
+    So = (S - 3) // int(stride) + 1
+    out = torch.empty((B, CO, So, So), dtype=torch.float32, device=dev, memory_format=cl)
+    ws = torch.empty(nws // 4, dtype=torch.float32, device=dev) if nws else None   # (from torch's caching allocator: no sync, graph-safe)
+    with _lib.device_guard(dev):
+        rc = lib.hdn_conv3x3v_f32(_lib.ptr(x), _lib.ptr(wpacked), _lib.ptr(bias) if bias is not None else None, _lib.ptr(out),
+                                  _lib.ptr(ws) if ws is not None else None, nws, B, S, CI, CO, int(stride), int(bool(relu)), int(act_domain),
+                                  _lib.stream_ptr(dev))
+    _lib.check(rc, "conv3x3v")
+    return out
+
+
+SIMI_STEM_MAX_SIDE = 255      # hdn_simi_stem_f32's documented limit (csrc/simi_stem.hip: MAX_S)
+
+
+def pack_simi_stem(weight):
+    """[64, 3, 7, 7] fp32 weights of the similarity backbone's conv1, BatchNorm folded in -> the stream hdn_simi_stem_f32 takes (hdn_pack_simi_stem_f32)."""
+    from . import _lib
+
+    if tuple(weight.shape) != (64, 3, 7, 7):
+        raise ValueError(f"pack_simi_stem takes [64, 3, 7, 7] weights, got {tuple(weight.shape)}")
+    lib, w = _lib.load(), _host_f32(weight)
+    return _c_pack("pack_simi_stem", lib.hdn_pack_simi_stem_bytes(), lambda o, n: lib.hdn_pack_simi_stem_f32(w.data_ptr(), o, n))
+
+
+def simi_stem(x, wpacked, bias):
+    """maxpool3x3/s2/p1(relu(conv7x7 / stride 2 / padding 0 (x) + bias)) through hdn_simi_stem_f32, one launch; x NCHW-contiguous [B,3,S,S] float32,
+    7 <= S <= SIMI_STEM_MAX_SIDE -> channels-last [B,64,Sp,Sp], Sp = ((S - 7) // 2) // 2 + 1; `wpacked` from pack_simi_stem, bias [64], on x's device."""
+    import torch
+
+    from . import _lib
+
+    dev = _lib.require_device(x, bias)
+    if x.dim() != 4 or x.dtype != torch.float32 or x.shape[1] != 3 or x.shape[2] != x.shape[3] or not x.is_contiguous():
+        raise ValueError("simi_stem: square NCHW-contiguous float32 input [B,3,S,S]")
+    B, _, S, _ = x.shape
+    lib = _lib.load()
+    if wpacked.dtype != torch.int16 or wpacked.device != dev or wpacked.numel() * 2 != lib.hdn_pack_simi_stem_bytes() or bias.numel() != 64:
+        raise ValueError("simi_stem: weights must come from pack_simi_stem (and a bias of 64), on the input's device")
+    if S < 7 or S > SIMI_STEM_MAX_SIDE:
+        raise ValueError(f"simi_stem: side {S} outside 7 .. {SIMI_STEM_MAX_SIDE}")
+    Sp = ((S - 7) // 2) // 2 + 1
+    out = torch.empty((B, 64, Sp, Sp), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
+    with _lib.device_guard(dev):
+        rc = lib.hdn_simi_stem_f32(_lib.ptr(x), _lib.ptr(wpacked), _lib.ptr(bias), _lib.ptr(out), B, S, 0, _lib.stream_ptr(dev))
+    _lib.check(rc, "simi_stem")
+    return out
+
+
 class FusedBottleneck(nn.Module):
     """Bottleneck.forward (backbone/resnet.py:113-133) of the BN-folded homography trunk: conv1 1x1 + bias + ReLU, conv2 3x3 + bias + ReLU,
     conv3 1x1 + bias + residual + ReLU, the residual being the input or the folded downsample branch (1x1 / stride, bias, no ReLU).  The 1x1

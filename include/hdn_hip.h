@@ -466,7 +466,9 @@ int hdn_xcorr_north_launch_events(void* start_event, void* stop_event);
  *   hdn_pack_head_tail_f32     w1 [G][H][H]                            -> hdn_head_tail_f32 (ban.py:60-66)
  *   hdn_pack_conv1x1_f32       w [CO][CI]                              -> hdn_conv1x1_f32 (backbone/resnet.py:97-133, 162-176), CO, CI multiples of 32
  *   hdn_pack_conv3x3s2_f32     w [C][C][3][3]                          -> hdn_conv3x3s2_f32 (backbone/resnet.py:97-133 conv2 at stride 2), C = 128 / 256 / 512
- *   hdn_pack_conv3x3d_f32      w [CO][CI][3][3]                        -> hdn_conv3x3d_f32 (hdn/models/backbone/resnet_atrous.py:62-110, 152-183), CO, CI multiples of 32
+ *   hdn_pack_conv3x3d_f32      w [CO][CI][3][3]                        -> hdn_conv3x3d_f32 (hdn/models/backbone/resnet_atrous.py:62-110, 152-183), CO, CI multiples of 32;
+ *                                                                         also hdn_conv3x3v_f32 (resnet_atrous.py:70-81, 162-174)
+ *   hdn_pack_simi_stem_f32     w [64][3][7][7]                         -> hdn_simi_stem_f32 (resnet_atrous.py:117-121); declared beside it further down
  */
 long long hdn_pack_conv3x3_bytes(int C);
 int hdn_pack_conv3x3_f32(const float* w, int C, void* out, long long out_bytes);
@@ -586,6 +588,48 @@ long long hdn_conv3x3d_workspace_bytes(int B, int S, int CI, int CO, int dilatio
 int hdn_conv3x3d_form(int B, int S, int CI, int CO, int dilation);                              /* resnet_atrous.py:62-110, 152-183 */
 int hdn_conv3x3d_f32(const float* x, const void* wpacked, const float* bias, float* out, void* ws, long long ws_bytes, int B, int S, int CI, int CO,
                      int dilation, int relu, int act_domain, void* stream);                     /* resnet_atrous.py:62-110, 152-183 */
+
+/*
+ * The same convolution without padding ("valid"), stride 1 or 2 (conv3x3d.hip, the kernel above with another pixel map; an addition to ABI 10):
+ *   out[B,So,So,CO] = [relu]( conv3x3 / stride s / padding 0 / dilation 1 (x[B,S,S,CI], w[CO][CI][3][3]) [+ bias[co]] ),   So = (S - 3) / s + 1,
+ * channels-last fp32 in and out; output pixel (oy, ox) reads input pixels (s oy + ky, s ox + kx), so with an even S at stride 2 the last input row and
+ * column are never read.  s = 1 / 2, S >= 3, CI and CO multiples of 32, any B >= 1, relu and act_domain 0 / 1 (else HDN_E_SHAPE); more than 2^31 - 1
+ * elements in x or out, a pointer that is not 16-byte aligned or a workspace that is too small: HDN_E_LIMIT.  `bias` may be NULL (zero: the 3x3 skip of
+ * layer2's first block, whose shift rides in the block's last bias).  `out` may overlap neither `x` nor `ws`, `ws` not `x` (HDN_E_ALIAS); NULL x,
+ * wpacked, out, or ws where one is needed: HDN_E_NULL.  act_domain as above ("Activation domain").  fp32 carried as two fp16 pieces, three products,
+ * hi / lo fp32 accumulators: the error of an fp32 convolution.  Deterministic, exactly as hdn_conv3x3d_f32: tap-major K, forms A / B / C over M = B So^2
+ * pixels by the same rule, K split into at most 16 slices of whole steps into `ws` [z][M][CO] with a finish pass in slice order.  No atomics.
+ * hdn_conv3x3v_workspace_bytes / hdn_conv3x3v_form: as the dilated kernel's queries, with `stride` in place of `dilation`; host only.
+ * Takes part in the range guard (hdn_set_check_range) on `x`.  Asynchronous on `stream`; allocates nothing.
+ * wpacked: the stream hdn_pack_conv3x3d_f32 wrote from the BatchNorm-folded w (the dilated kernel's stream; there is no second packer).
+ * Replaces conv2 + bn2 + relu (`padding = 2 - stride`) and the strided 3x3 downsample branch of layer2's first block,
+ * hdn/models/backbone/resnet_atrous.py:70-81, 162-174 (eval mode only).
+ */
+long long hdn_conv3x3v_workspace_bytes(int B, int S, int CI, int CO, int stride);               /* resnet_atrous.py:70-81, 162-174 */
+int hdn_conv3x3v_form(int B, int S, int CI, int CO, int stride);                                /* resnet_atrous.py:70-81, 162-174 */
+int hdn_conv3x3v_f32(const float* x, const void* wpacked, const float* bias, float* out, void* ws, long long ws_bytes, int B, int S, int CI, int CO,
+                     int stride, int relu, int act_domain, void* stream);                       /* resnet_atrous.py:70-81, 162-174 */
+
+/*
+ * First stage of the similarity branch's ResNet-50 in one launch (simi_stem.hip; an addition to ABI 10):
+ *   out[B,Sp,Sp,64] = maxpool3x3/s2/p1( relu( conv7x7 / s2 / p0 (x[B,3,S,S], w[64][3][7][7]) + bias[co] ) ),  Sc = (S - 7) / 2 + 1,  Sp = (Sc - 1) / 2 + 1,
+ * x NCHW fp32, out channels-last fp32 (255 -> 125 -> 63, 127 -> 61 -> 31).  Square inputs with 7 <= S <= 255: S < 7, B <= 0 or act_domain != 0 (the
+ * HIP backbone runs in real units): HDN_E_SHAPE; S > 255, more than 2^31 - 1 elements in x, wpacked or out not 16-byte aligned: HDN_E_LIMIT; `out`
+ * overlapping `x`: HDN_E_ALIAS; a NULL pointer (bias included): HDN_E_NULL.  The Sc x Sc x 64 convolution map stays in the workgroup (registers / LDS);
+ * the pool needs no -inf: behind the ReLU everything is >= 0 and every window holds a real element.
+ * fp32 carried as two fp16 pieces (pixels split as x 2^-8), three products, hi / lo fp32 accumulators: the error of an fp32 convolution.
+ * Deterministic: a conv output is the sum over k steps 0 .. 10 (k = 16 step + 8 g + j <-> ci * 7 + ky = 2 step + g, kx = j) into zeroed accumulators,
+ * joined, + bias; the order depends neither on B nor on the workgroup (image, pooled row, channel half) that computes it, so an image gives the same bits
+ * at any batch size.  Takes part in the range guard (hdn_set_check_range) on `x`.  Asynchronous on `stream`; allocates nothing; no workspace.
+ * wpacked: the stream hdn_pack_simi_stem_f32 wrote from the BatchNorm-folded w, 45,056 bytes, 16-byte aligned.  Current order, informative:
+ * [11 k steps][2 n tiles][2 pieces][64 lanes = (k half g, n)][8] fp16: element j is piece pc (p0 = fp16(w), p1 = fp16((w - p0) * 2048)) of
+ * w[co = 32 tile + n][ci][ky][kx = j], ci * 7 + ky = 2 * k step + g; 0 at j = 7 and at 2 * k step + g = 21.
+ * Replaces conv1 / bn1 / relu / maxpool of hdn/models/backbone/resnet_atrous.py:117-121, 186-189 (eval mode only; a network that returns the stem's
+ * own output, `0 in used_layers`, keeps the unfused stem).
+ */
+long long hdn_pack_simi_stem_bytes(void);                                                       /* resnet_atrous.py:117-121 */
+int hdn_pack_simi_stem_f32(const float* w, void* out, long long out_bytes);                     /* resnet_atrous.py:117-121 */
+int hdn_simi_stem_f32(const float* x, const void* wpacked, const float* bias, float* out, int B, int S, int act_domain, void* stream);   /* resnet_atrous.py:117-121, 186-189 */
 
 /* The compile-time exponent of the activation scale (csrc/mfma_split.h, HDN_ACT_SCALE_LOG2; 8): callers that hand over pre-scaled biases in
  * act_domain = 1 check it against the value they scale with (hdn_amd.trunk.ACT_SCALE_LOG2). */

@@ -1,14 +1,17 @@
-"""Similarity backbone + both necks, forward time three ways, on one GPU: one JSON line.
+"""Similarity backbone + both necks, forward time four ways, on one GPU: one JSON line.
 
     python tools/backbone_bench.py --batch N [--iters 30] [--warmup 5]
 
 The production stand-in's ResNet-50 (stride 8, atrous) and its two necks (tests/production_standin.py) on 127- and 255-px crops:
 (a) "as_built": the modules' own forward (BatchNorm / ReLU / add launches, MIOpen); (b) "folded": optimize_similarity_model(model), today's default
-(MIOpen convolutions + hdn_bias_relu_f32); (c) "hip": optimize_similarity_model(model, hip=True) (hdn_conv1x1_f32 / hdn_conv3x3d_f32).
-ms per forward: warmed, HIP-event timed per forward, median of --iters with the 10th / 90th percentile beside it.  All three in one process, on the same
+(MIOpen convolutions + hdn_bias_relu_f32); (c) "hip": optimize_similarity_model(model, hip=True) (hdn_conv1x1_f32 / hdn_conv3x3d_f32); (d) "hip_full":
+optimize_similarity_model(model, hip=2) (level 2: also hdn_conv3x3v_f32 and hdn_simi_stem_f32, no library convolution left).
+ms per forward: warmed, HIP-event timed per forward, median of --iters with the 10th / 90th percentile beside it.  All four in one process, on the same
 seeded weights and inputs.  It also lists every distinct hdn_conv3x3d_f32 launch of one forward per crop: shape, launch form, count per forward,
 algorithmic bytes (x + out + packed weights), its own event-timed median, and its floor = max(bytes / the measured copy rate, MFMA work at the dense
-fp16 peak x 3 piece products); K-slice workspace traffic is the kernel's own cost, not in the floor.
+fp16 peak x 3 piece products); K-slice workspace traffic is the kernel's own cost, not in the floor.  The same table for level 2's launches: "conv3x3v"
+(hdn_conv3x3v_f32) and "simi_stem" (hdn_simi_stem_f32, K = 147 in the floor's MFMA work), the latter beside "level1_stem_us": the event-timed sum of
+the four launches it replaces (library convolution, hdn_bias_relu_f32, max pool, NCHW -> channels-last copy), measured the same way.
 """
 from __future__ import annotations
 
@@ -72,6 +75,23 @@ def conv3x3d_launches(net, crop):
     return out
 
 
+def conv3x3v_launches(net, crop):
+    """{(CI, CO, S, stride): count} of the hdn_conv3x3v_f32 launches of one level-2 forward at this crop size (S: the INPUT side)."""
+    from hdn_amd import backbone as BB
+    S = ((crop - 7) // 2 + 1 - 1) // 2 + 1
+    out = {}
+    for name in ("layer1", "layer2", "layer3", "layer4"):
+        for blk in getattr(net, name):
+            convs = [blk.conv2] + ([blk.downsample[0]] if blk.downsample is not None else [])
+            for c in convs:
+                if BB.hip_conv_kind(c, level=2) == "conv3x3v":
+                    key = (c.in_channels, c.out_channels, S, c.stride[0])
+                    out[key] = out.get(key, 0) + 1
+            c2 = blk.conv2
+            S = (S + 2 * c2.padding[0] - c2.dilation[0] * 2 - 1) // c2.stride[0] + 1
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=1)
@@ -99,7 +119,8 @@ def main():
     with torch.no_grad():
         ref = {s: forward(x) for s, x in xs.items()}
         for form, setup in (("as_built", lambda: BB.restore_similarity_model(model)), ("folded", lambda: BB.optimize_similarity_model(model, hip=False)),
-                            ("hip", lambda: BB.optimize_similarity_model(model, hip=True))):
+                            ("hip", lambda: BB.optimize_similarity_model(model, hip=True)),
+                            ("hip_full", lambda: BB.optimize_similarity_model(model, hip=2))):
             setup()
             for s, x in xs.items():
                 got = forward(x)
@@ -109,6 +130,7 @@ def main():
         BB.restore_similarity_model(model)
         for s in xs:
             res["ms"][f"speedup_hip_vs_folded_{s}"] = round(res["ms"][f"folded_{s}"]["median"] / res["ms"][f"hip_{s}"]["median"], 3)
+            res["ms"][f"speedup_hip_full_vs_hip_{s}"] = round(res["ms"][f"hip_{s}"]["median"] / res["ms"][f"hip_full_{s}"]["median"], 3)
         rate = copy_rate(dev)
         res["copy_GBps"] = round(rate / 1e9, 1)
         rows, cl = [], torch.channels_last
@@ -127,6 +149,40 @@ def main():
                              "x_floor": round(1e3 * med / floor, 2)})
                 del xi, wp
         res["conv3x3d"] = rows
+        rows = []
+        for crop in xs:
+            for (CI, CO, S, st), count in conv3x3v_launches(model.backbone, crop).items():
+                So = (S - 3) // st + 1
+                xi = torch.rand(B, CI, S, S, device=dev).contiguous(memory_format=cl)
+                wp = T.pack_conv3x3d(torch.randn(CO, CI, 3, 3) * 0.02).to(dev)
+                bias = torch.zeros(CO, device=dev)
+                nbytes = 4 * (B * (S * S * CI + So * So * CO) + 9 * CI * CO)
+                med, lo, hi = timed(lambda: T.conv3x3v(xi, wp, bias, stride=st), args.iters, args.warmup)
+                floor = max(nbytes / rate, 3 * 2.0 * B * So * So * 9 * CI * CO / MFMA_F16_PEAK) * 1e6
+                fm = lib.hdn_conv3x3v_form(B, S, CI, CO, st)
+                rows.append({"crop": crop, "CI": CI, "CO": CO, "S": S, "So": So, "stride": st, "count": count,
+                             "form": f"Cfg<{fm & 15},{(fm >> 4) & 15},{(fm >> 8) & 15},{(fm >> 12) & 15}> x {fm >> 16}", "bytes": nbytes,
+                             "us": round(1e3 * med, 2), "us_p10": round(1e3 * lo, 2), "us_p90": round(1e3 * hi, 2), "floor_us": round(floor, 2),
+                             "x_floor": round(1e3 * med / floor, 2)})
+                del xi, wp
+        res["conv3x3v"] = rows
+        rows = []
+        BB.optimize_similarity_model(model, hip=True)
+        stem1 = vars(model.backbone)["_hdn_fused"]                      # level 1: its stem is the four launches the fused one replaces
+        w7, b7 = stem1.c1.weight, stem1.c1.bias
+        wp = T.pack_simi_stem(w7).to(dev)
+        for crop, x in xs.items():
+            Sc = (crop - 7) // 2 + 1
+            Sp = (Sc - 1) // 2 + 1
+            nbytes = 4 * (B * (3 * crop * crop + Sp * Sp * 64) + 64 * 147)
+            med, lo, hi = timed(lambda: T.simi_stem(x, wp, b7), args.iters, args.warmup)
+            m1, lo1, hi1 = timed(lambda: stem1.maxpool(stem1.c1.act(x)).contiguous(memory_format=cl), args.iters, args.warmup)
+            floor = max(nbytes / rate, 3 * 2.0 * B * Sc * Sc * 147 * 64 / MFMA_F16_PEAK) * 1e6
+            rows.append({"crop": crop, "Sc": Sc, "Sp": Sp, "grid": 2 * B * Sp, "bytes": nbytes, "us": round(1e3 * med, 2), "us_p10": round(1e3 * lo, 2),
+                         "us_p90": round(1e3 * hi, 2), "floor_us": round(floor, 2), "x_floor": round(1e3 * med / floor, 2),
+                         "level1_stem_us": round(1e3 * m1, 2), "level1_stem_us_p10": round(1e3 * lo1, 2), "level1_stem_us_p90": round(1e3 * hi1, 2)})
+        BB.restore_similarity_model(model)
+        res["simi_stem"] = rows
     print(json.dumps(res), flush=True)
 
 
