@@ -1,4 +1,4 @@
-// conv_search of the correlation heads at the tracker's B = 1: a 3x3 / stride 1 / no padding convolution of a 256-channel
+// conv_search of the correlation heads: a 3x3 / stride 1 / no padding convolution of a 256-channel
 // search feature map with the BatchNorm-folded weights of DepthwiseXCorr.conv_search (hdn/models/head/ban.py:55-59,75), + bias + ReLU, written as
 // contiguous NCHW planes - the layout the depthwise correlation kernels read.  The cls and loc branches of a level share their input, so the host
 // concatenates their weights (CO = 2 x 256) and the three levels of a head are the three problems of ONE launch.
@@ -53,16 +53,21 @@ __device__ __forceinline__ void wait_a(u32x4& a0, u32x4& a1) {
   asm volatile("s_waitcnt vmcnt(%2)" : "+v"(a0), "+v"(a1) : "n"(PENDING));
 }
 
+// BATCH (hdn_head_conv3x3_batch_f32): blockIdx.z = problem * B + image; the image is `xbs` elements into the problem's input and its channel block
+// lands in plane block (group * B + image) of CG = CO / groups channels, so that a group of a problem is a contiguous [B, CG, Ho, Wo].  Nothing else
+// differs: an output element is summed exactly as without BATCH.
+template <bool BATCH>
 __global__ __launch_bounds__(512) void head_conv_kernel(Ptrs P, const u32x4* __restrict__ wp, const float* __restrict__ bias, int CO, int Hi, int Wi,
-                                                        long long sc, long long sy, long long sx) {
+                                                        long long sc, long long sy, long long sx, int B, long long xbs, int CG) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x & 255, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)((threadIdx.x >> 6) & 3));
   const bool produce = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8)) != 0;
   const int li = lane & 31, g = lane >> 5;
   const int Ho = Hi - 2, Wo = Wi - 2, Pn = Ho * Wo;
-  const int p0 = blockIdx.x * TILE_N, cb = blockIdx.y, prob = blockIdx.z;
-  const float* __restrict__ x = P.x[prob];
+  const int p0 = blockIdx.x * TILE_N, cb = blockIdx.y;
+  const int prob = BATCH ? (int)blockIdx.z / B : (int)blockIdx.z, img = BATCH ? (int)blockIdx.z - prob * B : 0;
+  const float* __restrict__ x = P.x[prob] + (BATCH ? (long long)img * xbs : 0);
   const int y0 = p0 / Wo;                                     // first output row of the tile = first input row of its patch
   const int y1 = min(p0 + TILE_N - 1, Pn - 1) / Wo;
   const int LP = (y1 - y0 + 3) * Wi;                          // patch pixels (host checked: <= LP_MAX)
@@ -202,6 +207,10 @@ __global__ __launch_bounds__(512) void head_conv_kernel(Ptrs P, const u32x4* __r
   {
     const float* red = reinterpret_cast<const float*>(smem);
     float* __restrict__ out = P.out[prob];
+    if (BATCH) {
+      const int grp = cb * TILE_M / CG;                       // (CG is a multiple of TILE_M: a channel block lies in one group)
+      out += ((size_t)(grp * B + img) * CG - (size_t)grp * CG) * Pn;
+    }
     const int t512 = threadIdx.x;
 #pragma unroll
     for (int q = 0; q < (TILE_M * TILE_N) / 512; ++q) {
@@ -239,13 +248,61 @@ extern "C" int hdn_head_conv3x3_f32(const float* const* xs, const void* w_packed
   static hdn::PerDeviceOnce attr;
   const int dev_ = hdn::PerDeviceOnce::device();
   if (!attr.done(dev_)) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hdn::hc::head_conv_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, hdn::hc::LDS_BYTES);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hdn::hc::head_conv_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, hdn::hc::LDS_BYTES);
     if (e != hipSuccess) return -(1000 + (int)e);
     attr.set(dev_);
   }
   const long long sc = nhwc ? 1 : (long long)Hi * Wi, sy = nhwc ? (long long)Wi * hdn::hc::CI : Wi, sx = nhwc ? hdn::hc::CI : 1;
   const dim3 grid((Ho * Wo + hdn::hc::TILE_N - 1) / hdn::hc::TILE_N, CO / hdn::hc::TILE_M, n);
-  hipLaunchKernelGGL(hdn::hc::head_conv_kernel, grid, dim3(512), hdn::hc::LDS_BYTES, static_cast<hipStream_t>(stream), P, static_cast<const hdn::hc::u32x4*>(w_packed),
-                     bias, CO, Hi, Wi, sc, sy, sx);
+  hipLaunchKernelGGL(hdn::hc::head_conv_kernel<false>, grid, dim3(512), hdn::hc::LDS_BYTES, static_cast<hipStream_t>(stream), P,
+                     static_cast<const hdn::hc::u32x4*>(w_packed), bias, CO, Hi, Wi, sc, sy, sx, 1, 0LL, CO);
+  return hdn::launch_status();
+}
+
+// The same convolution at any batch B (the template branch conv_kernel of the heads, and conv_search of the lock-step trackers): level i's input is
+// [B, 256, Hi, Wi] with the images x_batch_stride elements apart, and `out` is ONE buffer [n][groups][B][CO / groups][Ho Wo] - each (level, group)
+// a contiguous [B, CO / groups, Ho, Wo], what hdn_xcorr_depthwise_multi_f32 reads.  Every argument is checked before the first HIP call.
+extern "C" int hdn_head_conv3x3_batch_f32(const float* const* xs, const void* w_packed, const float* bias, float* out, int n, int B, int groups, int CO,
+                                          int Hi, int Wi, int nhwc, long long x_batch_stride, void* stream) {
+  if (!xs || !w_packed || !bias || !out) return HDN_E_NULL;
+  if (n <= 0 || B <= 0 || CO <= 0 || Hi < 3 || Wi < 3 || (groups != 1 && groups != 2)) return HDN_E_SHAPE;
+  if (n > hdn::hc::MAX_PROBLEMS || CO % groups != 0 || (CO / groups) % hdn::hc::TILE_M != 0 || Hi > 1024 || Wi > 1024) return HDN_E_LIMIT;
+  const int Ho = Hi - 2, Wo = Wi - 2, CG = CO / groups;
+  const int rows = (hdn::hc::TILE_N - 1 + Wo - 1) / Wo + 1 + 2;                    // the patch of 64 consecutive output pixels, as above
+  if ((rows < Hi ? rows : Hi) * Wi > hdn::hc::LP_MAX) return HDN_E_LIMIT;
+  if ((long long)n * B > 65535) return HDN_E_LIMIT;                                // grid z
+  if (!hdn::aligned16(w_packed)) return HDN_E_LIMIT;
+  const long long image = (long long)hdn::hc::CI * Hi * Wi;
+  if (x_batch_stride < image) return HDN_E_LIMIT;
+  const size_t level_out = (size_t)CO * B * Ho * Wo;
+  const uintptr_t o0 = reinterpret_cast<uintptr_t>(out), o1 = o0 + n * level_out * sizeof(float);
+  hdn::hc::Ptrs P{};
+  for (int i = 0; i < n; ++i) {
+    if (!xs[i]) return HDN_E_NULL;
+    const uintptr_t x0 = reinterpret_cast<uintptr_t>(xs[i]), x1 = x0 + (size_t)((B - 1) * x_batch_stride + image) * sizeof(float);
+    if (x0 < o1 && o0 < x1) return HDN_E_ALIAS;
+    P.x[i] = xs[i];
+    P.out[i] = out + i * level_out;
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  for (int i = 0; i < n; ++i) {                                                    // the range guard: one reduction per level where the images are adjacent
+    if (x_batch_stride == image) {
+      if (const int rr = hdn::check_fp16_range(xs[i], image * B, s)) return rr;
+    } else {
+      for (int b = 0; b < B; ++b)
+        if (const int rr = hdn::check_fp16_range(xs[i] + b * x_batch_stride, image, s)) return rr;
+    }
+  }
+  static hdn::PerDeviceOnce attr;
+  const int dev_ = hdn::PerDeviceOnce::device();
+  if (!attr.done(dev_)) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hdn::hc::head_conv_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, hdn::hc::LDS_BYTES);
+    if (e != hipSuccess) return -(1000 + (int)e);
+    attr.set(dev_);
+  }
+  const long long sc = nhwc ? 1 : (long long)Hi * Wi, sy = nhwc ? (long long)Wi * hdn::hc::CI : Wi, sx = nhwc ? hdn::hc::CI : 1;
+  const dim3 grid((Ho * Wo + hdn::hc::TILE_N - 1) / hdn::hc::TILE_N, CO / hdn::hc::TILE_M, n * B);
+  hipLaunchKernelGGL(hdn::hc::head_conv_kernel<true>, grid, dim3(512), hdn::hc::LDS_BYTES, s, P, static_cast<const hdn::hc::u32x4*>(w_packed), bias, CO, Hi,
+                     Wi, sc, sy, sx, B, x_batch_stride, CG);
   return hdn::launch_status();
 }

@@ -10,11 +10,15 @@ PyTorch-ROCm (MIOpen / hipBLASLt); what changes is the schedule of a frame:
     level as one convolution, the 1x1 convolutions of all levels and the weighted sum as two batched matrix products): ~15 launches
     per head instead of ~70;
   * the template branch conv_kernel(z_f) is computed once per template (the reference recomputes it every
-    frame although self.zf only changes in template(), model_builder_e2e_unconstrained_v2.py:87-96, ban.py:74).
+    frame although self.zf only changes in template(), model_builder_e2e_unconstrained_v2.py:87-96, ban.py:74);
+  * opt-in (HDN_HIP_HEADS=1 or head._hdn_hip_heads = True, default off): the template branch of all levels and both branches as
+    ONE launch of hdn_head_conv3x3_batch_f32 at any batch, and conv_search at B > 1 as one launch of the same kernel.
 `fused_forward` works on any object with the reference's attribute layout, so install() can bind it onto the
 reference's own MultiBAN / MultiCircBAN classes.
 """
 from __future__ import annotations
+
+import os
 
 import torch
 import torch.nn as nn
@@ -127,6 +131,32 @@ def invalidate_template_cache(head):
     object.__setattr__(head, "_hdn_refs_template", None)
     object.__setattr__(head, "_hdn_refs_head", None)
     object.__setattr__(head, "_hdn_packable", None)
+    object.__setattr__(head, "_hdn_template_pack", None)
+    object.__setattr__(head, "_hdn_search_pack", None)
+
+
+_HIP_HEADS = None
+
+
+def hip_heads() -> bool:
+    """HDN_HIP_HEADS (default off), read once: the template branch at any batch and conv_search at B > 1 on hdn_head_conv3x3_batch_f32."""
+    global _HIP_HEADS
+    if _HIP_HEADS is None:
+        _HIP_HEADS = os.environ.get("HDN_HIP_HEADS", "0") not in ("", "0")
+    return _HIP_HEADS
+
+
+def _hip_heads_on(head) -> bool:
+    v = getattr(head, "_hdn_hip_heads", None)                # the per-head attribute overrides the environment
+    return hip_heads() if v is None else bool(v)
+
+
+class _ConvPack:
+    """The 3x3 convolutions of one side (conv_search or conv_kernel) of all levels, BatchNorm folded, cls || loc along CO: ws / bs the fp32 weights
+    and biases per level, wsp / bsp the stream and the [n, CO] bias hdn_head_conv3x3(_batch)_f32 take (None where the kernel does not fit).
+    `key`: the version counters it was built from; `ok`: what the predicate of its path said for that key."""
+
+    __slots__ = ("key", "ok", "ws", "bs", "wsp", "bsp")
 
 
 class _PackedHead:
@@ -154,8 +184,13 @@ def _head_key(self, boxes):
 def _packable(self, boxes, x_fs):
     """The packed path covers the reference's configuration: B = 1 on a GPU, every level with the same channel counts and the
     module layout of DepthwiseXCorr (conv3x3 no bias + BN + ReLU; conv1x1 no bias + BN + ReLU + conv1x1)."""
+    return x_fs[0].shape[0] == 1 and _packable_any_batch(self, boxes, x_fs)
+
+
+def _packable_any_batch(self, boxes, x_fs):
+    """_packable without its B = 1 condition: what the batched conv_search (hdn_head_conv3x3_batch_f32) asks of the modules."""
     x0 = x_fs[0]
-    if not x0.is_cuda or x0.shape[0] != 1 or x0.dtype != torch.float32 or any(x.shape != x0.shape for x in x_fs):
+    if not x0.is_cuda or x0.dtype != torch.float32 or any(x.shape != x0.shape for x in x_fs):
         return False
     ref = None
     for box in boxes:
@@ -216,6 +251,131 @@ def _pack_conv_search(ws):
                    lambda o, nb: lib.hdn_pack_head_conv3x3_f32(ptrs, n, CO, o, nb)).to(ws[0].device)
 
 
+def _patch_fits(Hi, Wi):
+    """The patch of 64 consecutive output pixels (their rows + 2, full width) fits the 224 pixels head_conv.hip stages."""
+    return Hi >= 3 and Wi >= 3 and min((63 + Wi - 3) // (Wi - 2) + 3, Hi) * Wi <= 224
+
+
+def _pack_convs(boxes, name):
+    """`name` (conv_search / conv_kernel) of every level -> a _ConvPack (key / ok left to the caller)."""
+    pk = _ConvPack()
+    pk.ws, pk.bs = [], []
+    for box in boxes:
+        wc, bc = _fold_bn(getattr(box.cls, name)[0], getattr(box.cls, name)[1])
+        wl, bl = _fold_bn(getattr(box.loc, name)[0], getattr(box.loc, name)[1])
+        pk.ws.append(torch.cat([wc, wl], 0).contiguous())
+        pk.bs.append(torch.cat([bc, bl], 0).contiguous())
+    # all levels as one launch on the matrix cores (hdn_head_conv3x3_f32 / _batch_f32): 3x3 / stride 1 / no padding, 256 input channels
+    w0 = pk.ws[0]
+    fits_conv = (w0.is_cuda and len(boxes) <= 4 and tuple(w0.shape[1:]) == (256, 3, 3) and w0.shape[0] % 32 == 0 and all(w.shape == w0.shape for w in pk.ws)
+                 and max(float(w.abs().max()) for w in pk.ws) < 65504.0)
+    pk.wsp = _pack_conv_search(pk.ws) if fits_conv else None
+    pk.bsp = torch.stack(pk.bs).contiguous() if fits_conv else None
+    return pk
+
+
+def _template_packable(boxes, z_fs, need_gpu=True):
+    """The template branch as one launch of hdn_head_conv3x3_batch_f32, at any B: fp32 on a GPU (need_gpu=False: anywhere, for host tests), every
+    level the same shape with 256 channels inside the kernel's patch limit, n <= 4, and conv_kernel of every (level, branch) the reference's
+    Sequential(Conv2d 3x3 no bias / stride 1 / no padding, eval-mode BatchNorm2d, ReLU) with one hidden width (a multiple of 32: the cls and loc
+    halves are tile-aligned groups) and folded |w| < 65504 (two fp16 pieces)."""
+    z0 = z_fs[0]
+    n = len(boxes)
+    if (need_gpu and not z0.is_cuda) or z0.dtype != torch.float32 or z0.dim() != 4 or any(z.shape != z0.shape for z in z_fs):
+        return False
+    B, C, Hi, Wi = z0.shape
+    if n != len(z_fs) or not 1 <= n <= 4 or C != 256 or B < 1 or n * B > 65535 or not _patch_fits(Hi, Wi):
+        return False
+    ref = None
+    for box in boxes:
+        for br in (box.cls, box.loc):
+            ck = br.conv_kernel
+            if not (isinstance(ck, nn.Sequential) and len(ck) == 3 and isinstance(ck[0], nn.Conv2d) and isinstance(ck[1], nn.BatchNorm2d)
+                    and isinstance(ck[2], nn.ReLU)):
+                return False
+            c0, bn = ck[0], ck[1]
+            if bn.training or not bn.track_running_stats or not bn.affine or bn.running_mean is None:
+                return False          # _fold_bn folds the running statistics and the affine weights: eval-mode BatchNorm only
+            if c0.bias is not None or c0.stride != (1, 1) or c0.padding != (0, 0) or c0.dilation != (1, 1) or c0.groups != 1:
+                return False
+            shape = tuple(c0.weight.shape)
+            if ref is None:
+                ref = shape
+            if shape != ref or shape[1:] != (256, 3, 3) or shape[0] % 32 != 0:
+                return False
+            if c0.weight.device.type != "meta" and not float(_fold_bn(c0, bn)[0].detach().abs().max()) < 65504.0:
+                return False
+    return True
+
+
+def _template_pack(self, boxes, branches, z_fs):
+    """The _ConvPack of conv_kernel for this head, or None where _template_packable refuses: rebuilt when a conv_kernel parameter / buffer or the
+    template's shape changes (the version counters _TemplateCache is keyed on), dropped by invalidate_template_cache."""
+    key = (_param_versions(branches), tuple(z_fs[0].shape), z_fs[0].device, z_fs[0].dtype)
+    tp = getattr(self, "_hdn_template_pack", None)
+    if tp is None or tp.key != key:
+        if _template_packable(boxes, z_fs):
+            tp = _pack_convs(boxes, "conv_kernel")
+            tp.ok = tp.wsp is not None
+        else:
+            tp = _ConvPack()
+            tp.ok = False
+        tp.key = key
+        object.__setattr__(self, "_hdn_template_pack", tp)
+    return tp if tp.ok else None
+
+
+def _search_pack(self, boxes, x_fs):
+    """The _ConvPack of conv_search for the batched form (B > 1), or None where it does not apply; keyed as _PackedHead is."""
+    key = (_head_key(self, boxes), tuple(x_fs[0].shape), x_fs[0].device, x_fs[0].dtype)
+    sp = getattr(self, "_hdn_search_pack", None)
+    if sp is None or sp.key != key:
+        _, C, Hi, Wi = x_fs[0].shape
+        if len(boxes) <= 4 and C == 256 and _patch_fits(Hi, Wi) and len(boxes) * x_fs[0].shape[0] <= 65535 and _packable_any_batch(self, boxes, x_fs):
+            sp = _pack_convs(boxes, "conv_search")
+            sp.ok = sp.wsp is not None
+        else:
+            sp = _ConvPack()
+            sp.ok = False
+        sp.key = key
+        object.__setattr__(self, "_hdn_search_pack", sp)
+    return sp if sp.ok else None
+
+
+def head_conv_batch(x_fs, wsp, bsp, groups=2):
+    """n levels [B, 256, Hi, Wi] through one launch of hdn_head_conv3x3_batch_f32 (3x3 / no padding + bias + ReLU with the stream `wsp` of
+    _pack_conv_search and the bias `bsp` [n, CO]) -> [n, groups, B, CO / groups, Ho, Wo] contiguous: out[l, g] is a contiguous [B, CO / groups, Ho, Wo].
+    An image that is dense NCHW or dense channels-last is read where it is, whatever the batch stride (a batch slice needs no copy)."""
+    import ctypes
+
+    from . import _lib
+
+    x0 = x_fs[0]
+    dev = _lib.require_device(*x_fs)
+    n, (B, C, Hi, Wi) = len(x_fs), x0.shape
+    if C != 256 or any(x.shape != x0.shape for x in x_fs):
+        raise ValueError("head_conv_batch: every level must be [B, 256, Hi, Wi] of one shape")
+    image = C * Hi * Wi
+    forms = ((Hi * Wi, Wi, 1), (1, Wi * C, C))                                    # (channel, row, pixel) strides: NCHW, channels-last
+    nhwc = 1 if tuple(x0.stride()[1:]) == forms[1] else 0
+
+    def dense(x):
+        return tuple(x.stride()[1:]) == forms[nhwc] and (B == 1 or x.stride(0) >= image)
+
+    xs = [x.detach() for x in x_fs]
+    xs = [x if dense(x) else x.contiguous(memory_format=torch.channels_last if nhwc else torch.contiguous_format) for x in xs]
+    if B > 1 and len({x.stride(0) for x in xs}) > 1:                                # one batch stride per launch
+        xs = [x if x.stride(0) == image else x.contiguous(memory_format=torch.channels_last if nhwc else torch.contiguous_format) for x in xs]
+    xbs = image if B == 1 else xs[0].stride(0)
+    CO = bsp.shape[1]
+    out = torch.empty((n, groups, B, CO // groups, Hi - 2, Wi - 2), dtype=torch.float32, device=dev)
+    with _lib.device_guard(dev):
+        rc = _lib.load().hdn_head_conv3x3_batch_f32((ctypes.c_void_p * n)(*[t.data_ptr() for t in xs]), _lib.ptr(wsp), _lib.ptr(bsp), _lib.ptr(out),
+                                                    n, B, groups, CO, Hi, Wi, nhwc, xbs, _lib.stream_ptr(dev))
+    _lib.check(rc, "head_conv_batch")
+    return out
+
+
 def head_conv_search(x_fs, pk):
     """The n levels' conv_search (both branches) + bias + ReLU in one launch -> [n, 2 hidden, Ho, Wo] contiguous (hdn_head_conv3x3_f32)."""
     import ctypes
@@ -262,12 +422,8 @@ def _pack_head(self, boxes):
     n = len(boxes)
     pk = _PackedHead()
     pk.key = _head_key(self, boxes)
-    pk.ws, pk.bs = [], []
-    for box in boxes:
-        wc, bc = _fold_bn(box.cls.conv_search[0], box.cls.conv_search[1])
-        wl, bl = _fold_bn(box.loc.conv_search[0], box.loc.conv_search[1])
-        pk.ws.append(torch.cat([wc, wl], 0).contiguous())
-        pk.bs.append(torch.cat([bc, bl], 0).contiguous())
+    cs = _pack_convs(boxes, "conv_search")                   # (shared with the batched form: _search_pack)
+    pk.ws, pk.bs, pk.wsp, pk.bsp = cs.ws, cs.bs, cs.wsp, cs.bsp
     pk.hidden = hidden = boxes[0].cls.head[0].weight.shape[0]
     order = [box.cls for box in boxes] + [box.loc for box in boxes]          # stacked order: cls of every level, then loc
     w1, b1 = zip(*[_fold_bn(br.head[0], br.head[1]) for br in order])
@@ -292,12 +448,6 @@ def _pack_head(self, boxes):
     lds = n * (hidden * 128 + 4 * hidden + 4 * om * hidden) + (hidden // 32) * 8 * 32 * 4       # what the kernel stages per workgroup (head_tail.hip)
     fits = pk.w1.is_cuda and hidden in (128, 256) and om <= 8 and n <= 4 and lds <= 160 * 1024 and float(pk.w1.abs().max()) < 65504.0
     pk.w1p = _pack_w1(pk.w1) if fits else None
-    # conv_search of all levels as one launch on the matrix cores (hdn_head_conv3x3_f32): 3x3 / stride 1 / no padding, 256 input channels
-    w0 = pk.ws[0]
-    fits_conv = (w0.is_cuda and n <= 4 and tuple(w0.shape[1:]) == (256, 3, 3) and w0.shape[0] % 32 == 0 and all(w.shape == w0.shape for w in pk.ws)
-                 and max(float(w.abs().max()) for w in pk.ws) < 65504.0)
-    pk.wsp = _pack_conv_search(pk.ws) if fits_conv else None
-    pk.bsp = torch.stack(pk.bs).contiguous() if fits_conv else None
     return pk
 
 
@@ -364,8 +514,14 @@ def fused_forward(self, z_fs, x_fs, circular=None):
         circular = bool(getattr(boxes[0].cls, "_circular", False)) or type(boxes[0].cls).__name__.endswith("Circ")
     with torch.no_grad():
         cache = getattr(self, "_hdn_template_cache", None)
+        hip_heads_on = _hip_heads_on(self)
         if cache is None or not cache.matches(z_fs, branches, False):
-            kern = [br.conv_kernel(z).contiguous() for box, z in zip(boxes, z_fs) for br in (box.cls, box.loc)]   # (NCHW once, not per frame)
+            tp = _template_pack(self, boxes, branches, z_fs) if hip_heads_on else None
+            if tp is not None:
+                y = head_conv_batch(z_fs, tp.wsp, tp.bsp)     # one launch; (cls, loc) per level, each a contiguous [B, hidden, h, w] view
+                kern = [y[l, g] for l in range(n) for g in range(2)]
+            else:
+                kern = [br.conv_kernel(z).contiguous() for box, z in zip(boxes, z_fs) for br in (box.cls, box.loc)]   # (NCHW once, not per frame)
             cache = _TemplateCache(z_fs, branches, False, kern)
             object.__setattr__(self, "_hdn_template_cache", cache)
         kern = cache.kern
@@ -377,7 +533,12 @@ def fused_forward(self, z_fs, x_fs, circular=None):
         if (pv[1] and all(x.shape == x_fs[0].shape for x in x_fs) and all(k.shape == kern[0].shape for k in kern)
                 and not getattr(self, "_hdn_no_packed_head", False)):
             return _packed_forward(self, boxes, kern, x_fs, circular)
-        srch = [br.conv_search(x) for box, x in zip(boxes, x_fs) for br in (box.cls, box.loc)]
+        sp = _search_pack(self, boxes, x_fs) if hip_heads_on and x_fs[0].shape[0] > 1 else None
+        if sp is not None:
+            y = head_conv_batch(x_fs, sp.wsp, sp.bsp)         # conv_search of every level and both branches at B > 1: one launch
+            srch = [y[l, g] for l in range(n) for g in range(2)]
+        else:
+            srch = [br.conv_search(x) for box, x in zip(boxes, x_fs) for br in (box.cls, box.loc)]
         same = all(k.shape == kern[0].shape for k in kern) and all(s.shape == srch[0].shape for s in srch)
         if same and len(kern) <= 8:
             feats = xcorr_depthwise_multi(srch, kern, circular=circular)

@@ -397,6 +397,25 @@ int hdn_head_conv3x3_f32(const float* const* xs, const void* w_packed, const flo
                          void* stream);
 
 /*
+ * The same convolution at any batch B, into one buffer (added within ABI 10): the template branch of the heads,
+ *   kernel = self.conv_kernel(kernel)   (hdn/models/head/ban.py:55-59,74; DepthwiseXCorrCirc in ban_lp.py likewise),
+ * for all levels and both branches of a MultiBAN / MultiCircBAN in one launch, and conv_search (ban.py:55-59,75) of the lock-step trackers at B > 1.
+ * xs[i]: level i's input [B, 256, Hi, Wi] fp32, every image dense NCHW (nhwc = 0) or dense channels-last (nhwc = 1), the images x_batch_stride
+ * (>= 256 Hi Wi) elements apart - a batch slice of a larger tensor needs no copy.  w_packed / bias [n, CO]: exactly what hdn_head_conv3x3_f32 takes
+ * (hdn_pack_head_conv3x3_f32).  out: one contiguous buffer [n][groups][B][CO / groups][Ho Wo], groups 1 or 2, CO / groups a multiple of 32: output
+ * channel co of level i, image b is at (((i groups + co / (CO / groups)) B + b) (CO / groups) + co % (CO / groups)) Ho Wo.  With groups = 2 and the cls
+ * and loc weights of a level concatenated along CO, each branch of each level is a contiguous [B, hidden, Ho, Wo] - what hdn_xcorr_depthwise_multi_f32
+ * reads; with B = 1 it is the layout of hdn_head_conv3x3_f32 with adjacent outs.  Every output element is summed in the order of hdn_head_conv3x3_f32:
+ * image b of a batch is bit-equal to that entry on the image alone (batch invariance).
+ * All arguments are checked before the first HIP call: HDN_E_NULL a null pointer; HDN_E_SHAPE n, B or CO <= 0, Hi or Wi < 3, groups not 1 or 2;
+ * HDN_E_LIMIT n > 4, CO / groups no multiple of 32, the 224-pixel patch limit above, n B > 65535, w_packed not 16-byte aligned, x_batch_stride
+ * < 256 Hi Wi; HDN_E_ALIAS out overlapping an input.  Takes part in the range guard (hdn_set_check_range) on every image.  Asynchronous on `stream`;
+ * allocates nothing; deterministic; capturable.
+ */
+int hdn_head_conv3x3_batch_f32(const float* const* xs, const void* w_packed, const float* bias, float* out, int n, int B, int groups, int CO, int Hi,
+                               int Wi, int nhwc, long long x_batch_stride, void* stream);
+
+/*
  * Whole residual-block convolutions of that trunk on the matrix cores, channels-last fp32 in and out:
  *   hdn_conv3x3_bias_relu_f32:  out = relu(conv3x3/s1/p1(x, W) + bias[c] (+ residual)),  x / residual / out [B,S,S,C], C -> C channels,
  *       (S, C) = (32, 64), (16, 128), (8, 256), (4, 512): conv1 / conv2 + bn + relu (+ `out += residual`) of BasicBlock.forward;
@@ -431,7 +450,7 @@ int hdn_head_conv3x3_f32(const float* const* xs, const void* w_packed, const flo
  * addition and hdn_bias_relu_f32 / hdn_conv3x3_finish_f32 are the same in either domain (they are positively homogeneous / linear with the scaled bias).
  *
  * Range guard of the two-fp16-piece kernels (ABI 6): hdn_conv3x3_bias_relu_f32, hdn_conv3x3s2_ds_f32, hdn_conv3x3_v2_f32,
- * hdn_conv3x3_chain_f32 (activation inputs), hdn_trunk_stem_mfma_f32, hdn_head_conv3x3_f32, hdn_head_tail_f32, hdn_conv1x1_f32, hdn_conv3x3s2_f32 and hdn_conv3x3d_f32 are finite and fp32-accurate
+ * hdn_conv3x3_chain_f32 (activation inputs), hdn_trunk_stem_mfma_f32, hdn_head_conv3x3_f32, hdn_head_conv3x3_batch_f32, hdn_head_tail_f32, hdn_conv1x1_f32, hdn_conv3x3s2_f32 and hdn_conv3x3d_f32 are finite and fp32-accurate
  * for |x| < 1.67e7 on their fp32 INPUTS by default (since ABI 9; 65,504 before).  Beyond that the first fp16 piece is inf and the result NaN,
  * where the reference's fp32 convolution stays finite up to 3.4e38.  With HDN_CHECK_RANGE=1 in the environment, or after hdn_set_check_range(1)
  * (returns the previous setting), each of those entry points first reduces max |x| over its input and returns HDN_E_LIMIT when it is
