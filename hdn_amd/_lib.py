@@ -59,6 +59,8 @@ SIGNATURES = {
     "hdn_bias_relu_f32": (_i, [_c_float_p] * 3 + [_i] * 4 + [ctypes.c_void_p]),
     "hdn_avgpool_fc_f32": (_i, [_c_float_p] * 4 + [_i] * 6 + [ctypes.c_void_p]),
     "hdn_head_tail_f32": (_i, [_c_float_p, ctypes.c_void_p] + [_c_float_p] * 4 + [_i] * 4 + [ctypes.c_void_p]),
+    "hdn_head_tail_batch_f32": (_i, [_c_float_p, ctypes.c_void_p] + [_c_float_p] * 4 + [_i] * 6 + [ctypes.c_void_p]),
+    "hdn_head_tail_lds_bytes": (ctypes.c_longlong, [_i] * 3),
     "hdn_head_conv3x3_f32": (_i, [ctypes.c_void_p, ctypes.c_void_p, _c_float_p, ctypes.c_void_p] + [_i] * 5 + [ctypes.c_void_p]),
     "hdn_head_conv3x3_batch_f32": (_i, [ctypes.c_void_p, ctypes.c_void_p, _c_float_p, _c_float_p] + [_i] * 7 + [ctypes.c_longlong, ctypes.c_void_p]),
     "hdn_set_check_range": (_i, [_i]),

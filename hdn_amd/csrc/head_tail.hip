@@ -59,10 +59,14 @@ __device__ __forceinline__ void wait_half(u32x4 (&a)[HK][2]) {
 }
 
 // H hidden channels, N levels (compile-time: every load of the prologue is then issued before the first wait); workgroup = H / 32 waves, one 32-row tile
-// of hidden channels each
-template <int H, int N>
+// of hidden channels each.
+// BATCH (hdn_head_tail_batch_f32): blockIdx.z = image; a group of feats is [B][H][P] and the image is img * H * P elements into it; out is the cls block
+// [B][oc][P] followed by the loc block [B][ol][P], and the workgroup writes the oc (ol) rows of its image.  Only the two addresses and the row count
+// differ: an output element is summed exactly as without BATCH.  An image's last tile is partial on its own (no tile spans two images).
+template <int H, int N, bool BATCH>
 __global__ __launch_bounds__(2 * H) void head_tail_kernel(const float* __restrict__ feats, const u32x4* __restrict__ w1p, const float* __restrict__ b1,
-                                                          const float* __restrict__ wf, const float* __restrict__ bf, float* __restrict__ out, int P, int om) {
+                                                          const float* __restrict__ wf, const float* __restrict__ bf, float* __restrict__ out, int P, int om,
+                                                          int B, int oc, int ol) {
   constexpr int n = N;
   constexpr int NW = H / 32, NT = 64 * NW, KSTEPS = H / 16;
   constexpr int KH_BYTES = TILE * 16, KSTEP_BYTES = 2 * KH_BYTES, PIECE_BYTES = KSTEPS * KSTEP_BYTES, IMG_BYTES = 2 * PIECE_BYTES;   // B image of a level
@@ -90,7 +94,8 @@ __global__ __launch_bounds__(2 * H) void head_tail_kernel(const float* __restric
 #pragma unroll
     for (int q = 0; q < ITEMS; ++q) {
       const int item = tid + q * NT, p = item & 31, cg = item >> 5;
-      const float* src = feats + (size_t)(br * n + l) * H * P + (size_t)(cg * 8) * P + min(p0 + p, P - 1);    // (clamped, not branched)
+      const size_t plane = BATCH ? (size_t)(br * n + l) * B + blockIdx.z : (size_t)(br * n + l);             // the [H][P] block of (group, image)
+      const float* src = feats + plane * H * P + (size_t)(cg * 8) * P + min(p0 + p, P - 1);                   // (clamped, not branched)
 #pragma unroll
       for (int j = 0; j < 8; ++j) v[l][q][j] = src[(size_t)j * P];
     }
@@ -198,7 +203,12 @@ __global__ __launch_bounds__(2 * H) void head_tail_kernel(const float* __restric
     float acc = bf[br * om + o];
 #pragma unroll
     for (int w = 0; w < NW; ++w) acc += red[(w * MAX_OUT + o) * TILE + p];
-    if (p0 + p < P) out[((size_t)br * om + o) * P + p0 + p] = acc;
+    if (BATCH) {                                                         // row o of (branch, image): (br B oc + img n_out[br] + o) P
+      const int rows = br ? ol : oc;
+      if (o < rows && p0 + p < P) out[((size_t)br * B * oc + (size_t)blockIdx.z * rows + o) * P + p0 + p] = acc;
+    } else if (p0 + p < P) {
+      out[((size_t)br * om + o) * P + p0 + p] = acc;
+    }
   }
 }
 
@@ -208,28 +218,32 @@ static size_t lds_bytes(int n, int om) {
   return (size_t)n * (2 * (H / 16) * 2 * TILE * 16) + sizeof(float) * ((size_t)n * H + (size_t)n * om * H + (size_t)(H / 32) * MAX_OUT * TILE);
 }
 
-template <int H, int N>
-static int launch(const float* feats, const void* w1p, const float* b1, const float* wf, const float* bf, float* out, int P, int om, hipStream_t s) {
+// BATCH: grid z = image, out rows (oc, ol) per image; otherwise B = 1 and both branches write om rows
+template <int H, int N, bool BATCH>
+static int launch(const float* feats, const void* w1p, const float* b1, const float* wf, const float* bf, float* out, int P, int om, int B, int oc, int ol,
+                  hipStream_t s) {
   const size_t lds = lds_bytes<H>(N, om);
   if (lds > LDS_LIMIT) return HDN_E_LIMIT;
   static PerDeviceOnce attr;
   const int dev_ = PerDeviceOnce::device();
   if (!attr.done(dev_)) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&head_tail_kernel<H, N>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&head_tail_kernel<H, N, BATCH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT);
     if (e != hipSuccess) return -(1000 + (int)e);
     attr.set(dev_);
   }
-  hipLaunchKernelGGL((head_tail_kernel<H, N>), dim3((P + TILE - 1) / TILE, 2), dim3(2 * H), lds, s, feats, static_cast<const u32x4*>(w1p), b1, wf, bf, out, P, om);
+  hipLaunchKernelGGL((head_tail_kernel<H, N, BATCH>), dim3((P + TILE - 1) / TILE, 2, B), dim3(2 * H), lds, s, feats, static_cast<const u32x4*>(w1p), b1, wf, bf,
+                     out, P, om, B, oc, ol);
   return launch_status();
 }
 
-template <int H>
-static int launch_levels(const float* feats, const void* w1p, const float* b1, const float* wf, const float* bf, float* out, int n, int P, int om, hipStream_t s) {
+template <int H, bool BATCH>
+static int launch_levels(const float* feats, const void* w1p, const float* b1, const float* wf, const float* bf, float* out, int n, int P, int om, int B, int oc,
+                         int ol, hipStream_t s) {
   switch (n) {
-    case 1: return launch<H, 1>(feats, w1p, b1, wf, bf, out, P, om, s);
-    case 2: return launch<H, 2>(feats, w1p, b1, wf, bf, out, P, om, s);
-    case 3: return launch<H, 3>(feats, w1p, b1, wf, bf, out, P, om, s);     // MultiBAN / MultiCircBAN: three levels
-    case 4: return launch<H, 4>(feats, w1p, b1, wf, bf, out, P, om, s);
+    case 1: return launch<H, 1, BATCH>(feats, w1p, b1, wf, bf, out, P, om, B, oc, ol, s);
+    case 2: return launch<H, 2, BATCH>(feats, w1p, b1, wf, bf, out, P, om, B, oc, ol, s);
+    case 3: return launch<H, 3, BATCH>(feats, w1p, b1, wf, bf, out, P, om, B, oc, ol, s);     // MultiBAN / MultiCircBAN: three levels
+    case 4: return launch<H, 4, BATCH>(feats, w1p, b1, wf, bf, out, P, om, B, oc, ol, s);
     default: return HDN_E_LIMIT;
   }
 }
@@ -246,6 +260,36 @@ extern "C" int hdn_head_tail_f32(const float* feats, const void* w1_packed, cons
   if (!hdn::aligned16(w1_packed)) return HDN_E_LIMIT;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (const int rr = hdn::check_fp16_range(feats, (long long)2 * n_levels * hidden * pixels, s)) return rr;
-  return hidden == 256 ? hdn::ht::launch_levels<256>(feats, w1_packed, b1, wf, bf, out, n_levels, pixels, n_out, s)
-                        : hdn::ht::launch_levels<128>(feats, w1_packed, b1, wf, bf, out, n_levels, pixels, n_out, s);
+  return hidden == 256 ? hdn::ht::launch_levels<256, false>(feats, w1_packed, b1, wf, bf, out, n_levels, pixels, n_out, 1, n_out, n_out, s)
+                        : hdn::ht::launch_levels<128, false>(feats, w1_packed, b1, wf, bf, out, n_levels, pixels, n_out, 1, n_out, n_out, s);
+}
+
+// Bytes of LDS a workgroup stages for (n_levels, hidden, n_out = max(n_out_cls, n_out_loc)); negative = HDN_E_*.  Both entries refuse more than 160 KB.
+extern "C" long long hdn_head_tail_lds_bytes(int n_levels, int hidden, int n_out) {
+  if (n_levels <= 0 || hidden <= 0 || n_out <= 0) return HDN_E_SHAPE;
+  if (n_levels > 4 || n_out > hdn::ht::MAX_OUT || (hidden != 128 && hidden != 256)) return HDN_E_LIMIT;
+  return (long long)(hidden == 256 ? hdn::ht::lds_bytes<256>(n_levels, n_out) : hdn::ht::lds_bytes<128>(n_levels, n_out));
+}
+
+// The same tail at any batch B (the lock-step trackers' heads): feats [2 n_levels][B][hidden][pixels], each group a contiguous [B, hidden, Ho, Wo] as
+// hdn_xcorr_depthwise_multi_f32 writes it; out = the cls block [B][n_out_cls][pixels] followed by the loc block [B][n_out_loc][pixels].  The weights are
+// those of hdn_head_tail_f32 with n_out = max(n_out_cls, n_out_loc).  Every argument is checked before the first HIP call.
+extern "C" int hdn_head_tail_batch_f32(const float* feats, const void* w1_packed, const float* b1, const float* wf, const float* bf, float* out, int n_levels,
+                                       int B, int hidden, int pixels, int n_out_cls, int n_out_loc, void* stream) {
+  if (!feats || !w1_packed || !b1 || !wf || !bf || !out) return HDN_E_NULL;
+  if (n_levels <= 0 || B <= 0 || hidden <= 0 || pixels <= 0 || n_out_cls <= 0 || n_out_loc <= 0) return HDN_E_SHAPE;
+  if (n_levels > 4 || n_out_cls > hdn::ht::MAX_OUT || n_out_loc > hdn::ht::MAX_OUT || (hidden != 128 && hidden != 256) || B > 65535) return HDN_E_LIMIT;
+  const long long n_feats = (long long)2 * n_levels * B * hidden * pixels;                     // (< 2^63: every factor is below 2^31 and the first three below 2^20)
+  if (n_feats > 0x7fffffffLL) return HDN_E_LIMIT;
+  const int om = n_out_cls > n_out_loc ? n_out_cls : n_out_loc;
+  if ((hidden == 256 ? hdn::ht::lds_bytes<256>(n_levels, om) : hdn::ht::lds_bytes<128>(n_levels, om)) > hdn::ht::LDS_LIMIT) return HDN_E_LIMIT;
+  if (!hdn::aligned16(w1_packed)) return HDN_E_LIMIT;
+  const long long n_out = (long long)B * (n_out_cls + n_out_loc) * pixels;
+  const uintptr_t f0 = reinterpret_cast<uintptr_t>(feats), f1 = f0 + (size_t)n_feats * sizeof(float);
+  const uintptr_t o0 = reinterpret_cast<uintptr_t>(out), o1 = o0 + (size_t)n_out * sizeof(float);
+  if (f0 < o1 && o0 < f1) return HDN_E_ALIAS;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (const int rr = hdn::check_fp16_range(feats, n_feats, s)) return rr;                      // every image of every group
+  return hidden == 256 ? hdn::ht::launch_levels<256, true>(feats, w1_packed, b1, wf, bf, out, n_levels, pixels, om, B, n_out_cls, n_out_loc, s)
+                        : hdn::ht::launch_levels<128, true>(feats, w1_packed, b1, wf, bf, out, n_levels, pixels, om, B, n_out_cls, n_out_loc, s);
 }

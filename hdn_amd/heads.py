@@ -12,7 +12,9 @@ PyTorch-ROCm (MIOpen / hipBLASLt); what changes is the schedule of a frame:
   * the template branch conv_kernel(z_f) is computed once per template (the reference recomputes it every
     frame although self.zf only changes in template(), model_builder_e2e_unconstrained_v2.py:87-96, ban.py:74);
   * opt-in (HDN_HIP_HEADS=1 or head._hdn_hip_heads = True, default off): the template branch of all levels and both branches as
-    ONE launch of hdn_head_conv3x3_batch_f32 at any batch, and conv_search at B > 1 as one launch of the same kernel.
+    ONE launch of hdn_head_conv3x3_batch_f32 at any batch, and conv_search at B > 1 as one launch of the same kernel;
+  * opt-in level 2 (HDN_HIP_HEADS=2 or head._hdn_hip_heads = 2): on top of that, everything behind the correlations at B > 1 as ONE launch
+    of hdn_head_tail_batch_f32 - a head forward at any batch is then three launches of this project's kernels and no library call.
 `fused_forward` works on any object with the reference's attribute layout, so install() can bind it onto the
 reference's own MultiBAN / MultiCircBAN classes.
 """
@@ -149,6 +151,26 @@ def hip_heads() -> bool:
 def _hip_heads_on(head) -> bool:
     v = getattr(head, "_hdn_hip_heads", None)                # the per-head attribute overrides the environment
     return hip_heads() if v is None else bool(v)
+
+
+_HIP_HEADS_LEVEL = None
+
+
+def hip_heads_level() -> int:
+    """HDN_HIP_HEADS as a level, read once: 0 off (default), 1 what hip_heads() switches on, 2 also the 1x1 tail at B > 1 on hdn_head_tail_batch_f32.
+    Any other non-empty value is level 1, as hip_heads() reads it."""
+    global _HIP_HEADS_LEVEL
+    if _HIP_HEADS_LEVEL is None:
+        v = os.environ.get("HDN_HIP_HEADS", "0").strip()
+        _HIP_HEADS_LEVEL = 0 if v in ("", "0") else 2 if v == "2" else 1
+    return _HIP_HEADS_LEVEL
+
+
+def _hip_heads_level_of(head) -> int:
+    v = getattr(head, "_hdn_hip_heads", None)                # True and 1: level 1; 2: level 2
+    if v is None:
+        return hip_heads_level()
+    return 2 if (v is not True and v == 2) else 1 if v else 0
 
 
 class _ConvPack:
@@ -418,11 +440,44 @@ def head_tail(feats, pk, n):
     return out
 
 
-def _pack_head(self, boxes):
+def head_tail_batch(feats, pk, n, B):
+    """feats [2n, B, H, Ho, Wo] -> (cls [B, oc, Ho, Wo], loc [B, ol, Ho, Wo]), contiguous views of ONE output buffer, through hdn_head_tail_batch_f32
+    (pk: a _PackedHead with w1p)."""
+    from . import _lib
+
+    dev = _lib.require_device(feats)
+    if feats.dim() != 5 or feats.shape[0] != 2 * n or feats.shape[1] != B or feats.dtype != torch.float32 or not feats.is_contiguous():
+        raise ValueError(f"head_tail_batch: feats must be a contiguous float32 [{2 * n}, {B}, H, Ho, Wo], got {tuple(feats.shape)}")
+    H, Ho, Wo = feats.shape[2:]
+    P = Ho * Wo
+    out = torch.empty(B * (pk.oc + pk.ol) * P, dtype=torch.float32, device=dev)
+    with _lib.device_guard(dev):
+        rc = _lib.load().hdn_head_tail_batch_f32(_lib.ptr(feats), _lib.ptr(pk.w1p), _lib.ptr(pk.b1), _lib.ptr(pk.wf), _lib.ptr(pk.bf), _lib.ptr(out),
+                                                 n, B, H, P, pk.oc, pk.ol, _lib.stream_ptr(dev))
+    _lib.check(rc, "head_tail_batch")
+    split = B * pk.oc * P
+    return out[:split].view(B, pk.oc, Ho, Wo), out[split:].view(B, pk.ol, Ho, Wo)
+
+
+def _tail_lds_bytes(n, hidden, om):
+    """What a workgroup of hdn_head_tail(_batch)_f32 stages (head_tail.hip; hdn_head_tail_lds_bytes): the split pixel tile of every level, b1, the branch's
+    block of Wf and the waves' partial sums."""
+    return n * (hidden * 128 + 4 * hidden + 4 * om * hidden) + (hidden // 32) * 8 * 32 * 4
+
+
+def _tail_fits(n, hidden, om, w1):
+    """The shapes and range hdn_head_tail_f32 / hdn_head_tail_batch_f32 take: hidden 128 or 256, at most 8 output rows and 4 levels, the staged operands
+    inside the 160 KB of LDS, and the folded first 1x1 weights `w1` inside fp16 (two pieces).  Asks nothing of the device."""
+    return (hidden in (128, 256) and 1 <= om <= 8 and 1 <= n <= 4 and _tail_lds_bytes(n, hidden, om) <= 160 * 1024
+            and bool(float(w1.detach().abs().max()) < 65504.0))
+
+
+def _pack_head(self, boxes, cs=None):
     n = len(boxes)
     pk = _PackedHead()
     pk.key = _head_key(self, boxes)
-    cs = _pack_convs(boxes, "conv_search")                   # (shared with the batched form: _search_pack)
+    if cs is None:
+        cs = _pack_convs(boxes, "conv_search")               # (shared with the batched form: _search_pack hands its own over)
     pk.ws, pk.bs, pk.wsp, pk.bsp = cs.ws, cs.bs, cs.wsp, cs.bsp
     pk.hidden = hidden = boxes[0].cls.head[0].weight.shape[0]
     order = [box.cls for box in boxes] + [box.loc for box in boxes]          # stacked order: cls of every level, then loc
@@ -445,10 +500,28 @@ def _pack_head(self, boxes):
         pk.bf[0, :pk.oc, 0] += cw[i] * box.cls.head[3].bias
         pk.bf[1, :pk.ol, 0] += lw[i] * box.loc.head[3].bias
     # the whole tail as one launch (hdn_head_tail_f32) where its shapes allow; the two batched matrix products otherwise
-    lds = n * (hidden * 128 + 4 * hidden + 4 * om * hidden) + (hidden // 32) * 8 * 32 * 4       # what the kernel stages per workgroup (head_tail.hip)
-    fits = pk.w1.is_cuda and hidden in (128, 256) and om <= 8 and n <= 4 and lds <= 160 * 1024 and float(pk.w1.abs().max()) < 65504.0
-    pk.w1p = _pack_w1(pk.w1) if fits else None
+    pk.w1p = _pack_w1(pk.w1) if pk.w1.is_cuda and _tail_fits(n, hidden, om, pk.w1) else None
     return pk
+
+
+def _batched_forward(self, boxes, kern, x_fs, sp, circular):
+    """Level 2 at B > 1: conv_search, the correlations and the tail as one launch each (head_conv_batch, xcorr_depthwise_multi into one feats buffer,
+    head_tail_batch).  None where the tail does not fit (the caller goes on with the level-1 path)."""
+    n, B = len(boxes), x_fs[0].shape[0]
+    pk = getattr(self, "_hdn_packed_head", None)
+    key = _head_key(self, boxes)
+    if pk is None or pk.key != key:
+        pk = _pack_head(self, boxes, sp)
+        object.__setattr__(self, "_hdn_packed_head", pk)
+    if pk.w1p is None or tuple(pk.w1.shape[1:]) != (sp.bsp.shape[1] // 2,) * 2:      # (the head's 1x1 is hidden x hidden on conv_search's channels)
+        return None
+    y = head_conv_batch(x_fs, sp.wsp, sp.bsp)                 # [n, 2, B, hidden, Ho, Wo]
+    srch = [y[l, 0] for l in range(n)] + [y[l, 1] for l in range(n)]          # stacked order: cls of every level, then loc
+    kern = list(kern[0::2]) + list(kern[1::2])
+    shape = out_shape(srch[0].shape, kern[0].shape, circular)
+    feats = torch.empty((2 * n, B, pk.hidden, shape[2], shape[3]), dtype=torch.float32, device=y.device)
+    xcorr_depthwise_multi(srch, kern, circular=circular, outs=[feats[i] for i in range(2 * n)])
+    return head_tail_batch(feats, pk, n, B)
 
 
 def _packed_forward(self, boxes, kern, x_fs, circular):
@@ -534,6 +607,11 @@ def fused_forward(self, z_fs, x_fs, circular=None):
                 and not getattr(self, "_hdn_no_packed_head", False)):
             return _packed_forward(self, boxes, kern, x_fs, circular)
         sp = _search_pack(self, boxes, x_fs) if hip_heads_on and x_fs[0].shape[0] > 1 else None
+        if (sp is not None and 2 * n <= 8 and _hip_heads_level_of(self) == 2 and all(k.shape == kern[0].shape for k in kern)
+                and kern[0].shape[:2] == (x_fs[0].shape[0], sp.bsp.shape[1] // 2) and not getattr(self, "_hdn_no_head_tail", False)):
+            out = _batched_forward(self, boxes, kern, x_fs, sp, circular)     # level 2: the 1x1 tail too, three launches in all
+            if out is not None:
+                return out
         if sp is not None:
             y = head_conv_batch(x_fs, sp.wsp, sp.bsp)         # conv_search of every level and both branches at B > 1: one launch
             srch = [y[l, g] for l in range(n) for g in range(2)]

@@ -383,6 +383,30 @@ int hdn_head_tail_f32(const float* feats, const void* w1_packed, const float* b1
                       int pixels, int n_out, void* stream);
 
 /*
+ * The same tail at any batch B, as one launch (added within ABI 10): everything of MultiBAN.forward / MultiCircBAN.forward behind the correlations for
+ * the heads of the lock-step trackers - the six `head` Sequentials (hdn/models/head/ban.py:60-66), loc_scale, the softmax of the level weights and the
+ * two weighted sums (ban.py:113-127, ban_lp.py:77-92).
+ * feats [2 n_levels][B][hidden][pixels] fp32, dense: group g = branch * n_levels + level, cls groups first, each group a contiguous [B, hidden, Ho, Wo] -
+ * exactly what hdn_xcorr_depthwise_multi_f32 writes through `outs`.  w1_packed, b1, wf, bf: exactly what hdn_head_tail_f32 takes with
+ * n_out = om = max(n_out_cls, n_out_loc): wf [2, om, n_levels * hidden], bf [2, om], the stream of hdn_pack_head_tail_f32.
+ * out: ONE buffer of B (n_out_cls + n_out_loc) pixels floats, the cls block [B][n_out_cls][pixels] first, the loc block [B][n_out_loc][pixels] behind it:
+ * row o of branch br, image b is at (br B n_out_cls + b n_out[br] + o) pixels, n_out[0] = n_out_cls, n_out[1] = n_out_loc; rows o >= n_out[br] are not
+ * written.  Both results are contiguous [B, n_out_cls, Ho, Wo] / [B, n_out_loc, Ho, Wo] views, as the reference's heads return them; with B = 1 and
+ * n_out_cls == n_out_loc it is hdn_head_tail_f32's [2, n_out, pixels].  A workgroup owns 32 pixels of ONE image and one branch (grid z = image; images do
+ * not share a pixel tile), and every output element is summed in the order of hdn_head_tail_f32: image b of a batch is bit-equal to that entry on the
+ * image alone (batch invariance).
+ * All arguments are checked before the first HIP call: HDN_E_NULL a null pointer; HDN_E_SHAPE n_levels, B, hidden, pixels, n_out_cls or n_out_loc <= 0;
+ * HDN_E_LIMIT n_levels > 4, an out count > 8, hidden not 128 or 256, B > 65535, 2 n_levels B hidden pixels > 2^31 - 1, staged operands beyond the 160 KB of
+ * LDS (hdn_head_tail_lds_bytes), w1_packed not 16-byte aligned; HDN_E_ALIAS out's byte range overlapping feats'.  Takes part in the range guard
+ * (hdn_set_check_range) over all images.  Asynchronous on `stream`; allocates nothing; deterministic; capturable.
+ */
+int hdn_head_tail_batch_f32(const float* feats, const void* w1_packed, const float* b1, const float* wf, const float* bf, float* out,
+                            int n_levels, int B, int hidden, int pixels, int n_out_cls, int n_out_loc, void* stream);
+/* Bytes of LDS a workgroup of hdn_head_tail_f32 / hdn_head_tail_batch_f32 stages for (n_levels, hidden, n_out = max of the two out counts); both entries
+ * return HDN_E_LIMIT above 160 KB (163,840).  Negative = HDN_E_* (the limits above).  Host only. */
+long long hdn_head_tail_lds_bytes(int n_levels, int hidden, int n_out);
+
+/*
  * conv_search of the correlation heads at B = 1: n (<= 4) same-shaped problems in one launch, each
  *   out[i] [CO, Hi - 2, Wi - 2] = relu(conv3x3 / stride 1 / no padding (x[i] [256, Hi, Wi], W[i]) + bias[i])
  * = DepthwiseXCorr.conv_search (Conv2d 3x3 no bias + BatchNorm, folded by the host, + ReLU; hdn/models/head/ban.py:55-59,75) for the levels of a
@@ -450,7 +474,7 @@ int hdn_head_conv3x3_batch_f32(const float* const* xs, const void* w_packed, con
  * addition and hdn_bias_relu_f32 / hdn_conv3x3_finish_f32 are the same in either domain (they are positively homogeneous / linear with the scaled bias).
  *
  * Range guard of the two-fp16-piece kernels (ABI 6): hdn_conv3x3_bias_relu_f32, hdn_conv3x3s2_ds_f32, hdn_conv3x3_v2_f32,
- * hdn_conv3x3_chain_f32 (activation inputs), hdn_trunk_stem_mfma_f32, hdn_head_conv3x3_f32, hdn_head_conv3x3_batch_f32, hdn_head_tail_f32, hdn_conv1x1_f32, hdn_conv3x3s2_f32 and hdn_conv3x3d_f32 are finite and fp32-accurate
+ * hdn_conv3x3_chain_f32 (activation inputs), hdn_trunk_stem_mfma_f32, hdn_head_conv3x3_f32, hdn_head_conv3x3_batch_f32, hdn_head_tail_f32, hdn_head_tail_batch_f32, hdn_conv1x1_f32, hdn_conv3x3s2_f32 and hdn_conv3x3d_f32 are finite and fp32-accurate
  * for |x| < 1.67e7 on their fp32 INPUTS by default (since ABI 9; 65,504 before).  Beyond that the first fp16 piece is inf and the result NaN,
  * where the reference's fp32 convolution stays finite up to 3.4e38.  With HDN_CHECK_RANGE=1 in the environment, or after hdn_set_check_range(1)
  * (returns the previous setting), each of those entry points first reduces max |x| over its input and returns HDN_E_LIMIT when it is
