@@ -43,32 +43,13 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-
-def fold_conv_bn(conv: nn.Conv2d, bn: nn.BatchNorm2d):
-    """(weight, bias) of the convolution that equals eval-mode bn(conv(x)): w' = w * gamma / sqrt(var + eps), b' = beta - mean * (that
-    factor) (+ the convolution's own bias through it), computed in float64 and rounded once."""
-    if not isinstance(conv, nn.Conv2d) or not isinstance(bn, nn.BatchNorm2d) or conv.groups != 1:
-        raise ValueError("fold_conv_bn takes a dense Conv2d and the BatchNorm2d behind it")
-    if bn.running_var is None or bn.running_mean is None:
-        raise ValueError("fold_conv_bn needs running statistics (track_running_stats)")
-    var, mean = bn.running_var.double(), bn.running_mean.double()
-    gamma = bn.weight.double() if bn.weight is not None else torch.ones_like(var)
-    beta = bn.bias.double() if bn.bias is not None else torch.zeros_like(var)
-    s = gamma / torch.sqrt(var + bn.eps)
-    w = (conv.weight.double() * s.view(-1, 1, 1, 1)).to(conv.weight.dtype)
-    b0 = conv.bias.double() if conv.bias is not None else torch.zeros_like(var)
-    b = (beta + (b0 - mean) * s).to(conv.weight.dtype)
-    if conv.weight.is_contiguous(memory_format=torch.channels_last) and not conv.weight.is_contiguous():
-        w = w.contiguous(memory_format=torch.channels_last)
-    return w.detach(), b.detach()
+from .ops import SIMI_STEM_MAX_SIDE, bias_relu_, conv1x1, conv3x3d, conv3x3v, fold_conv_bn, pack_conv1x1, pack_conv3x3d, pack_simi_stem, simi_stem
 
 
 def _epilogue(y, bias, residual=None):
     """y = relu(y + bias[c] (+ residual)) in place: one HIP pass (hdn_bias_relu_f32) for device tensors; CPU tensors (the CPU tests
     of the folding against the reference's modules) take the same arithmetic in torch ops."""
     if y.is_cuda:
-        from .trunk import bias_relu_
-
         return bias_relu_(y, bias, residual)
     y.add_(bias.view(1, -1, 1, 1))
     if residual is not None:
@@ -157,13 +138,17 @@ class FusedAtrousResNet(nn.Module):
                 raise ValueError(f"{name}: expected a Sequential of blocks")
         self.used_layers = list(net.used_layers)
 
-    def forward(self, x):
+    def stem(self, x):
+        """(the stem's own output: level 0 of `used_layers`, or None where it is never written out; layer1's input)"""
         x_ = self.c1.act(x)
-        p1 = self.layers[0](self.maxpool(x_))
-        p2 = self.layers[1](p1)
-        p3 = self.layers[2](p2)
-        p4 = self.layers[3](p3)
-        out = [x_, p1, p2, p3, p4]
+        return x_, self.maxpool(x_)
+
+    def forward(self, x):
+        x_, p = self.stem(x)
+        out = [x_]
+        for layer in self.layers:
+            p = layer(p)
+            out.append(p)
         out = [out[i] for i in self.used_layers]
         return out[0] if len(out) == 1 else out
 
@@ -248,8 +233,6 @@ class _HipConv(nn.Module):
 
     def __init__(self, conv, bn, level=1):
         super().__init__()
-        from . import trunk as T
-
         w, b = fold_conv_bn(conv, bn)
         self.kind = hip_conv_kind(conv, level)
         self.stride, self.padding, self.dilation = conv.stride, conv.padding, conv.dilation
@@ -259,22 +242,20 @@ class _HipConv(nn.Module):
             self.register_buffer("packed", None, persistent=False)
         else:
             self.register_buffer("weight", None)
-            self.register_buffer("packed", (T.pack_conv1x1 if self.kind == "conv1x1" else T.pack_conv3x3d)(w).to(w.device), persistent=False)
+            self.register_buffer("packed", (pack_conv1x1 if self.kind == "conv1x1" else pack_conv3x3d)(w).to(w.device), persistent=False)
 
     def run(self, x, bias=None, residual=None, relu=True):
-        from . import trunk as T
-
         if self.kind == "conv1x1":
-            return T.conv1x1(x, self.packed, self.bias if bias is None else bias, residual, stride=self.stride[0], relu=relu)
+            return conv1x1(x, self.packed, self.bias if bias is None else bias, residual, stride=self.stride[0], relu=relu)
         if self.kind == "conv3x3d" and residual is None:
-            return T.conv3x3d(x, self.packed, bias, dilation=self.dilation[0], relu=relu)
+            return conv3x3d(x, self.packed, bias, dilation=self.dilation[0], relu=relu)
         if self.kind == "conv3x3v" and residual is None:
-            return T.conv3x3v(x, self.packed, bias, stride=self.stride[0], relu=relu)
+            return conv3x3v(x, self.packed, bias, stride=self.stride[0], relu=relu)
         if self.kind != "miopen":
             raise ValueError("hdn_conv3x3d_f32 / hdn_conv3x3v_f32 take no residual")
         y = F.conv2d(x, self.weight, None, self.stride, self.padding, self.dilation).contiguous(memory_format=torch.channels_last)
         if relu:
-            return T.bias_relu_(y, bias, residual)
+            return bias_relu_(y, bias, residual)
         if residual is not None:
             raise ValueError("a residual without the ReLU has no fused pass")
         return y if bias is None else y.add_(bias.view(1, -1, 1, 1))
@@ -328,15 +309,9 @@ class HipAtrousResNet(FusedAtrousResNet):
 
     block = HipBottleneck
 
-    def forward(self, x):
-        x_ = self.c1.act(x)
-        p1 = self.layers[0](self.maxpool(x_).contiguous(memory_format=torch.channels_last))
-        p2 = self.layers[1](p1)
-        p3 = self.layers[2](p2)
-        p4 = self.layers[3](p3)
-        out = [x_, p1, p2, p3, p4]
-        out = [out[i] for i in self.used_layers]
-        return out[0] if len(out) == 1 else out
+    def stem(self, x):
+        x_, p = super().stem(x)
+        return x_, p.contiguous(memory_format=torch.channels_last)
 
 
 def _bottleneck_level2(blk):
@@ -347,29 +322,19 @@ class HipAtrousResNetFull(HipAtrousResNet):
     """Level 2 of the HIP form: HipBottleneck blocks at level 2 (no "miopen" convolution left in the reference's layout) and, where simi_stem_ok(net),
     conv1 + shift + ReLU + maxpool as one hdn_simi_stem_f32 launch on the NCHW input, channels-last out: the packed stream is a non-persistent buffer
     (`stem_packed`; state_dict keys unchanged, a reload re-packs into the same storage), the folded shift is c1.bias.  A network the fused stem does not
-    serve — and an input that is not square with a side of 7 .. trunk.SIMI_STEM_MAX_SIDE — runs the level-1 stem."""
+    serve — and an input that is not square with a side of 7 .. ops.SIMI_STEM_MAX_SIDE — runs the level-1 stem."""
 
     block = staticmethod(_bottleneck_level2)
 
     def __init__(self, net):
         super().__init__(net)
-        from . import trunk as T
-
         self.fused_stem = simi_stem_ok(net)
-        self.register_buffer("stem_packed", T.pack_simi_stem(self.c1.weight).to(self.c1.weight.device) if self.fused_stem else None, persistent=False)
+        self.register_buffer("stem_packed", pack_simi_stem(self.c1.weight).to(self.c1.weight.device) if self.fused_stem else None, persistent=False)
 
-    def forward(self, x):
-        from . import trunk as T
-
-        if not (self.fused_stem and x.dim() == 4 and x.shape[2] == x.shape[3] and 7 <= x.shape[2] <= T.SIMI_STEM_MAX_SIDE):
-            return super().forward(x)
-        p1 = self.layers[0](T.simi_stem(x.contiguous(), self.stem_packed, self.c1.bias))
-        p2 = self.layers[1](p1)
-        p3 = self.layers[2](p2)
-        p4 = self.layers[3](p3)
-        out = [None, p1, p2, p3, p4]
-        out = [out[i] for i in self.used_layers]
-        return out[0] if len(out) == 1 else out
+    def stem(self, x):
+        if not (self.fused_stem and x.dim() == 4 and x.shape[2] == x.shape[3] and 7 <= x.shape[2] <= SIMI_STEM_MAX_SIDE):
+            return super().stem(x)
+        return None, simi_stem(x.contiguous(), self.stem_packed, self.c1.bias)       # (simi_stem_ok: 0 is not in used_layers)
 
 
 _BACKBONE_FORMS = (FusedAtrousResNet, HipAtrousResNet, HipAtrousResNetFull)       # by level

@@ -215,109 +215,85 @@ static int launch(const float* x, const void* wp, const float* bias, float* out,
   return launch_status();
 }
 
-// HDN_OK, or what the entry point answers for a shape it does not take
-static int check_shape(int B, int S, int CI, int CO, int d) {
-  if (B <= 0 || S <= 0 || CI <= 0 || CO <= 0 || CI % 32 || CO % 32 || (d != 1 && d != 2 && d != 4)) return HDN_E_SHAPE;
-  const long long m = (long long)B * S * S;
-  if (m * CI > INT_MAX || m * CO > INT_MAX || 9LL * CI * CO > INT_MAX) return HDN_E_LIMIT;
+// HDN_OK, or what the entry points answer for a shape they do not take.  step: the dilation (1 / 2 / 4: stride 1, padding = dilation) or, VALID, the stride
+// (1 / 2: padding 0, S >= 3).  *M = output pixels, *nx = input elements, *So = the output side
+static int check_shape(bool valid, int B, int S, int CI, int CO, int step, long long* M, long long* nx, int* So) {
+  if (B <= 0 || S < (valid ? 3 : 1) || CI <= 0 || CO <= 0 || CI % 32 || CO % 32) return HDN_E_SHAPE;
+  if (step != 1 && step != 2 && (valid || step != 4)) return HDN_E_SHAPE;
+  *So = valid ? (S - 3) / step + 1 : S;
+  *M = (long long)B * *So * *So;
+  *nx = (long long)B * S * S * CI;
+  if (*nx > INT_MAX || *M * CO > INT_MAX || 9LL * CI * CO > INT_MAX) return HDN_E_LIMIT;
   return HDN_OK;
 }
 
-// the same for the padding-0 form; *So = the output side
-static int check_shape_valid(int B, int S, int CI, int CO, int stride, int* So) {
-  if (B <= 0 || S < 3 || CI <= 0 || CO <= 0 || CI % 32 || CO % 32 || (stride != 1 && stride != 2)) return HDN_E_SHAPE;
-  *So = (S - 3) / stride + 1;
-  if ((long long)B * S * S * CI > INT_MAX || (long long)B * *So * *So * CO > INT_MAX || 9LL * CI * CO > INT_MAX) return HDN_E_LIMIT;
-  return HDN_OK;
+static int form(bool valid, int B, int S, int CI, int CO, int step) {
+  long long M, nx;
+  int So;
+  if (const int rc = check_shape(valid, B, S, CI, CO, step, &M, &nx, &So)) return rc;
+  return (int)dispatch(M, CI, CO, [&](auto cfg, int sps) -> long long {
+    using C = decltype(cfg);
+    return C::MT | C::NT << 4 | C::WM << 8 | C::WN << 12 | cdiv(9 * (CI / 32), sps) << 16;
+  });
+}
+
+static long long workspace(bool valid, int B, int S, int CI, int CO, int step) {
+  long long M, nx;
+  int So;
+  if (const int rc = check_shape(valid, B, S, CI, CO, step, &M, &nx, &So)) return rc;
+  return dispatch(M, CI, CO, [&](auto, int sps) -> long long {
+    const int Z = cdiv(9 * (CI / 32), sps);
+    return Z > 1 ? Z * M * CO * 4 : 0;
+  });
+}
+
+template <bool VALID>
+static int run(const float* x, const void* wpacked, const float* bias, float* out, void* ws, long long ws_bytes, int B, int S, int CI, int CO, int step,
+               int relu, int act_domain, void* stream) {
+  if (!x || !wpacked || !out) return HDN_E_NULL;
+  if ((relu != 0 && relu != 1) || (act_domain != 0 && act_domain != 1)) return HDN_E_SHAPE;
+  long long M, nx;
+  int So;
+  if (const int rc = check_shape(VALID, B, S, CI, CO, step, &M, &nx, &So)) return rc;
+  const long long nout = M * CO;
+  if (bytes_overlap(out, nout * 4, x, nx * 4)) return HDN_E_ALIAS;
+  if (!aligned16(x) || !aligned16(wpacked) || !aligned16(out) || (bias && !aligned16(bias))) return HDN_E_LIMIT;
+  const long long need = workspace(VALID, B, S, CI, CO, step);
+  if (need > 0) {
+    if (!ws) return HDN_E_NULL;
+    if (!aligned16(ws) || ws_bytes < need) return HDN_E_LIMIT;
+    if (bytes_overlap(ws, need, x, nx * 4) || bytes_overlap(ws, need, out, nout * 4)) return HDN_E_ALIAS;
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (const int rr = check_fp16_range(x, nx, s, act_domain)) return rr;
+  return (int)dispatch(M, CI, CO, [&](auto cfg, int sps) -> long long {
+    using C = decltype(cfg);
+    return act_domain ? launch<C, true, VALID>(x, wpacked, bias, out, static_cast<float*>(ws), (int)M, S, So, step, CI, CO, relu, sps, s)
+                      : launch<C, false, VALID>(x, wpacked, bias, out, static_cast<float*>(ws), (int)M, S, So, step, CI, CO, relu, sps, s);
+  });
 }
 
 }  // namespace c3d
 }  // namespace hdn
 
 // the launch form dispatch() picks for a problem, for tests and profiles: MT | NT << 4 | WM << 8 | WN << 12 | (K slices Z) << 16.  Host only.
-extern "C" int hdn_conv3x3d_form(int B, int S, int CI, int CO, int dilation) {
-  if (const int rc = hdn::c3d::check_shape(B, S, CI, CO, dilation)) return rc;
-  return (int)hdn::c3d::dispatch((long long)B * S * S, CI, CO, [&](auto cfg, int sps) -> long long {
-    using C = decltype(cfg);
-    return C::MT | C::NT << 4 | C::WM << 8 | C::WN << 12 | hdn::cdiv(9 * (CI / 32), sps) << 16;
-  });
-}
+extern "C" int hdn_conv3x3d_form(int B, int S, int CI, int CO, int dilation) { return hdn::c3d::form(false, B, S, CI, CO, dilation); }
 
-extern "C" long long hdn_conv3x3d_workspace_bytes(int B, int S, int CI, int CO, int dilation) {
-  if (const int rc = hdn::c3d::check_shape(B, S, CI, CO, dilation)) return rc;
-  const long long M = (long long)B * S * S;
-  return hdn::c3d::dispatch(M, CI, CO, [&](auto, int sps) -> long long {
-    const int Z = hdn::cdiv(9 * (CI / 32), sps);
-    return Z > 1 ? Z * M * CO * 4 : 0;
-  });
-}
+extern "C" long long hdn_conv3x3d_workspace_bytes(int B, int S, int CI, int CO, int dilation) { return hdn::c3d::workspace(false, B, S, CI, CO, dilation); }
 
 // wpacked (hdn_pack_conv3x3d_f32): [CO / 32 n tiles][9 taps][CI / 32 chunks][2 k steps t][2 pieces][k half g][32 n][8] fp16; element e of lane (g, n) =
 // piece of w[co = 32 tile + n][ci = 32 chunk + 16 g + 8 t + e][tap = 3 ky + kx]
 extern "C" int hdn_conv3x3d_f32(const float* x, const void* wpacked, const float* bias, float* out, void* ws, long long ws_bytes, int B, int S, int CI,
                                 int CO, int dilation, int relu, int act_domain, void* stream) {
-  if (!x || !wpacked || !out) return HDN_E_NULL;
-  if ((relu != 0 && relu != 1) || (act_domain != 0 && act_domain != 1)) return HDN_E_SHAPE;
-  if (const int rc = hdn::c3d::check_shape(B, S, CI, CO, dilation)) return rc;
-  const long long M = (long long)B * S * S, nx = M * CI, nout = M * CO;
-  if (hdn::bytes_overlap(out, nout * 4, x, nx * 4)) return HDN_E_ALIAS;
-  if (!hdn::aligned16(x) || !hdn::aligned16(wpacked) || !hdn::aligned16(out) || (bias && !hdn::aligned16(bias))) return HDN_E_LIMIT;
-  const long long need = hdn_conv3x3d_workspace_bytes(B, S, CI, CO, dilation);
-  if (need > 0) {
-    if (!ws) return HDN_E_NULL;
-    if (!hdn::aligned16(ws) || ws_bytes < need) return HDN_E_LIMIT;
-    if (hdn::bytes_overlap(ws, need, x, nx * 4) || hdn::bytes_overlap(ws, need, out, nout * 4)) return HDN_E_ALIAS;
-  }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (const int rr = hdn::check_fp16_range(x, nx, s, act_domain)) return rr;
-  return (int)hdn::c3d::dispatch(M, CI, CO, [&](auto cfg, int sps) -> long long {
-    using C = decltype(cfg);
-    return act_domain ? hdn::c3d::launch<C, true>(x, wpacked, bias, out, static_cast<float*>(ws), (int)M, S, S, dilation, CI, CO, relu, sps, s)
-                      : hdn::c3d::launch<C, false>(x, wpacked, bias, out, static_cast<float*>(ws), (int)M, S, S, dilation, CI, CO, relu, sps, s);
-  });
+  return hdn::c3d::run<false>(x, wpacked, bias, out, ws, ws_bytes, B, S, CI, CO, dilation, relu, act_domain, stream);
 }
 
-// ---------------------------------------------------------------------------------------------------- padding 0, stride 1 / 2 (hdn_conv3x3v_f32)
-extern "C" int hdn_conv3x3v_form(int B, int S, int CI, int CO, int stride) {
-  int So = 0;
-  if (const int rc = hdn::c3d::check_shape_valid(B, S, CI, CO, stride, &So)) return rc;
-  return (int)hdn::c3d::dispatch((long long)B * So * So, CI, CO, [&](auto cfg, int sps) -> long long {
-    using C = decltype(cfg);
-    return C::MT | C::NT << 4 | C::WM << 8 | C::WN << 12 | hdn::cdiv(9 * (CI / 32), sps) << 16;
-  });
-}
+// ------------------------------------------------------------------------------- padding 0, stride 1 / 2 (hdn_conv3x3v_f32), on the same stream
+extern "C" int hdn_conv3x3v_form(int B, int S, int CI, int CO, int stride) { return hdn::c3d::form(true, B, S, CI, CO, stride); }
 
-extern "C" long long hdn_conv3x3v_workspace_bytes(int B, int S, int CI, int CO, int stride) {
-  int So = 0;
-  if (const int rc = hdn::c3d::check_shape_valid(B, S, CI, CO, stride, &So)) return rc;
-  const long long M = (long long)B * So * So;
-  return hdn::c3d::dispatch(M, CI, CO, [&](auto, int sps) -> long long {
-    const int Z = hdn::cdiv(9 * (CI / 32), sps);
-    return Z > 1 ? Z * M * CO * 4 : 0;
-  });
-}
+extern "C" long long hdn_conv3x3v_workspace_bytes(int B, int S, int CI, int CO, int stride) { return hdn::c3d::workspace(true, B, S, CI, CO, stride); }
 
-// wpacked: hdn_pack_conv3x3d_f32's stream (layout above)
 extern "C" int hdn_conv3x3v_f32(const float* x, const void* wpacked, const float* bias, float* out, void* ws, long long ws_bytes, int B, int S, int CI,
                                 int CO, int stride, int relu, int act_domain, void* stream) {
-  if (!x || !wpacked || !out) return HDN_E_NULL;
-  if ((relu != 0 && relu != 1) || (act_domain != 0 && act_domain != 1)) return HDN_E_SHAPE;
-  int So = 0;
-  if (const int rc = hdn::c3d::check_shape_valid(B, S, CI, CO, stride, &So)) return rc;
-  const long long M = (long long)B * So * So, nx = (long long)B * S * S * CI, nout = M * CO;
-  if (hdn::bytes_overlap(out, nout * 4, x, nx * 4)) return HDN_E_ALIAS;
-  if (!hdn::aligned16(x) || !hdn::aligned16(wpacked) || !hdn::aligned16(out) || (bias && !hdn::aligned16(bias))) return HDN_E_LIMIT;
-  const long long need = hdn_conv3x3v_workspace_bytes(B, S, CI, CO, stride);
-  if (need > 0) {
-    if (!ws) return HDN_E_NULL;
-    if (!hdn::aligned16(ws) || ws_bytes < need) return HDN_E_LIMIT;
-    if (hdn::bytes_overlap(ws, need, x, nx * 4) || hdn::bytes_overlap(ws, need, out, nout * 4)) return HDN_E_ALIAS;
-  }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (const int rr = hdn::check_fp16_range(x, nx, s, act_domain)) return rr;
-  return (int)hdn::c3d::dispatch(M, CI, CO, [&](auto cfg, int sps) -> long long {
-    using C = decltype(cfg);
-    return act_domain ? hdn::c3d::launch<C, true, true>(x, wpacked, bias, out, static_cast<float*>(ws), (int)M, S, So, stride, CI, CO, relu, sps, s)
-                      : hdn::c3d::launch<C, false, true>(x, wpacked, bias, out, static_cast<float*>(ws), (int)M, S, So, stride, CI, CO, relu, sps, s);
-  });
+  return hdn::c3d::run<true>(x, wpacked, bias, out, ws, ws_bytes, B, S, CI, CO, stride, relu, act_domain, stream);
 }

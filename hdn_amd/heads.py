@@ -26,6 +26,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .ops import _c_pack, _host_f32, bias_relu_
 from .xcorr import out_shape, xcorr_depthwise, xcorr_depthwise_circular, xcorr_depthwise_multi
 
 
@@ -249,7 +250,6 @@ def _fold_bn(conv, bn):
 def _pack_w1(w1):
     """[G, H, H] fp32 (row = output channel) -> the stream hdn_head_tail_f32 takes (hdn_pack_head_tail_f32, csrc/pack.hip), on w1's device."""
     from . import _lib
-    from .trunk import _c_pack, _host_f32
 
     G, H, _ = w1.shape
     lib, w = _lib.load(), _host_f32(w1)
@@ -261,7 +261,6 @@ def _pack_conv_search(ws):
     import ctypes
 
     from . import _lib
-    from .trunk import _c_pack, _host_f32
 
     host = [_host_f32(t) for t in ws]
     n, CO = len(host), host[0].shape[0]
@@ -525,7 +524,6 @@ def _batched_forward(self, boxes, kern, x_fs, sp, circular):
 
 
 def _packed_forward(self, boxes, kern, x_fs, circular):
-    from .trunk import bias_relu_
     n = len(boxes)
     pk = getattr(self, "_hdn_packed_head", None)
     key = _head_key(self, boxes)

@@ -10,7 +10,16 @@ from __future__ import annotations
 
 import os
 
+import torch
 import torch.nn as nn
+import torch.nn.functional as F
+
+from . import _lib
+# the launch wrappers and packers live in hdn_amd.ops; every name is kept importable from here
+from .ops import (ACT_SCALE_LOG2, MATRIX_CORE_CHANNELS, S2_CHANNELS, SIMI_STEM_MAX_SIDE, SPLIT_PIECES, V2_MIN_BATCH, _MC_SIDE,  # noqa: F401
+                  LazyAct, _c_pack, _host_f32, _launch, bias_relu_, chain_conv, conv1x1, conv3x3_bias_relu, conv3x3d, conv3x3s2, conv3x3s2_ds, conv3x3v,
+                  fold_conv_bn, pack_conv1x1, pack_conv3x3, pack_conv3x3_v2, pack_conv3x3d, pack_conv3x3s2, pack_conv3x3s2_ds, pack_conv3x3s2_ds_v2,
+                  pack_simi_stem, pack_stem_mfma, simi_stem)
 
 
 class BasicBlock(nn.Module):
@@ -102,12 +111,6 @@ class HomoResNet(nn.Module):
         return x.mul_(float(1 << ACT_SCALE_LOG2)) if self.act_domain else x      # (a fresh tensor of this forward: in place is safe; exact)
 
 
-# The matrix-core kernels split an activation as x * 2^-8 (csrc/mfma_split.h: finite and fp32-accurate to |x| < 1.67e7).  A fully fused trunk pays that
-# multiply ONCE: its first stage writes relu(conv) * 2^-8, every block runs with act_domain = 1 (activations already scaled in memory, biases handed over
-# scaled: exact), and the exit multiplies by 2^8 (hdn_avgpool_fc_f32's in_domain, or HomoResNet.forward).
-ACT_SCALE_LOG2 = 8
-
-
 _scale_checked = False
 
 
@@ -117,8 +120,6 @@ def check_act_scale():
     global _scale_checked
     if _scale_checked:
         return
-    from . import _lib
-
     got = int(_lib.load().hdn_act_scale_log2())
     if got != ACT_SCALE_LOG2:
         raise RuntimeError(f"libhdn_hip.so was built with HDN_ACT_SCALE_LOG2 = {got}, hdn_amd.trunk scales activations by 2^-{ACT_SCALE_LOG2}: "
@@ -141,39 +142,6 @@ def resnet50_homo(layers=(3, 4, 6, 3)):
 STEM_MFMA_MIN_BATCH = int(os.environ.get("HDN_STEM_MFMA_MIN_BATCH", "1"))
 
 
-def _c_pack(what, n_bytes, call):
-    """Run one of the library's packers (csrc/pack.hip, host code): -> int16 CPU tensor holding the opaque stream."""
-    import torch
-
-    from . import _lib
-
-    if n_bytes < 0:
-        raise ValueError(f"{what}: no matrix-core kernel takes weights of this shape")
-    out = torch.empty(n_bytes // 2, dtype=torch.int16)
-    rc = call(out.data_ptr(), n_bytes)
-    if rc == -3:                                   # HDN_E_LIMIT
-        raise ValueError(f"{what}: weights beyond the fp16 range (|w| >= 65,504) or NaN")
-    _lib.check(rc, what)
-    return out
-
-
-def _host_f32(t):
-    import torch
-
-    return t.detach().to(device="cpu", dtype=torch.float32).contiguous()
-
-
-def pack_stem_mfma(weight):
-    """[64, 2, 7, 7] fp32 weights (BatchNorm folded in) -> the stream hdn_trunk_stem_mfma_f32 takes (hdn_pack_stem_mfma_f32; the layout is
-    the library's: csrc/pack.hip)."""
-    from . import _lib
-
-    if tuple(weight.shape) != (64, 2, 7, 7):
-        raise ValueError(f"pack_stem_mfma takes [64, 2, 7, 7] weights, got {tuple(weight.shape)}")
-    lib, w = _lib.load(), _host_f32(weight)
-    return _c_pack("pack_stem_mfma", lib.hdn_pack_stem_mfma_bytes(), lambda o, n: lib.hdn_pack_stem_mfma_f32(w.data_ptr(), o, n))
-
-
 class FusedStem(nn.Module):
     """conv1 + folded bn1 + relu + maxpool of the trunk as ONE HIP kernel (hdn_trunk_stem_f32): the 64-channel 64 x 64 conv output
     never goes through HBM.  Built from a folded conv (weight [64,2,7,7], bias [64]); eval / no-grad only; CUDA tensors only."""
@@ -190,14 +158,10 @@ class FusedStem(nn.Module):
         self.mfma_disabled = False                                                           # A/B switch (tools/experiments, tests)
 
     def forward(self, x):
-        from . import _lib
-
         if x.dim() != 4 or x.shape[1] != 2 or x.dtype != self.wT.dtype:
             raise ValueError("FusedStem takes float32 [B,2,H,W]")
         B, _, H, W = x.shape
         if W < 2 or W > 128:  # outside the kernel's range: the same arithmetic through the library
-            import torch.nn.functional as F
-
             y = F.conv2d(x, self.wT.permute(3, 0, 1, 2), self.b, stride=2, padding=3)
             y = F.max_pool2d(F.relu(y), 3, 2, 1)
             return y.mul_(2.0 ** -ACT_SCALE_LOG2) if self.out_domain else y
@@ -207,269 +171,20 @@ class FusedStem(nn.Module):
         xs = x.detach().contiguous()  # NCHW
         Hc, Wc = (H - 1) // 2 + 1, (W - 1) // 2 + 1
         Hp, Wp = (Hc - 1) // 2 + 1, (Wc - 1) // 2 + 1
-        import torch
-
         out = torch.empty((B, 64, Hp, Wp), dtype=x.dtype, device=dev,
                           memory_format=torch.channels_last if self.channels_last else torch.contiguous_format)
         if self.channels_last and H == 127 and W == 127 and B >= STEM_MFMA_MIN_BATCH and not self.mfma_disabled:
-            with _lib.device_guard(dev):
-                rc = _lib.load().hdn_trunk_stem_mfma_f32(_lib.ptr(xs), _lib.ptr(self.wfrag), _lib.ptr(self.b), _lib.ptr(out), B, H, W, self.out_domain,
-                                                         _lib.stream_ptr(dev))
-            _lib.check(rc, "trunk_stem_mfma")
+            _launch("trunk_stem_mfma", dev, _lib.load().hdn_trunk_stem_mfma_f32, _lib.ptr(xs), _lib.ptr(self.wfrag), _lib.ptr(self.b), _lib.ptr(out),
+                    B, H, W, self.out_domain)
             return out
-        with _lib.device_guard(dev):
-            rc = _lib.load().hdn_trunk_stem_f32(_lib.ptr(xs), _lib.ptr(self.wT), _lib.ptr(self.b), _lib.ptr(out), B, H, W,
-                                                1 if self.channels_last else 0, _lib.stream_ptr(dev))
-        _lib.check(rc, "trunk_stem")
+        _launch("trunk_stem", dev, _lib.load().hdn_trunk_stem_f32, _lib.ptr(xs), _lib.ptr(self.wT), _lib.ptr(self.b), _lib.ptr(out), B, H, W,
+                1 if self.channels_last else 0)
         return out.mul_(2.0 ** -ACT_SCALE_LOG2) if self.out_domain else out
-
-
-def bias_relu_(y, bias, residual=None):
-    """In place: y = relu(y + bias[c] (+ residual)) through hdn_bias_relu_f32; y / residual [B,C,H,W] float32, both NCHW-contiguous
-    or both channels-last."""
-    import torch
-
-    from . import _lib
-
-    dev = _lib.require_device(y, bias) if residual is None else _lib.require_device(y, bias, residual)
-    if y.dim() != 4 or bias.numel() != y.shape[1] or (residual is not None and residual.shape != y.shape):
-        raise ValueError(f"bias_relu_: y [B,C,H,W], bias [C], residual like y; got {tuple(y.shape)}, {tuple(bias.shape)}")
-    B, C, H, W = y.shape
-    if y.is_contiguous():   # (a [B,C,1,1] tensor is both: NCHW arithmetic is right for it)
-        nhwc = 0
-    elif y.is_contiguous(memory_format=torch.channels_last):
-        nhwc = 1
-    else:
-        raise ValueError("bias_relu_: y must be NCHW-contiguous or channels-last")
-    if residual is not None and not (residual.is_contiguous(memory_format=torch.channels_last) if nhwc else residual.is_contiguous()):
-        residual = residual.contiguous(memory_format=torch.channels_last if nhwc else torch.contiguous_format)
-    with _lib.device_guard(dev):
-        rc = _lib.load().hdn_bias_relu_f32(_lib.ptr(y), _lib.ptr(bias), _lib.ptr(residual) if residual is not None else None, B, C, H * W,
-                                           nhwc, _lib.stream_ptr(dev))
-    _lib.check(rc, "bias_relu")
-    return y
-
-
-SPLIT_PIECES = 2
-
-
-def pack_conv3x3(weight):
-    """[C, C, 3, 3] fp32 weights of a stride-1 convolution -> the stream hdn_conv3x3_bias_relu_f32 / hdn_conv3x3_chain_f32 take
-    (hdn_pack_conv3x3_f32).  The side S is implied by C in the trunk (64 -> 32, 128 -> 16, 256 -> 8, 512 -> 4)."""
-    from . import _lib
-
-    C = weight.shape[0]
-    if tuple(weight.shape) != (C, C, 3, 3):
-        raise ValueError(f"pack_conv3x3 takes [C, C, 3, 3] weights, got {tuple(weight.shape)}")
-    lib, w = _lib.load(), _host_f32(weight)
-    return _c_pack("pack_conv3x3", lib.hdn_pack_conv3x3_bytes(C), lambda o, n: lib.hdn_pack_conv3x3_f32(w.data_ptr(), C, o, n))
-
-
-def pack_conv3x3_v2(weight):
-    """[C, C, 3, 3] fp32 weights -> the stream of hdn_conv3x3_v2_f32 (hdn_pack_conv3x3_v2_f32)."""
-    from . import _lib
-
-    C = weight.shape[0]
-    if tuple(weight.shape) != (C, C, 3, 3):
-        raise ValueError(f"pack_conv3x3_v2 takes [C, C, 3, 3] weights, got {tuple(weight.shape)}")
-    lib, w = _lib.load(), _host_f32(weight)
-    return _c_pack("pack_conv3x3_v2", lib.hdn_pack_conv3x3_v2_bytes(C), lambda o, n: lib.hdn_pack_conv3x3_v2_f32(w.data_ptr(), C, o, n))
-
-
-V2_MIN_BATCH = 24      # below: the chained / K-sliced form of conv3x3_kernel (CHAIN_MAX_BATCH = 16 pairs and the sizes between)
-
-
-def _s2_weights(weight, ds_weight, what):
-    CO, CI = weight.shape[0], weight.shape[1]
-    if tuple(weight.shape) != (2 * CI, CI, 3, 3) or tuple(ds_weight.shape) != (2 * CI, CI, 1, 1):
-        raise ValueError(f"{what} takes [2C, C, 3, 3] and [2C, C, 1, 1] weights, got {tuple(weight.shape)}, {tuple(ds_weight.shape)}")
-    return CI, _host_f32(weight), _host_f32(ds_weight)
-
-
-def pack_conv3x3s2_ds(weight, ds_weight):
-    """[2C, C, 3, 3] weights of the stride-2 convolution + [2C, C, 1, 1] weights of the block's downsample branch -> the stream of
-    hdn_conv3x3s2_ds_f32 (hdn_pack_conv3x3s2_ds_f32)."""
-    from . import _lib
-
-    CI, w, wd = _s2_weights(weight, ds_weight, "pack_conv3x3s2_ds")
-    lib = _lib.load()
-    return _c_pack("pack_conv3x3s2_ds", lib.hdn_pack_conv3x3s2_ds_bytes(CI), lambda o, n: lib.hdn_pack_conv3x3s2_ds_f32(w.data_ptr(), wd.data_ptr(), CI, o, n))
-
-
-def pack_conv3x3s2_ds_v2(weight, ds_weight):
-    """The same two weight tensors -> the stream of hdn_conv3x3s2_v2_f32 (hdn_pack_conv3x3s2_v2_f32)."""
-    from . import _lib
-
-    CI, w, wd = _s2_weights(weight, ds_weight, "pack_conv3x3s2_ds_v2")
-    lib = _lib.load()
-    return _c_pack("pack_conv3x3s2_ds_v2", lib.hdn_pack_conv3x3s2_v2_bytes(CI), lambda o, n: lib.hdn_pack_conv3x3s2_v2_f32(w.data_ptr(), wd.data_ptr(), CI, o, n))
-
-
-def conv3x3_bias_relu(x, wpacked, bias, residual=None, wpacked_v2=None, act_domain=0):
-    """relu(conv3x3(x) + bias (+ residual)) through hdn_conv3x3_bias_relu_f32 — or, given `wpacked_v2` (pack_conv3x3_v2) and a batch of
-    V2_MIN_BATCH or more, through hdn_conv3x3_v2_f32; x / residual channels-last [B,C,S,S] float32.  act_domain = 1: x, residual and the result are
-    x_real * 2^-8 in memory and `bias` is bias * 2^-8 (include/hdn_hip.h, "Activation domain")."""
-    import torch
-
-    from . import _lib
-
-    dev = _lib.require_device(x, bias) if residual is None else _lib.require_device(x, bias, residual)
-    B, C, S, S2 = x.shape
-    cl = torch.channels_last
-    if S != S2 or not x.is_contiguous(memory_format=cl) or (residual is not None and (residual.shape != x.shape or not residual.is_contiguous(memory_format=cl))):
-        raise ValueError("conv3x3_bias_relu: square channels-last inputs of equal shape")
-    if wpacked.dtype != torch.int16 or wpacked.device != dev or wpacked.numel() != 9 * SPLIT_PIECES * C * C or bias.numel() != C:
-        raise ValueError("conv3x3_bias_relu: weights must come from pack_conv3x3 for this channel count, on the input's device")
-    out = torch.empty_like(x, memory_format=cl)
-    lib = _lib.load()
-    v2 = wpacked_v2 is not None and B >= V2_MIN_BATCH
-    if v2 and (wpacked_v2.dtype != torch.int16 or wpacked_v2.device != dev or wpacked_v2.numel() != 9 * SPLIT_PIECES * C * C):
-        raise ValueError("conv3x3_bias_relu: wpacked_v2 must come from pack_conv3x3_v2 for this channel count, on the input's device")
-    nws = lib.hdn_conv3x3_v2_workspace_bytes(B, S, C) if v2 else lib.hdn_conv3x3_workspace_bytes(B, S, C, 1)
-    if nws < 0:
-        _lib.check(int(nws), "conv3x3_bias_relu")
-    ws = torch.empty(nws // 4, dtype=torch.float32, device=dev) if nws else None   # (from torch's caching allocator: no sync, graph-safe)
-    with _lib.device_guard(dev):
-        fn = lib.hdn_conv3x3_v2_f32 if v2 else lib.hdn_conv3x3_bias_relu_f32
-        rc = fn(_lib.ptr(x), _lib.ptr(wpacked_v2 if v2 else wpacked), _lib.ptr(bias), _lib.ptr(residual) if residual is not None else None,
-                _lib.ptr(out), _lib.ptr(ws) if ws is not None else None, nws, B, S, C, int(act_domain), _lib.stream_ptr(dev))
-    _lib.check(rc, "conv3x3_bias_relu")
-    return out
-
-
-# channel counts whose stride-1 3x3 convolutions run on hdn_conv3x3_bias_relu_f32 instead of MIOpen (measured per shape at
-# B = 64, profiles/round3_conv3x3.txt: the kernel is kept only where it wins)
-MATRIX_CORE_CHANNELS = (64, 128, 256, 512)
-_MC_SIDE = {64: 32, 128: 16, 256: 8, 512: 4}
-S2_CHANNELS = (128, 256, 512)       # ... whose stride-2 C -> C convolutions (a Bottleneck's conv2) run on hdn_conv3x3s2_f32, input side 2 * _MC_SIDE[C]
-
-
-def conv3x3s2_ds(x, wpacked, bias, wpacked_v2=None, act_domain=0):
-    """(relu(conv3x3/s2(x) + bias), conv1x1/s2(x)) through hdn_conv3x3s2_ds_f32 - or, given `wpacked_v2` (pack_conv3x3s2_ds_v2) and a batch of
-    V2_MIN_BATCH or more, through hdn_conv3x3s2_v2_f32; x channels-last [B,C,2S,2S] -> two [B,2C,S,S]."""
-    import torch
-
-    from . import _lib
-
-    dev = _lib.require_device(x, bias)
-    B, CI, H, W = x.shape
-    cl = torch.channels_last
-    if H != W or H % 2 or not x.is_contiguous(memory_format=cl):
-        raise ValueError("conv3x3s2_ds: square, even-sided channels-last input")
-    S, CO = H // 2, 2 * CI
-    if wpacked_v2 is not None and B >= V2_MIN_BATCH:
-        if wpacked_v2.dtype != torch.int16 or wpacked_v2.device != dev or wpacked_v2.numel() != SPLIT_PIECES * 10 * CI * CO or bias.numel() != CO:
-            raise ValueError("conv3x3s2_ds: v2 weights must come from pack_conv3x3s2_ds_v2 for this channel count, on the input's device")
-        out = torch.empty((B, CO, S, S), dtype=torch.float32, device=dev, memory_format=cl)
-        out_ds = torch.empty_like(out, memory_format=cl)
-        with _lib.device_guard(dev):
-            rc = _lib.load().hdn_conv3x3s2_v2_f32(_lib.ptr(x), _lib.ptr(wpacked_v2), _lib.ptr(bias), _lib.ptr(out), _lib.ptr(out_ds), B, S, CI,
-                                                  int(act_domain), _lib.stream_ptr(dev))
-        _lib.check(rc, "conv3x3s2_v2")
-        return out, out_ds
-    if wpacked.dtype != torch.int16 or wpacked.device != dev or wpacked.numel() != SPLIT_PIECES * 3 * 4 * CI * CO or bias.numel() != CO:
-        raise ValueError("conv3x3s2_ds: weights must come from pack_conv3x3s2_ds for this channel count, on the input's device")
-    out = torch.empty((B, CO, S, S), dtype=torch.float32, device=dev, memory_format=cl)
-    out_ds = torch.empty_like(out, memory_format=cl)
-    lib = _lib.load()
-    nws = lib.hdn_conv3x3_workspace_bytes(B, S, CI, 2)
-    if nws < 0:
-        _lib.check(int(nws), "conv3x3s2_ds")
-    ws = torch.empty(nws // 4, dtype=torch.float32, device=dev) if nws else None
-    with _lib.device_guard(dev):
-        rc = lib.hdn_conv3x3s2_ds_f32(_lib.ptr(x), _lib.ptr(wpacked), _lib.ptr(bias), _lib.ptr(out), _lib.ptr(out_ds),
-                                      _lib.ptr(ws) if ws is not None else None, nws, B, S, CI, int(act_domain), _lib.stream_ptr(dev))
-    _lib.check(rc, "conv3x3s2_ds")
-    return out, out_ds
 
 
 # Batches up to this run the blocks CHAINED (hdn_conv3x3_chain_f32): at the tracker's B = 1 every launch is a dependent step of ~5 us
 # and the launches that only add the K slices up were half of the trunk's 70
 CHAIN_MAX_BATCH = 16
-
-
-class LazyAct:
-    """An activation of the chained trunk that was never written out: relu(sum of `slices` [z,B,S,S,C] + bias[c] (+ res)), finished by
-    the convolution that reads it (or by finish()).  res: None, a channels-last activation [B,C,S,S], or raw slices [zr,B,S,S,C]
-    (the downsample branch)."""
-
-    __slots__ = ("slices", "bias", "res")
-
-    def __init__(self, slices, bias, res=None):
-        if slices.dim() != 5 or slices.shape[2] != slices.shape[3] or not slices.is_contiguous() or bias.numel() != slices.shape[4]:
-            raise ValueError(f"LazyAct: slices [z,B,S,S,C] contiguous with a bias of C elements, got {tuple(slices.shape)}, {tuple(bias.shape)}")
-        self.slices, self.bias, self.res = slices, bias, res
-
-    @property
-    def shape(self):
-        z, B, S, _, C = self.slices.shape
-        return (B, C, S, S)
-
-    def res_args(self):
-        """(pointer, slice count) of the residual for the C ABI: a channels-last activation counts as one slice."""
-        import torch
-
-        from . import _lib
-
-        r = self.res
-        if r is None:
-            return None, 0
-        z, B, S, _, C = self.slices.shape
-        if r.dim() == 5:
-            ok = tuple(r.shape[1:]) == (B, S, S, C) and r.is_contiguous()
-        else:
-            ok = tuple(r.shape) == (B, C, S, S) and r.is_contiguous(memory_format=torch.channels_last)
-        if not ok or r.dtype != torch.float32 or r.device != self.slices.device:
-            raise ValueError(f"LazyAct residual must be a channels-last [B,C,S,S] activation or [z,B,S,S,C] slices matching {tuple(self.slices.shape)}")
-        return _lib.ptr(r), (r.shape[0] if r.dim() == 5 else 1)
-
-    def finish(self):
-        """The activation itself, channels-last [B,C,S,S] (hdn_conv3x3_finish_f32)."""
-        import torch
-
-        from . import _lib
-
-        z, B, S, _, C = self.slices.shape
-        dev = self.slices.device
-        out = torch.empty((B, C, S, S), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
-        rp, rz = self.res_args()
-        with _lib.device_guard(dev):
-            rc = _lib.load().hdn_conv3x3_finish_f32(_lib.ptr(self.slices), z, _lib.ptr(self.bias), rp, rz, _lib.ptr(out), B, S, C, _lib.stream_ptr(dev))
-        _lib.check(rc, "conv3x3_finish")
-        return out
-
-
-def chain_conv(x, wpacked, stride=1, want_x=False, act_domain=0):
-    """One convolution of the chained trunk (hdn_conv3x3_chain_f32): x a channels-last activation [B,CI,SI,SI] or a LazyAct; returns
-    (slices [z,B,S,S,CO], downsample slices or None (stride 2), the finished input as an activation or None (want_x, LazyAct input))."""
-    import torch
-
-    from . import _lib
-
-    lazy = isinstance(x, LazyAct)
-    B, CI, SI, SI2 = x.shape
-    src = x.slices if lazy else x
-    dev = _lib.require_device(src)
-    if SI != SI2 or SI % stride or (not lazy and not x.is_contiguous(memory_format=torch.channels_last)):
-        raise ValueError("chain_conv: square channels-last input")
-    S, CO = SI // stride, CI * stride
-    T = 4 if stride == 2 else 3
-    if wpacked.dtype != torch.int16 or wpacked.device != dev or wpacked.numel() != SPLIT_PIECES * 3 * T * CI * CO:
-        raise ValueError("chain_conv: weights must come from pack_conv3x3 / pack_conv3x3s2_ds for this channel count")
-    lib = _lib.load()
-    z = lib.hdn_conv3x3_chain_slices(B, S, CI, stride)
-    if z < 0:
-        _lib.check(int(z), "conv3x3_chain")
-    out = torch.empty((z, B, S, S, CO), dtype=torch.float32, device=dev)
-    out_ds = torch.empty_like(out) if stride == 2 else None
-    x_out = torch.empty((B, CI, SI, SI), dtype=torch.float32, device=dev, memory_format=torch.channels_last) if (lazy and want_x) else None
-    rp, rz = x.res_args() if lazy else (None, 0)
-    with _lib.device_guard(dev):
-        rc = lib.hdn_conv3x3_chain_f32(_lib.ptr(src), src.shape[0] if lazy else 0, _lib.ptr(x.bias) if lazy else None, rp, rz,
-                                       _lib.ptr(x_out) if x_out is not None else None, _lib.ptr(wpacked), _lib.ptr(out),
-                                       _lib.ptr(out_ds) if out_ds is not None else None, B, S, CI, stride, int(act_domain), _lib.stream_ptr(dev))
-    _lib.check(rc, "conv3x3_chain")
-    return out, out_ds, x_out
 
 
 class FusedBasicBlock(nn.Module):
@@ -481,8 +196,6 @@ class FusedBasicBlock(nn.Module):
 
     def __init__(self, blk: "BasicBlock", matrix_core: bool = False, act_domain: int = 0):
         super().__init__()
-        import torch
-
         self.act_domain = int(act_domain)     # 1: input, output and residuals are x * 2^-ACT_SCALE_LOG2 in memory (a fully fused trunk's interior)
 
         for c in (blk.conv1, blk.conv2) + ((blk.downsample,) if blk.downsample is not None else ()):
@@ -530,9 +243,6 @@ class FusedBasicBlock(nn.Module):
     v2_s2_disabled = False     # ... of the stride-2 stages' large-batch form alone
 
     def forward(self, x):
-        import torch
-        import torch.nn.functional as F
-
         def shape_ok(t):   # the kernel's shapes: square, side tied to the channel count (127-px crops), channels-last
             return t.is_contiguous(memory_format=torch.channels_last) and t.shape[2] == t.shape[3] == _MC_SIDE.get(t.shape[1], -1)
 
@@ -561,8 +271,6 @@ class FusedBasicBlock(nn.Module):
     def _chained(self, x):
         """The block as two chained launches (None: not this input).  A LazyAct in: the previous block's output, finished while conv1
         stages it (and written out once, as this block's residual); a LazyAct out."""
-        import torch
-
         lazy = isinstance(x, LazyAct)
         if self.p2 is None or getattr(self, "_hdn_no_chain", False) or FusedBasicBlock.chain_disabled:
             return None
@@ -580,191 +288,6 @@ class FusedBasicBlock(nn.Module):
             s2, _, _ = chain_conv(LazyAct(s1, b1), self.p2, act_domain=dom)
             return LazyAct(s2, b2, idt if lazy else x)
         return None
-
-
-def pack_conv1x1(weight):
-    """[CO, CI, 1, 1] (or [CO, CI]) fp32 weights, BatchNorm folded in -> the stream hdn_conv1x1_f32 takes (hdn_pack_conv1x1_f32)."""
-    from . import _lib
-
-    CO, CI = weight.shape[0], weight.shape[1]
-    if tuple(weight.shape) not in ((CO, CI), (CO, CI, 1, 1)):
-        raise ValueError(f"pack_conv1x1 takes [CO, CI, 1, 1] weights, got {tuple(weight.shape)}")
-    lib, w = _lib.load(), _host_f32(weight.reshape(CO, CI))
-    return _c_pack("pack_conv1x1", lib.hdn_pack_conv1x1_bytes(CO, CI), lambda o, n: lib.hdn_pack_conv1x1_f32(w.data_ptr(), CO, CI, o, n))
-
-
-def conv1x1(x, wpacked, bias, residual=None, stride=1, relu=True, act_domain=0):
-    """[relu](conv1x1/stride(x) + bias (+ residual)) through hdn_conv1x1_f32; x channels-last [B,CI,S,S] float32, residual / result channels-last
-    [B,CO,So,So], So = (S - 1) // stride + 1; `wpacked` from pack_conv1x1, on x's device.  act_domain as conv3x3_bias_relu's."""
-    import torch
-
-    from . import _lib
-
-    dev = _lib.require_device(x, bias) if residual is None else _lib.require_device(x, bias, residual)
-    cl = torch.channels_last
-    if x.dim() != 4 or x.dtype != torch.float32 or x.shape[2] != x.shape[3] or not x.is_contiguous(memory_format=cl):
-        raise ValueError("conv1x1: square channels-last float32 input [B,CI,S,S]")
-    B, CI, S, _ = x.shape
-    CO, So = bias.numel(), (S - 1) // stride + 1
-    if wpacked.dtype != torch.int16 or wpacked.device != dev or wpacked.numel() != SPLIT_PIECES * CO * CI:
-        raise ValueError("conv1x1: weights must come from pack_conv1x1 for this (CO, CI), on the input's device")
-    if residual is not None and (tuple(residual.shape) != (B, CO, So, So) or not residual.is_contiguous(memory_format=cl)):
-        raise ValueError(f"conv1x1: residual must be channels-last {(B, CO, So, So)}")
-    out = torch.empty((B, CO, So, So), dtype=torch.float32, device=dev, memory_format=cl)
-    with _lib.device_guard(dev):
-        rc = _lib.load().hdn_conv1x1_f32(_lib.ptr(x), _lib.ptr(wpacked), _lib.ptr(bias), _lib.ptr(residual) if residual is not None else None,
-                                         _lib.ptr(out), B, S, CI, CO, int(stride), int(bool(relu)), int(act_domain), _lib.stream_ptr(dev))
-    _lib.check(rc, "conv1x1")
-    return out
-
-
-def pack_conv3x3s2(weight):
-    """[C, C, 3, 3] fp32 weights of a Bottleneck's stride-2 convolution, BatchNorm folded in, C = 128 / 256 / 512 -> the stream hdn_conv3x3s2_f32
-    takes (hdn_pack_conv3x3s2_f32)."""
-    from . import _lib
-
-    C = weight.shape[0]
-    if tuple(weight.shape) != (C, C, 3, 3):
-        raise ValueError(f"pack_conv3x3s2 takes [C, C, 3, 3] weights, got {tuple(weight.shape)}")
-    lib, w = _lib.load(), _host_f32(weight)
-    return _c_pack("pack_conv3x3s2", lib.hdn_pack_conv3x3s2_bytes(C), lambda o, n: lib.hdn_pack_conv3x3s2_f32(w.data_ptr(), C, o, n))
-
-
-def conv3x3s2(x, wpacked, bias, act_domain=0):
-    """relu(conv3x3 / stride 2 / padding 1 (x) + bias) through hdn_conv3x3s2_f32; x channels-last [B,C,2S,2S] float32 with (S, C) = (16, 128),
-    (8, 256) or (4, 512) -> channels-last [B,C,S,S]; `wpacked` from pack_conv3x3s2, on x's device.  act_domain as conv3x3_bias_relu's."""
-    import torch
-
-    from . import _lib
-
-    dev = _lib.require_device(x, bias)
-    cl = torch.channels_last
-    if x.dim() != 4 or x.shape[2] != x.shape[3] or x.shape[2] % 2 or not x.is_contiguous(memory_format=cl):
-        raise ValueError("conv3x3s2: square, even-sided channels-last float32 input [B,C,2S,2S]")
-    B, C, H, _ = x.shape
-    S = H // 2
-    if wpacked.dtype != torch.int16 or wpacked.device != dev or wpacked.numel() != 9 * SPLIT_PIECES * C * C or bias.numel() != C:
-        raise ValueError("conv3x3s2: weights must come from pack_conv3x3s2 for this channel count, on the input's device")
-    lib = _lib.load()
-    nws = lib.hdn_conv3x3s2_workspace_bytes(B, S, C)
-    if nws < 0:
-        _lib.check(int(nws), "conv3x3s2")
-    out = torch.empty((B, C, S, S), dtype=torch.float32, device=dev, memory_format=cl)
-    ws = torch.empty(nws // 4, dtype=torch.float32, device=dev) if nws else None   # (from torch's caching allocator: no sync, graph-safe)
-    with _lib.device_guard(dev):
-        rc = lib.hdn_conv3x3s2_f32(_lib.ptr(x), _lib.ptr(wpacked), _lib.ptr(bias), _lib.ptr(out), _lib.ptr(ws) if ws is not None else None, nws,
-                                   B, S, C, int(act_domain), _lib.stream_ptr(dev))
-    _lib.check(rc, "conv3x3s2")
-    return out
-
-
-def pack_conv3x3d(weight):
-    """[CO, CI, 3, 3] fp32 weights of a stride-1 convolution with padding == dilation (any of 1 / 2 / 4: the stream is the same), BatchNorm folded in,
-    CO and CI multiples of 32 -> the stream hdn_conv3x3d_f32 takes (hdn_pack_conv3x3d_f32)."""
-    from . import _lib
-
-    CO, CI = weight.shape[0], weight.shape[1]
-    if tuple(weight.shape) != (CO, CI, 3, 3):
-        raise ValueError(f"pack_conv3x3d takes [CO, CI, 3, 3] weights, got {tuple(weight.shape)}")
-    lib, w = _lib.load(), _host_f32(weight)
-    return _c_pack("pack_conv3x3d", lib.hdn_pack_conv3x3d_bytes(CO, CI), lambda o, n: lib.hdn_pack_conv3x3d_f32(w.data_ptr(), CO, CI, o, n))
-
-
-def conv3x3d(x, wpacked, bias, dilation=1, relu=True, act_domain=0):
-    """[relu](conv3x3 / stride 1 / dilation / padding = dilation (x) [+ bias]) through hdn_conv3x3d_f32; x channels-last [B,CI,S,S] float32 -> channels-last
-    [B,CO,S,S]; `wpacked` from pack_conv3x3d, on x's device (CO is read off its size); bias [CO] or None (zero).  act_domain as conv3x3_bias_relu's."""
-    import torch
-
-    from . import _lib
-
-    dev = _lib.require_device(x) if bias is None else _lib.require_device(x, bias)
-    cl = torch.channels_last
-    if x.dim() != 4 or x.dtype != torch.float32 or x.shape[2] != x.shape[3] or not x.is_contiguous(memory_format=cl):
-        raise ValueError("conv3x3d: square channels-last float32 input [B,CI,S,S]")
-    B, CI, S, _ = x.shape
-    CO = wpacked.numel() // (9 * SPLIT_PIECES * CI) if CI else 0
-    if wpacked.dtype != torch.int16 or wpacked.device != dev or CO <= 0 or wpacked.numel() != 9 * SPLIT_PIECES * CO * CI or (bias is not None and bias.numel() != CO):
-        raise ValueError("conv3x3d: weights must come from pack_conv3x3d for this CI (and the bias's CO), on the input's device")
-    lib = _lib.load()
-    nws = lib.hdn_conv3x3d_workspace_bytes(B, S, CI, CO, int(dilation))
-    if nws < 0:
-        _lib.check(int(nws), "conv3x3d")
-    out = torch.empty((B, CO, S, S), dtype=torch.float32, device=dev, memory_format=cl)
-    ws = torch.empty(nws // 4, dtype=torch.float32, device=dev) if nws else None   # (from torch's caching allocator: no sync, graph-safe)
-    with _lib.device_guard(dev):
-        rc = lib.hdn_conv3x3d_f32(_lib.ptr(x), _lib.ptr(wpacked), _lib.ptr(bias) if bias is not None else None, _lib.ptr(out),
-                                  _lib.ptr(ws) if ws is not None else None, nws, B, S, CI, CO, int(dilation), int(bool(relu)), int(act_domain),
-                                  _lib.stream_ptr(dev))
-    _lib.check(rc, "conv3x3d")
-    return out
-
-
-def conv3x3v(x, wpacked, bias, stride=2, relu=True, act_domain=0):
-    """[relu](conv3x3 / stride 1 or 2 / padding 0 (x) [+ bias]) through hdn_conv3x3v_f32; x channels-last [B,CI,S,S] float32, S >= 3 -> channels-last
-    [B,CO,So,So], So = (S - 3) // stride + 1; `wpacked` from pack_conv3x3d, on x's device (CO is read off its size); bias [CO] or None (zero).
-    act_domain as conv3x3_bias_relu's."""
-    import torch
-
-    from . import _lib
-
-    dev = _lib.require_device(x) if bias is None else _lib.require_device(x, bias)
-    cl = torch.channels_last
-    if x.dim() != 4 or x.dtype != torch.float32 or x.shape[2] != x.shape[3] or not x.is_contiguous(memory_format=cl):
-        raise ValueError("conv3x3v: square channels-last float32 input [B,CI,S,S]")
-    B, CI, S, _ = x.shape
-    CO = wpacked.numel() // (9 * SPLIT_PIECES * CI) if CI else 0
-    if wpacked.dtype != torch.int16 or wpacked.device != dev or CO <= 0 or wpacked.numel() != 9 * SPLIT_PIECES * CO * CI or (bias is not None and bias.numel() != CO):
-        raise ValueError("conv3x3v: weights must come from pack_conv3x3d for this CI (and the bias's CO), on the input's device")
-    lib = _lib.load()
-    nws = lib.hdn_conv3x3v_workspace_bytes(B, S, CI, CO, int(stride))
-    if nws < 0:
-        _lib.check(int(nws), "conv3x3v")
-    So = (S - 3) // int(stride) + 1
-    out = torch.empty((B, CO, So, So), dtype=torch.float32, device=dev, memory_format=cl)
-    ws = torch.empty(nws // 4, dtype=torch.float32, device=dev) if nws else None   # (from torch's caching allocator: no sync, graph-safe)
-    with _lib.device_guard(dev):
-        rc = lib.hdn_conv3x3v_f32(_lib.ptr(x), _lib.ptr(wpacked), _lib.ptr(bias) if bias is not None else None, _lib.ptr(out),
-                                  _lib.ptr(ws) if ws is not None else None, nws, B, S, CI, CO, int(stride), int(bool(relu)), int(act_domain),
-                                  _lib.stream_ptr(dev))
-    _lib.check(rc, "conv3x3v")
-    return out
-
-
-SIMI_STEM_MAX_SIDE = 255      # hdn_simi_stem_f32's documented limit (csrc/simi_stem.hip: MAX_S)
-
-
-def pack_simi_stem(weight):
-    """[64, 3, 7, 7] fp32 weights of the similarity backbone's conv1, BatchNorm folded in -> the stream hdn_simi_stem_f32 takes (hdn_pack_simi_stem_f32)."""
-    from . import _lib
-
-    if tuple(weight.shape) != (64, 3, 7, 7):
-        raise ValueError(f"pack_simi_stem takes [64, 3, 7, 7] weights, got {tuple(weight.shape)}")
-    lib, w = _lib.load(), _host_f32(weight)
-    return _c_pack("pack_simi_stem", lib.hdn_pack_simi_stem_bytes(), lambda o, n: lib.hdn_pack_simi_stem_f32(w.data_ptr(), o, n))
-
-
-def simi_stem(x, wpacked, bias):
-    """maxpool3x3/s2/p1(relu(conv7x7 / stride 2 / padding 0 (x) + bias)) through hdn_simi_stem_f32, one launch; x NCHW-contiguous [B,3,S,S] float32,
-    7 <= S <= SIMI_STEM_MAX_SIDE -> channels-last [B,64,Sp,Sp], Sp = ((S - 7) // 2) // 2 + 1; `wpacked` from pack_simi_stem, bias [64], on x's device."""
-    import torch
-
-    from . import _lib
-
-    dev = _lib.require_device(x, bias)
-    if x.dim() != 4 or x.dtype != torch.float32 or x.shape[1] != 3 or x.shape[2] != x.shape[3] or not x.is_contiguous():
-        raise ValueError("simi_stem: square NCHW-contiguous float32 input [B,3,S,S]")
-    B, _, S, _ = x.shape
-    lib = _lib.load()
-    if wpacked.dtype != torch.int16 or wpacked.device != dev or wpacked.numel() * 2 != lib.hdn_pack_simi_stem_bytes() or bias.numel() != 64:
-        raise ValueError("simi_stem: weights must come from pack_simi_stem (and a bias of 64), on the input's device")
-    if S < 7 or S > SIMI_STEM_MAX_SIDE:
-        raise ValueError(f"simi_stem: side {S} outside 7 .. {SIMI_STEM_MAX_SIDE}")
-    Sp = ((S - 7) // 2) // 2 + 1
-    out = torch.empty((B, 64, Sp, Sp), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
-    with _lib.device_guard(dev):
-        rc = lib.hdn_simi_stem_f32(_lib.ptr(x), _lib.ptr(wpacked), _lib.ptr(bias), _lib.ptr(out), B, S, 0, _lib.stream_ptr(dev))
-    _lib.check(rc, "simi_stem")
-    return out
 
 
 class FusedBottleneck(nn.Module):
@@ -805,9 +328,6 @@ class FusedBottleneck(nn.Module):
                 self.register_buffer(name + "d", b * 2.0 ** -ACT_SCALE_LOG2 if b is not None else None, persistent=False)
 
     def forward(self, x):
-        import torch
-        import torch.nn.functional as F
-
         cl = torch.channels_last
         dom = self.act_domain
         b1, b2, b3, bd = (self.b1d, self.b2d, self.b3d, self.bdd) if dom else (self.b1, self.b2, self.b3, self.bd)
@@ -876,17 +396,13 @@ def fold_for_inference(net: HomoResNet, channels_last: bool = True, fused_stem: 
     With every stage fused the interior runs in the scaled activation domain; the library's scale constant is checked first (check_act_scale)."""
     import copy
 
-    import torch
-
     trunk_block_kinds(net)
     net = copy.deepcopy(net).eval()
 
     def fuse(conv, bn):
-        s = bn.weight.double() / torch.sqrt(bn.running_var.double() + bn.eps)
         out = nn.Conv2d(conv.in_channels, conv.out_channels, conv.kernel_size, conv.stride, conv.padding, bias=True)
         out = out.to(conv.weight.device)
-        out.weight.data = (conv.weight.double() * s.view(-1, 1, 1, 1)).float()
-        out.bias.data = (bn.bias.double() - bn.running_mean.double() * s).float()
+        out.weight.data, out.bias.data = fold_conv_bn(conv, bn)
         return out
 
     net.conv1, net.bn1 = fuse(net.conv1, net.bn1), nn.Identity()
@@ -901,8 +417,7 @@ def fold_for_inference(net: HomoResNet, channels_last: bool = True, fused_stem: 
     for p in net.parameters():
         p.requires_grad_(False)
     if channels_last:
-        import torch as _t
-        net = net.to(memory_format=_t.channels_last)
+        net = net.to(memory_format=torch.channels_last)
     mc = bool(channels_last) if matrix_core is None else bool(matrix_core)
     # every stage fused and on the matrix cores: the interior runs in the scaled activation domain (ACT_SCALE_LOG2 above)
     dom = 1 if (fused_epilogue and fused_stem and mc and channels_last and os.environ.get("HDN_TRUNK_SCALED_DOMAIN", "1") not in ("", "0")) else 0
@@ -913,8 +428,7 @@ def fold_for_inference(net: HomoResNet, channels_last: bool = True, fused_stem: 
             setattr(net, name, nn.Sequential(*[(FusedBottleneck if hasattr(blk, "conv3") else FusedBasicBlock)(blk, mc, act_domain=dom)
                                                for blk in getattr(net, name)]))
         if channels_last:
-            import torch as _t
-            net = net.to(memory_format=_t.channels_last)
+            net = net.to(memory_format=torch.channels_last)
     if fused_stem:  # conv1 (+ folded bn1) + relu + maxpool in one HIP kernel; the stages behind it stay on MIOpen
         net.conv1 = FusedStem(net.conv1, channels_last, out_domain=dom)
         net.relu, net.maxpool = nn.Identity(), nn.Identity()
