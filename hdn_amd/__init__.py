@@ -13,3 +13,4 @@ from .refine import homo_refine, refine_warp  # noqa: F401
 
 __version__ = "0.1.0"
 from .backbone import optimize_similarity_model, restore_similarity_model  # noqa: F401
+from .batched_tracker import track_videos  # noqa: F401

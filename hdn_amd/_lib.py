@@ -46,6 +46,9 @@ SIGNATURES = {
     "hdn_subwindow_batch_f32": (_i, [_c_float_p] * 2 + [_i, _c_float_p] + [_i] * 6 + [ctypes.c_void_p]),
     "hdn_frame_warp_perspective_batch_u8": (_i, [_c_float_p] * 2 + [_i, _c_float_p] + [_i] * 4 + [ctypes.c_void_p]),
     "hdn_frame_warp_affine_cubic_batch_u8": (_i, [_c_float_p] * 2 + [_i, _c_float_p] + [_i] * 4 + [ctypes.c_void_p]),
+    "hdn_subwindow_ragged_f32": (_i, [_c_float_p, ctypes.c_longlong, _c_float_p, _c_float_p, _i, _c_float_p] + [_i] * 6 + [ctypes.c_void_p]),
+    "hdn_frame_warp_perspective_ragged_u8": (_i, [_c_float_p, ctypes.c_longlong, _c_float_p, _c_float_p, _i, _c_float_p] + [_i] * 4 + [ctypes.c_void_p]),
+    "hdn_frame_warp_affine_cubic_ragged_u8": (_i, [_c_float_p, ctypes.c_longlong, _c_float_p, _c_float_p, _i, _c_float_p] + [_i] * 4 + [ctypes.c_void_p]),
     "hdn_l1_score2_batch_f32": (_i, [_c_float_p] * 4 + [_i, ctypes.c_longlong, _i, ctypes.c_float, ctypes.c_void_p]),
     "hdn_remap_linear_f32": (_i, [_c_float_p] * 4 + [_i] * 5 + [ctypes.c_void_p]),
     "hdn_similarity_translation_f32": (_i, [_c_float_p] * 6 + [_i, _i, ctypes.c_double, ctypes.c_float, ctypes.c_double, _i, ctypes.c_void_p]),

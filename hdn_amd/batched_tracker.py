@@ -19,8 +19,12 @@ algorithms at another batch size) and of the B = 1-only packed head / chained tr
 sequence of a batch to its own B = 1 run (<= 1e-4 px on the corners with the stand-in networks; bit-exact frame kernels) and to the CPU
 restatement of the loop.
 
-Frames of all sequences of a step must have one size (they share the [N,H,W,3] buffer); sequences of different lengths: keep feeding
-the last frame of a finished one (its results are simply not read).
+Frames of all sequences of a step must have one size (they share the [N,H,W,3] buffer) - unless the tracker is given a
+`frame_capacity=(Hmax, Wmax)`: the frames then live in a hdn_amd.frame.FrameArena, every slot at its own size, the three frame kernels read
+each slot's size from device memory (hdn_*_ragged_*), and the same captured hipGraph goes on replaying while `reinit(slot, ...)` hands a
+slot a new video of another size.  Sequences of different lengths, or more videos than slots: track_videos(tracker, videos) below feeds a
+list of videos through the n slots (a finished slot takes the next video; with none left it is fed its last frame again and its results
+are dropped).
 """
 from __future__ import annotations
 
@@ -37,11 +41,20 @@ from .tracker import TRACK_CONST_DOUBLES
 
 
 class BatchedHomoTracker:
-    def __init__(self, hm_net, n: int, iterations: int = 1, similarity=None, score_gate: float = 2.5, graph: bool = False, cfg: TrackerConfig = None):
+    def __init__(self, hm_net, n: int, iterations: int = 1, similarity=None, score_gate: float = 2.5, graph: bool = False, cfg: TrackerConfig = None,
+                 frame_capacity=None):
         """hm_net: hdn_amd.HomoModelBuilder (or the reference's, after install()) in eval mode on the GPU; n: sequences per step.
-        similarity: None (identity) or a DeviceSimilarity (its model then holds n templates).  graph: one hipGraph per step."""
+        similarity: None (identity) or a DeviceSimilarity (its model then holds n templates).  graph: one hipGraph per step.
+        frame_capacity: None (all frames of a step have one size), or (Hmax, Wmax): arena mode - every slot has its own frame size up to
+        that capacity, and reinit() is available."""
         if n < 1:
             raise ValueError("n must be >= 1")
+        self.frame_capacity = None
+        if frame_capacity is not None:
+            self.frame_capacity = (int(frame_capacity[0]), int(frame_capacity[1]))
+            if min(self.frame_capacity) < 1:
+                raise ValueError("frame_capacity must be (Hmax, Wmax) >= 1")
+        self._arena = None
         self.net, self.n = hm_net, int(n)
         self.cfg = cfg or (similarity.cfg if similarity is not None and hasattr(similarity, "cfg") else TrackerConfig())
         self.use_graph, self._graph = bool(graph), None
@@ -91,7 +104,38 @@ class BatchedHomoTracker:
             self._copy_done.record()
         return dst
 
+    def _upload_arena(self, imgs, same_size: bool):
+        """n frames -> the arena's slots (arena mode); same_size: every frame must have its slot's current size (a step of running sequences)."""
+        n = self.n
+        if isinstance(imgs, torch.Tensor) or len(imgs) != n:
+            raise ValueError(f"this tracker advances {n} sequences per step and takes a list of {n} frames (each of its slot's size)")
+        if same_size:
+            for b, im in enumerate(imgs):
+                if tuple(im.shape[:2]) != self._arena.size(b):
+                    raise ValueError(f"slot {b} runs a sequence of {self._arena.size(b)} frames, got a frame of {tuple(im.shape[:2])}; "
+                                     "a slot changes its frame size in reinit() only")
+        self._arena.set_all(imgs)
+        return self._arena
+
     # -------------------------------------------------------------------------------------------------- init
+    @staticmethod
+    def _geometry(poly, cfg):
+        """(init_pos [2], size [2], init_s_z, init_s_z_sm) of one sequence from its poly (cx, cy, w, h, ...) (hdn_tracker_proj_e2e.py:66-84)."""
+        p = np.asarray(poly, np.float64).reshape(-1)[:4]
+        pos, size = p[0:2].copy(), p[2:4].copy()
+        ctx = cfg.context_amount * size.sum()
+        return pos, size, np.floor(np.sqrt((size[0] + ctx) * (size[1] + ctx))), np.floor(np.sqrt(size[0] * size[1]))
+
+    def _const_row(self, zp):
+        """One row of _consts (:251-258, as HomoTracker.init builds them: float32 matrices, float32 inverses)."""
+        E, row = self.cfg.exemplar_size, np.zeros(TRACK_CONST_DOUBLES, np.float64)
+        S = np.diag([E / (zp[2] - zp[0] + 1), E / (zp[3] - zp[1] + 1), 1.0]).astype(np.float32)
+        Sh = np.array([[1, 0, -zp[0]], [0, 1, -zp[1]], [0, 0, 1]], np.float32)
+        row[0:9], row[9:18] = np.linalg.inv(S).astype(np.float64).reshape(-1), S.astype(np.float64).reshape(-1)
+        row[18:27], row[27:36] = np.linalg.inv(Sh).astype(np.float64).reshape(-1), Sh.astype(np.float64).reshape(-1)
+        row[36] = self.score_gate
+        return row
+
     def init(self, imgs, bboxes, polys, gt_points, first_points=None):
         """Per sequence what hdnTrackerHomo.init takes (hdn_tracker_proj_e2e.py:60): imgs n x BGR uint8 [H,W,3]; bboxes n x (x, y, w, h);
         polys n x (cx, cy, w, h, theta); gt_points n x the initial corners (the same number of points for every sequence)."""
@@ -99,18 +143,23 @@ class BatchedHomoTracker:
         if not (len(bboxes) == len(polys) == len(gt_points) == n):
             raise ValueError(f"init takes {n} bboxes / polys / gt_points")
         self.dev = next(self.net.parameters()).device
-        polys = np.asarray([np.asarray(p, np.float64).reshape(-1)[:4] for p in polys], np.float64)
-        self.init_pos = polys[:, 0:2].copy()
-        self.size = polys[:, 2:4].copy()
-        ctx = c.context_amount * self.size.sum(axis=1)
-        self.init_s_z = np.floor(np.sqrt((self.size[:, 0] + ctx) * (self.size[:, 1] + ctx)))
-        self.init_s_z_sm = np.floor(np.sqrt(self.size[:, 0] * self.size[:, 1]))
-        frames = self._upload(imgs)
-        # np.mean(img, axis=(0, 1)) of every first frame: one reduction on the device, read once
-        self.channel_average = frames.to(torch.float64).mean(dim=(1, 2)).cpu().numpy()
+        geo = [self._geometry(p, c) for p in polys]
+        self.init_pos, self.size = np.stack([g[0] for g in geo]), np.stack([g[1] for g in geo])
+        self.init_s_z, self.init_s_z_sm = np.array([g[2] for g in geo], np.float64), np.array([g[3] for g in geo], np.float64)
+        if self.frame_capacity is not None:      # arena mode: first frames of different sizes
+            if not torch.cuda.is_available():
+                raise _lib.HdnHipError("hdn_amd runs on the GPU only; there is no CPU fallback")
+            self._arena = FR.FrameArena(n, self.frame_capacity[0], self.frame_capacity[1], 3, device=self.dev)
+            frames = self._upload_arena(imgs, same_size=False)
+            self.channel_average = torch.stack([frames.frame(b).to(torch.float64).mean(dim=(0, 1)) for b in range(n)]).cpu().numpy()
+            sizes = [frames.size(b) for b in range(n)]
+        else:
+            frames = self._upload(imgs)
+            # np.mean(img, axis=(0, 1)) of every first frame: one reduction on the device, read once
+            self.channel_average = frames.to(torch.float64).mean(dim=(1, 2)).cpu().numpy()
+            sizes = [tuple(frames.shape[1:3])] * n
         self.host_syncs += 1
-        _, H, W, _ = frames.shape
-        self.z_crop_points_sm = [FR.crop_points(self.init_pos[b], self.init_s_z_sm[b], H, W) for b in range(n)]
+        self.z_crop_points_sm = [FR.crop_points(self.init_pos[b], self.init_s_z_sm[b], sizes[b][0], sizes[b][1]) for b in range(n)]
         # get_template_info(get_subwindow_for_homo(...)[:, 0:3]): the normalised gray templates, constant for the sequences
         self._const_params = torch.from_numpy(np.concatenate([self.init_pos, self.init_s_z_sm[:, None], self.channel_average], axis=1)).to(self.dev)
         self.init_homo_tmp = FR.get_search_info(frames, None, None, None, model_sz=c.exemplar_size, params=self._const_params)
@@ -127,15 +176,40 @@ class BatchedHomoTracker:
         self._Ht, self._Hinv = (torch.empty((n, 9), dtype=torch.float64, device=self.dev) for _ in range(2))
         self._out = torch.empty((n, 2 * self.n_points + 1), dtype=torch.float32, device=self.dev)
         self._graph = None
-        E = c.exemplar_size
-        consts = np.zeros((n, TRACK_CONST_DOUBLES), np.float64)
-        for b, zp in enumerate(self.z_crop_points_sm):       # (:251-258, as HomoTracker.init builds them: float32 matrices, float32 inverses)
-            S = np.diag([E / (zp[2] - zp[0] + 1), E / (zp[3] - zp[1] + 1), 1.0]).astype(np.float32)
-            Sh = np.array([[1, 0, -zp[0]], [0, 1, -zp[1]], [0, 0, 1]], np.float32)
-            consts[b, 0:9], consts[b, 9:18] = np.linalg.inv(S).astype(np.float64).reshape(-1), S.astype(np.float64).reshape(-1)
-            consts[b, 18:27], consts[b, 27:36] = np.linalg.inv(Sh).astype(np.float64).reshape(-1), Sh.astype(np.float64).reshape(-1)
-            consts[b, 36] = self.score_gate
+        consts = np.stack([self._const_row(zp) for zp in self.z_crop_points_sm])
         self._consts = torch.from_numpy(consts).to(self.dev)
+
+    def reinit(self, slot: int, img, bbox, poly, gt_points, first_point=None):
+        """What init does for ONE sequence, written in place into row `slot` of every per-sequence tensor: the slot starts a new video (of any
+        frame size up to the capacity) while the other slots keep going.  No other row is touched and no tensor is replaced, so the captured
+        hipGraph is not re-captured.  Arena mode only (frame_capacity=...).  gt_points: as many points as init was given.  One host read, the one
+        init has (the first frame's channel average).  The similarity branch's template goes through DeviceSimilarity.reinit, which also refreshes
+        the heads' cached template-branch features in place - with HDN_HIP_HEADS too: its template pack holds weights only and serves one row."""
+        if self._arena is None:
+            raise RuntimeError("reinit() needs arena mode (frame_capacity=(Hmax, Wmax)) and an init() before it")
+        if not 0 <= slot < self.n:
+            raise IndexError(f"slot {slot} of {self.n}")
+        pts = np.asarray(gt_points, np.float64).reshape(-1, 2)
+        if pts.shape[0] != self.n_points:
+            raise ValueError(f"this tracker follows {self.n_points} points per sequence, got {pts.shape[0]}")
+        c = self.cfg
+        pos, size, s_z, s_z_sm = self._geometry(poly, c)
+        self._arena.set(slot, img)                   # (raises for a frame above the capacity, before anything is written)
+        frame = self._arena.frame(slot)
+        avg = frame.to(torch.float64).mean(dim=(0, 1)).cpu().numpy()
+        self.host_syncs += 1
+        self.init_pos[slot], self.size[slot], self.init_s_z[slot], self.init_s_z_sm[slot], self.channel_average[slot] = pos, size, s_z, s_z_sm, avg
+        zp = self.z_crop_points_sm[slot] = FR.crop_points(pos, s_z_sm, frame.shape[0], frame.shape[1])
+        self._const_params[slot].copy_(torch.from_numpy(np.concatenate([pos, [s_z_sm], avg])))
+        tmp = FR.get_search_info(frame, None, None, None, model_sz=c.exemplar_size, params=self._const_params[slot])
+        self.init_homo_tmp[slot:slot + 1].copy_(tmp)
+        with torch.no_grad():
+            self.init_patch_1[slot:slot + 1].copy_(self.net.ShareFeature(tmp))
+        if self.similarity is not None:
+            self.similarity.reinit(slot, frame, pos, s_z, s_z_sm, avg)
+        self.init_points[slot].copy_(torch.from_numpy(pts))
+        self.H_total[slot].copy_(torch.eye(3, dtype=torch.float64))
+        self._consts[slot].copy_(torch.from_numpy(self._const_row(zp)))
 
     # -------------------------------------------------------------------------------------------------- one step = one frame of every sequence
     def _body(self, frames):
@@ -164,7 +238,8 @@ class BatchedHomoTracker:
         return self._out, score
 
     def _capture(self, frame_shape):
-        self._static_frames = torch.empty(frame_shape, dtype=torch.uint8, device=self.dev)
+        # (arena mode: the arena IS the static input - its slots hold the sequences' latest frames, their sizes are device data)
+        self._static_frames = self._arena if self._arena is not None else torch.empty(frame_shape, dtype=torch.uint8, device=self.dev)
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         H0 = self.H_total.clone()
@@ -185,9 +260,13 @@ class BatchedHomoTracker:
         """One frame of every sequence.  -> list of n result dictionaries with hdnTrackerHomo.track_new's keys (sync=True; one host read
         for all of them), or device views {'points' [n, P, 2], 'best_score' [n]} (sync=False)."""
         n, P = self.n, self.n_points
+        arena = self._arena is not None
+        if arena:
+            imgs = [np.asarray(im) if not isinstance(im, torch.Tensor) else im for im in imgs] if not isinstance(imgs, torch.Tensor) else imgs
+            self._upload_arena(imgs, same_size=True)          # (before a first capture too: a refused step leaves nothing half done)
         if self.use_graph:
             if self._graph is None:
-                shape = tuple(imgs.shape) if isinstance(imgs, torch.Tensor) else (n,) + tuple(np.asarray(imgs[0]).shape)
+                shape = None if arena else tuple(imgs.shape) if isinstance(imgs, torch.Tensor) else (n,) + tuple(np.asarray(imgs[0]).shape)
                 try:
                     self._capture(shape)
                 except RuntimeError as e:
@@ -195,13 +274,14 @@ class BatchedHomoTracker:
                     warnings.warn(f"hdn_amd: the batched per-frame body could not be captured as a hipGraph ({type(e).__name__}: {e}); running it eagerly")
                     self.use_graph, self._graph = False, None
                     return self.track_new(fr_idx, imgs, sync=sync)
-            self._upload(imgs, into=self._static_frames)
+            if not arena:
+                self._upload(imgs, into=self._static_frames)
             self._graph.replay()
             out, score = self._g_out, self._g_score
             if not sync:
                 out, score = out.clone(), score.clone()
         else:
-            out, score = self._body(self._upload(imgs))
+            out, score = self._body(self._arena if arena else self._upload(imgs))
             out = out.clone()
         self.last_points, self.last_score = out[:, :2 * P].view(n, P, 2), score
         if not sync:
@@ -227,7 +307,7 @@ class BatchedDeviceTracker(BatchedHomoTracker):
     per step (graph=False or HDN_TRACKER_GRAPH=0: eager), exactly as DeviceTrackerHomo does for one sequence; `hip_trunk` as there."""
 
     def __init__(self, model, n: int, graph: bool = None, iterations: int = 1, cfg: TrackerConfig = None, fold_backbone: bool = None,
-                 hip_trunk: bool = None):
+                 hip_trunk: bool = None, frame_capacity=None):
         if cfg is None:
             cfg = TrackerConfig()
             try:
@@ -244,7 +324,8 @@ class BatchedDeviceTracker(BatchedHomoTracker):
         self.folded = BB.optimize_similarity_model(model) if (BB.enabled() if fold_backbone is None else fold_backbone) else []
         from .tracker import attach_hip_trunk
         self.hip_trunk = attach_hip_trunk(model, hip_trunk)
-        super().__init__(model.hm_net, n, iterations=iterations, similarity=DeviceSimilarity(model, cfg), graph=graph, cfg=cfg)
+        super().__init__(model.hm_net, n, iterations=iterations, similarity=DeviceSimilarity(model, cfg), graph=graph, cfg=cfg,
+                         frame_capacity=frame_capacity)
 
     def _find_mode(self):
         import contextlib
@@ -268,3 +349,70 @@ class BatchedDeviceTracker(BatchedHomoTracker):
     def track_new(self, fr_idx, imgs, sync: bool = True):
         with self._find_mode():
             return super().track_new(fr_idx, imgs, sync=sync)
+
+    def reinit(self, slot, img, bbox, poly, gt_points, first_point=None):
+        with self._find_mode():
+            return super().reinit(slot, img, bbox, poly, gt_points, first_point)
+
+
+def track_videos(tracker, videos, on_result=None):
+    """Feed a list of videos (any lengths; in arena mode any frame sizes up to the capacity) through the tracker's n slots - what the reference's
+    users do by splitting the dataset by hand across processes (tools/test.py:91-103).
+
+    videos: iterable of (frames, init) - frames an iterable of BGR uint8 [H,W,3] whose first frame initialises the sequence, init a dict with
+    'bbox', 'poly', 'gt_points' and optionally 'first_point'.  The first n videos fill the slots (init); every step advances all slots
+    (track_new: one host read); a slot whose video ended is handed the next one (reinit), and with none left it is fed its last frame again,
+    its results dropped.  Fewer videos than slots: the spare slots run copies of the last video, dropped as well.
+    -> list, in input order, of per-video lists of track_new's dictionaries (one per frame after the first); with on_result, that is called as
+    on_result(video_index, frame_index, result) instead and the lists stay empty.
+    Plain scheduling over tracker.n / init / track_new / reinit (and tracker.frame_capacity where it has one: a video whose first frame is
+    above it raises before anything is launched)."""
+    n = tracker.n
+    cap = getattr(tracker, "frame_capacity", None)
+    queue = []
+    for k, (frames, init) in enumerate(videos):
+        it = iter(frames)
+        try:
+            first = next(it)
+        except StopIteration:
+            raise ValueError(f"video {k} has no frames") from None
+        if cap is not None and (first.shape[0] > cap[0] or first.shape[1] > cap[1]):
+            raise ValueError(f"video {k}: frames of {tuple(first.shape[:2])} are above the tracker's frame capacity {tuple(cap)}")
+        queue.append((k, first, it, init))
+    results = [[] for _ in queue]
+    if not queue:
+        return results
+    queue.reverse()                                  # pop() from the end = input order
+    # slot state: [video index or None (idle), frame iterator, last frame fed, frames fed after the first]
+    slots = []
+    for b in range(n):
+        if queue:
+            k, first, it, init = queue.pop()
+            slots.append([k, it, first, 0, init])
+        else:                                        # fewer videos than slots: an idle copy of the last one
+            slots.append([None, iter(()), slots[-1][2], 0, slots[-1][4]])
+    tracker.init([s[2] for s in slots], [s[4]["bbox"] for s in slots], [s[4]["poly"] for s in slots], [s[4]["gt_points"] for s in slots],
+                 [s[4].get("first_point") for s in slots])
+    while True:
+        # a slot whose video has no further frame takes the next video, or goes idle
+        for b, s in enumerate(slots):
+            while s[0] is not None:
+                nxt = next(s[1], None)
+                if nxt is not None:
+                    s[2], s[3] = nxt, s[3] + 1
+                    break
+                if not queue:
+                    s[0] = None
+                    break
+                k, first, it, init = queue.pop()
+                tracker.reinit(b, first, init["bbox"], init["poly"], init["gt_points"], init.get("first_point"))
+                s[0], s[1], s[2], s[3], s[4] = k, it, first, 0, init
+        if all(s[0] is None for s in slots):
+            return results
+        res = tracker.track_new(None, [s[2] for s in slots])
+        for b, s in enumerate(slots):
+            if s[0] is not None:
+                if on_result is not None:
+                    on_result(s[0], s[3], res[b])
+                else:
+                    results[s[0]].append(res[b])

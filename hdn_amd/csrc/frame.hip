@@ -47,12 +47,10 @@ __device__ __forceinline__ ResizeAxis resize_axis(int d, int dn, int sn) {
 // params (device, float64): [cx, cy, original_sz, avg_0 .. avg_{C-1}]
 // blockIdx.y = the frame of a batch (one sequence each, hdn_subwindow_batch_f32): frames contiguous [B,H,W,C], the parameter records
 // `params_stride` doubles apart (they may be columns of a wider per-sequence record), the crops contiguous [B, C | 1, model_sz, model_sz].
-__global__ __launch_bounds__(HDN_BLOCK) void subwindow_kernel(const uint8_t* __restrict__ frame, const double* __restrict__ params,
-                                                              float* __restrict__ out, int H, int W, int C, int model_sz, int mode,
-                                                              int params_stride) {
-  frame += size_t(blockIdx.y) * H * W * C;
-  params += size_t(blockIdx.y) * params_stride;
-  out += size_t(blockIdx.y) * (mode ? 1 : C) * model_sz * model_sz;
+// (the body of one frame: `frame` / `params` / `out` are this frame's own; shared by the batch kernel, where H and W are launch arguments, and the
+// ragged one, where every workgroup reads its slot's from device memory)
+__device__ __forceinline__ void subwindow_body(const uint8_t* __restrict__ frame, const double* __restrict__ params, float* __restrict__ out, int H,
+                                               int W, int C, int model_sz, int mode) {
   const double cx = params[0], cy = params[1], sz = params[2];
   const double c = (sz - 1.0) / 2.0;
   const double xmin_d = floor(cx - c + 0.5), ymin_d = floor(cy - c + 0.5);
@@ -103,6 +101,33 @@ __global__ __launch_bounds__(HDN_BLOCK) void subwindow_kernel(const uint8_t* __r
   }
 }
 
+__global__ __launch_bounds__(HDN_BLOCK) void subwindow_kernel(const uint8_t* __restrict__ frame, const double* __restrict__ params,
+                                                              float* __restrict__ out, int H, int W, int C, int model_sz, int mode,
+                                                              int params_stride) {
+  subwindow_body(frame + size_t(blockIdx.y) * H * W * C, params + size_t(blockIdx.y) * params_stride,
+                 out + size_t(blockIdx.y) * (mode ? 1 : C) * model_sz * model_sz, H, W, C, model_sz, mode);
+}
+
+// ---- ragged launches: B slots `slot_stride` bytes apart, slot b a dense [H_b, W_b, C] frame at its start, (H_b, W_b) = dims[b] on the DEVICE ---------
+// The grid is sized from the capacity (Hmax, Wmax); a workgroup reads its slot's record and runs the same grid-stride loop over its own H_b * W_b (the
+// workgroups beyond it find nothing to do).  dims is device data the host never sees: a record that does not fit its slot is skipped, the slot
+// neither read nor written.
+__device__ __forceinline__ bool slot_dims(const int* __restrict__ dims, int Hmax, int Wmax, int C, long long slot_stride, int& H, int& W) {
+  H = dims[2 * blockIdx.y];
+  W = dims[2 * blockIdx.y + 1];
+  return H >= 1 && W >= 1 && H <= Hmax && W <= Wmax && (long long)H * W * C <= slot_stride;
+}
+
+__global__ __launch_bounds__(HDN_BLOCK) void subwindow_ragged_kernel(const uint8_t* __restrict__ frames, long long slot_stride,
+                                                                     const int* __restrict__ dims, const double* __restrict__ params,
+                                                                     float* __restrict__ out, int Hmax, int Wmax, int C, int model_sz, int mode,
+                                                                     int params_stride) {
+  int H, W;
+  if (!slot_dims(dims, Hmax, Wmax, C, slot_stride, H, W)) return;
+  subwindow_body(frames + size_t(blockIdx.y) * slot_stride, params + size_t(blockIdx.y) * params_stride,
+                 out + size_t(blockIdx.y) * (mode ? 1 : C) * model_sz * model_sz, H, W, C, model_sz, mode);
+}
+
 // ---- cv2.warpPerspective, 8U, INTER_LINEAR, BORDER_REPLICATE ----------------------------------------------------------
 // A pixel of the BGR frame is 3 bytes at a byte-aligned address; neighbouring taps of a row are contiguous.  One byte-aligned 4-byte
 // load (global memory takes them) per 4 bytes instead of one byte load per sample: the warps are bound by the number of loads.
@@ -118,12 +143,8 @@ __device__ __forceinline__ void inv3(const double* m, double* o) {
 }
 __device__ __forceinline__ int cv_round_sat(double v) { return (int)rint(fmax(-2147483648.0, fmin(2147483647.0, v))); }
 
-__global__ __launch_bounds__(HDN_BLOCK) void frame_warp_perspective_kernel(const uint8_t* __restrict__ src, const double* __restrict__ M,
-                                                                           uint8_t* __restrict__ dst, int H, int W, int C, int bw,
-                                                                           int m_stride) {
-  src += size_t(blockIdx.y) * H * W * C;      // (blockIdx.y = the frame of a batch, each with its own matrix: hdn_frame_warp_perspective_batch_u8)
-  dst += size_t(blockIdx.y) * H * W * C;
-  M += size_t(blockIdx.y) * m_stride;
+__device__ __forceinline__ void frame_warp_perspective_body(const uint8_t* __restrict__ src, const double* __restrict__ M,
+                                                            uint8_t* __restrict__ dst, int H, int W, int C, int bw) {
   double m[9], mi[9];
 #pragma unroll
   for (int q = 0; q < 9; ++q) m[q] = M[q];
@@ -169,14 +190,36 @@ __global__ __launch_bounds__(HDN_BLOCK) void frame_warp_perspective_kernel(const
   }
 }
 
+__global__ __launch_bounds__(HDN_BLOCK) void frame_warp_perspective_kernel(const uint8_t* __restrict__ src, const double* __restrict__ M,
+                                                                           uint8_t* __restrict__ dst, int H, int W, int C, int bw,
+                                                                           int m_stride) {
+  // (blockIdx.y = the frame of a batch, each with its own matrix: hdn_frame_warp_perspective_batch_u8)
+  frame_warp_perspective_body(src + size_t(blockIdx.y) * H * W * C, M + size_t(blockIdx.y) * m_stride, dst + size_t(blockIdx.y) * H * W * C, H, W,
+                              C, bw);
+}
+
+// OpenCV's block walk (BLOCK_SZ 32): it fixes the summation order of x.  The batch entry computes it on the host; a ragged slot has its own.
+__host__ __device__ __forceinline__ int perspective_bw(int H, int W) {
+  const int bh = H < 16 ? H : 16;
+  return 1024 / bh < W ? 1024 / bh : W;
+}
+
+__global__ __launch_bounds__(HDN_BLOCK) void frame_warp_perspective_ragged_kernel(const uint8_t* __restrict__ src, long long slot_stride,
+                                                                                  const int* __restrict__ dims, const double* __restrict__ M,
+                                                                                  uint8_t* __restrict__ dst, int Hmax, int Wmax, int C,
+                                                                                  int m_stride) {
+  int H, W;
+  if (!slot_dims(dims, Hmax, Wmax, C, slot_stride, H, W)) return;
+  // (the 4-byte fast path's guard inside uses this slot's own H * W: a frame's last pixels never read the next slot's bytes as their own)
+  frame_warp_perspective_body(src + size_t(blockIdx.y) * slot_stride, M + size_t(blockIdx.y) * m_stride, dst + size_t(blockIdx.y) * slot_stride, H,
+                              W, C, perspective_bw(H, W));
+}
+
 // ---- cv2.warpAffine, 8U, INTER_CUBIC, BORDER_REPLICATE ---------------------------------------------------------------
 __device__ short g_cubic_itab[32 * 32 * 16];
 
-__global__ __launch_bounds__(HDN_BLOCK) void frame_warp_affine_cubic_kernel(const uint8_t* __restrict__ src, const double* __restrict__ M,
-                                                                            uint8_t* __restrict__ dst, int H, int W, int C, int m_stride) {
-  src += size_t(blockIdx.y) * H * W * C;      // (blockIdx.y = the frame of a batch: hdn_frame_warp_affine_cubic_batch_u8)
-  dst += size_t(blockIdx.y) * H * W * C;
-  M += size_t(blockIdx.y) * m_stride;
+__device__ __forceinline__ void frame_warp_affine_cubic_body(const uint8_t* __restrict__ src, const double* __restrict__ M,
+                                                             uint8_t* __restrict__ dst, int H, int W, int C) {
   // invert the 2x3 matrix as cv::warpAffine does
   double m00 = M[0], m01 = M[1], m02 = M[2], m10 = M[3], m11 = M[4], m12 = M[5];
   double D = m00 * m11 - m01 * m10;
@@ -227,6 +270,23 @@ __global__ __launch_bounds__(HDN_BLOCK) void frame_warp_affine_cubic_kernel(cons
     if (valid)
       for (int q = 0; q < C; ++q) dst[pix * C + q] = (uint8_t)res[q];
   }
+}
+
+__global__ __launch_bounds__(HDN_BLOCK) void frame_warp_affine_cubic_kernel(const uint8_t* __restrict__ src, const double* __restrict__ M,
+                                                                            uint8_t* __restrict__ dst, int H, int W, int C, int m_stride) {
+  // (blockIdx.y = the frame of a batch: hdn_frame_warp_affine_cubic_batch_u8)
+  frame_warp_affine_cubic_body(src + size_t(blockIdx.y) * H * W * C, M + size_t(blockIdx.y) * m_stride, dst + size_t(blockIdx.y) * H * W * C, H, W,
+                               C);
+}
+
+__global__ __launch_bounds__(HDN_BLOCK) void frame_warp_affine_cubic_ragged_kernel(const uint8_t* __restrict__ src, long long slot_stride,
+                                                                                   const int* __restrict__ dims, const double* __restrict__ M,
+                                                                                   uint8_t* __restrict__ dst, int Hmax, int Wmax, int C,
+                                                                                   int m_stride) {
+  int H, W;
+  if (!slot_dims(dims, Hmax, Wmax, C, slot_stride, H, W)) return;
+  frame_warp_affine_cubic_body(src + size_t(blockIdx.y) * slot_stride, M + size_t(blockIdx.y) * m_stride, dst + size_t(blockIdx.y) * slot_stride,
+                               H, W, C);
 }
 
 // BicubicTab_i of OpenCV's initInterTab2D (A = -0.75; short(v * 32768) with the 16 taps' sum forced to 32768)
@@ -341,8 +401,7 @@ int hdn_frame_warp_perspective_batch_u8(const unsigned char* src, const double* 
     const unsigned char* const de = dst + (size_t)B * H * W * C;
     if (src < de && dst < se) return HDN_E_ALIAS;
   }
-  int bh = H < 16 ? H : 16;                      // OpenCV's block walk (BLOCK_SZ 32): it fixes the summation order of x
-  int bw = 1024 / bh < W ? 1024 / bh : W;
+  const int bw = hdn::perspective_bw(H, W);
   hipLaunchKernelGGL(hdn::frame_warp_perspective_kernel, dim3(hdn::frame_grid((size_t)H * W), B), dim3(HDN_BLOCK), 0,
                      static_cast<hipStream_t>(stream), src, M, dst, H, W, C, bw, m_stride);
   return hdn::launch_status();
@@ -371,6 +430,55 @@ int hdn_frame_warp_affine_cubic_batch_u8(const unsigned char* src, const double*
 
 int hdn_frame_warp_affine_cubic_u8(const unsigned char* src, const double* M, unsigned char* dst, int H, int W, int C, void* stream) {
   return hdn_frame_warp_affine_cubic_batch_u8(src, M, 6, dst, 1, H, W, C, stream);
+}
+
+// The host side of a ragged launch: what the batch entries check, on the capacity, plus the slots' stride; -> 0 or the error code.
+static int ragged_check(const void* a, const void* dims, const void* rec, const void* b, long long slot_stride, int rec_stride, int rec_min, int B,
+                        int Hmax, int Wmax, int C) {
+  if (!a || !dims || !rec || !b) return HDN_E_NULL;
+  if (B <= 0 || Hmax <= 0 || Wmax <= 0 || C <= 0 || rec_stride < rec_min) return HDN_E_SHAPE;
+  if (C > hdn::FR_MAXC || (long long)Hmax * Wmax > (1LL << 30) || B > 65535) return HDN_E_LIMIT;
+  if (slot_stride < (long long)Hmax * Wmax * C) return HDN_E_SHAPE;
+  return HDN_OK;
+}
+static bool overlap(const void* a, size_t an, const void* b, size_t bn) {
+  const unsigned char *p = (const unsigned char*)a, *q = (const unsigned char*)b;
+  return p < q + bn && q < p + an;
+}
+
+int hdn_subwindow_ragged_f32(const unsigned char* frames, long long slot_stride, const int* dims, const double* params, int params_stride,
+                             float* out, int B, int Hmax, int Wmax, int C, int model_sz, int mode, void* stream) {
+  if (!frames || !dims || !params || !out) return HDN_E_NULL;
+  if (model_sz <= 0 || (mode != 0 && mode != 1) || (mode == 1 && C != 3)) return HDN_E_SHAPE;
+  const int rc = ragged_check(frames, dims, params, out, slot_stride, params_stride, 3 + (C > 0 ? C : 0), B, Hmax, Wmax, C);
+  if (rc != HDN_OK) return rc;
+  if (model_sz > 4096) return HDN_E_LIMIT;
+  if (overlap(frames, (size_t)B * slot_stride, out, (size_t)B * (mode ? 1 : C) * model_sz * model_sz * sizeof(float))) return HDN_E_ALIAS;
+  hipLaunchKernelGGL(hdn::subwindow_ragged_kernel, dim3(hdn::frame_grid((size_t)model_sz * model_sz), B), dim3(HDN_BLOCK), 0,
+                     static_cast<hipStream_t>(stream), frames, slot_stride, dims, params, out, Hmax, Wmax, C, model_sz, mode, params_stride);
+  return hdn::launch_status();
+}
+
+int hdn_frame_warp_perspective_ragged_u8(const unsigned char* src, long long slot_stride, const int* dims, const double* M, int m_stride,
+                                         unsigned char* dst, int B, int Hmax, int Wmax, int C, void* stream) {
+  const int rc = ragged_check(src, dims, M, dst, slot_stride, m_stride, 9, B, Hmax, Wmax, C);
+  if (rc != HDN_OK) return rc;
+  if (overlap(src, (size_t)B * slot_stride, dst, (size_t)B * slot_stride)) return HDN_E_ALIAS;
+  hipLaunchKernelGGL(hdn::frame_warp_perspective_ragged_kernel, dim3(hdn::frame_grid((size_t)Hmax * Wmax), B), dim3(HDN_BLOCK), 0,
+                     static_cast<hipStream_t>(stream), src, slot_stride, dims, M, dst, Hmax, Wmax, C, m_stride);
+  return hdn::launch_status();
+}
+
+int hdn_frame_warp_affine_cubic_ragged_u8(const unsigned char* src, long long slot_stride, const int* dims, const double* M, int m_stride,
+                                          unsigned char* dst, int B, int Hmax, int Wmax, int C, void* stream) {
+  int rc = ragged_check(src, dims, M, dst, slot_stride, m_stride, 6, B, Hmax, Wmax, C);
+  if (rc != HDN_OK) return rc;
+  if (overlap(src, (size_t)B * slot_stride, dst, (size_t)B * slot_stride)) return HDN_E_ALIAS;
+  rc = hdn::ensure_cubic_tab();
+  if (rc != HDN_OK) return rc;
+  hipLaunchKernelGGL(hdn::frame_warp_affine_cubic_ragged_kernel, dim3(hdn::frame_grid((size_t)Hmax * Wmax), B), dim3(HDN_BLOCK), 0,
+                     static_cast<hipStream_t>(stream), src, slot_stride, dims, M, dst, Hmax, Wmax, C, m_stride);
+  return hdn::launch_status();
 }
 
 int hdn_remap_linear_f32(const float* src, const float* mapx, const float* mapy, float* dst, int C, int Hs, int Ws, int Hd, int Wd,

@@ -10,6 +10,8 @@ The reference handles every frame on the host (numpy + OpenCV) and uploads three
     warp_perspective(frame, M)                             <- cv2.warpPerspective(img, M, BORDER_REPLICATE), hdn_tracker_proj_e2e.py:154
     rot_around_center(frame, cx, cy, rot)                  <- img_rot_around_center, hdn/utils/transform.py:69-100
     get_polar_img(patch) / get_subwindow(..., islog=1)     <- getPolarImg (cv2.logPolar), hdn/models/logpolar.py:11-29, base_tracker.py:119-126
+    FrameArena(n, Hmax, Wmax)                              n slots holding frames of DIFFERENT sizes (the videos of a dataset, tools/test.py:91-103,
+                                                           fed through the lock-step tracker): the crops / warps take it where they take [B,H,W,C]
 
 Same argument meaning and return shapes as the reference's functions; `pos` / `original_sz` / matrices may be host numbers
 (packed into a small device array without synchronising) or float64 device tensors (nothing leaves the device).  The parts
@@ -50,6 +52,140 @@ def _check_frame(frame):
     return frame.shape[-3:]
 
 
+class FrameArena:
+    """n slots of uint8 frames of different sizes in one device buffer: slot b holds a dense [H_b, W_b, C] frame at its start, the slots are
+    `slot_stride` = Hmax * Wmax * C bytes apart, and `dims` is the DEVICE int32 [n, 2] table of (H_b, W_b) the ragged kernels read
+    (hdn_*_ragged_*, include/hdn_hip.h).  Sizes therefore are data, not launch arguments: a captured hipGraph keeps replaying while set()
+    changes a slot's frame size.  A slot that was never set has dims (0, 0) and is skipped by every kernel.
+
+        set(b, img) / set_all(imgs)   np.uint8 [H,W,C] (or a uint8 tensor) -> slot b / every slot, through one pinned staging arena; a frame
+                                      above the capacity raises before anything is written
+        frame(b)                      the dense [H_b, W_b, C] view of slot b
+        like()                        an empty arena of the same geometry sharing THIS `dims` tensor: what the warps return
+    """
+
+    def __init__(self, n: int, Hmax: int, Wmax: int, C: int = 3, device=None, _like=None):
+        n, Hmax, Wmax, C = int(n), int(Hmax), int(Wmax), int(C)
+        if n < 1 or Hmax < 1 or Wmax < 1 or C < 1:
+            raise ValueError("FrameArena takes n, Hmax, Wmax, C >= 1")
+        self.n, self.Hmax, self.Wmax, self.C = n, Hmax, Wmax, C
+        self.slot_stride = Hmax * Wmax * C
+        # (a host arena holds frames and checks sizes like a device one - what the host tests use - but no kernel takes it: there is no CPU fallback)
+        self.device = _like.device if _like is not None else torch.device(device if device is not None else "cuda")
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.data = torch.empty((n, self.slot_stride), dtype=torch.uint8, device=self.device)
+        if _like is None:
+            self.dims = torch.zeros((n, 2), dtype=torch.int32, device=self.device)
+            self._sizes = [(0, 0)] * n            # the host's copy of `dims` (shared with like(): one table, one copy)
+        else:
+            self.dims, self._sizes = _like.dims, _like._sizes
+        self._staging = self._dims_staging = self._copy_done = None
+
+    def like(self) -> "FrameArena":
+        return FrameArena(self.n, self.Hmax, self.Wmax, self.C, _like=self)
+
+    def size(self, b: int):
+        """(H_b, W_b) of slot b as last set(); (0, 0): empty."""
+        return self._sizes[b]
+
+    def frame(self, b: int) -> torch.Tensor:
+        H, W = self._sizes[b]
+        if H < 1:
+            raise ValueError(f"slot {b} of the arena holds no frame")
+        return self.data[b, :H * W * self.C].view(H, W, self.C)
+
+    def _checked(self, b, img):
+        """-> (flat uint8 tensor, H, W) of a frame that fits slot b; raises before anything is written."""
+        if not 0 <= b < self.n:
+            raise IndexError(f"slot {b} of an arena of {self.n}")
+        if not isinstance(img, torch.Tensor):
+            img = np.asarray(img)
+            if img.dtype != np.uint8:
+                raise TypeError(f"slot {b}: expected a uint8 [H,W,{self.C}] frame, got {img.dtype} {img.shape}")
+            img = torch.from_numpy(np.ascontiguousarray(img))
+        t = img
+        if t.dtype != torch.uint8 or t.dim() != 3:
+            raise TypeError(f"slot {b}: expected a uint8 [H,W,{self.C}] frame, got {t.dtype} {tuple(t.shape)}")
+        H, W, C = t.shape
+        if C != self.C or H < 1 or W < 1 or H > self.Hmax or W > self.Wmax:
+            raise ValueError(f"slot {b}: a frame of {H} x {W} x {C} does not fit the arena's capacity {self.Hmax} x {self.Wmax} x {self.C}")
+        return t.contiguous().reshape(-1), H, W
+
+    def _put(self, b, t, H, W):
+        nb, pinned = H * W * self.C, self.data.is_cuda and not t.is_cuda
+        if pinned and self._staging is None:
+            self._staging = torch.empty((self.n, self.slot_stride), dtype=torch.uint8).pin_memory()
+            self._dims_staging = torch.zeros((self.n, 2), dtype=torch.int32).pin_memory()
+        if pinned:
+            self._staging[b, :nb].copy_(t)
+            t = self._staging[b, :nb]
+        self.data[b, :nb].copy_(t, non_blocking=True)
+        if self._sizes[b] != (H, W):
+            rec = self._dims_staging[b] if self._dims_staging is not None else torch.empty(2, dtype=torch.int32)
+            rec[0], rec[1] = H, W
+            self.dims[b].copy_(rec, non_blocking=self._dims_staging is not None)
+            self._sizes[b] = (H, W)
+
+    def _wait(self):
+        if self._copy_done is not None:
+            self._copy_done.synchronize()          # the previous copies have left the staging arena
+            self._copy_done = None
+
+    def _guard(self):
+        return _lib.device_guard(self.device) if self.data.is_cuda else _lib._NO_GUARD
+
+    def _mark(self):
+        if self._staging is not None:
+            self._copy_done = torch.cuda.Event()
+            self._copy_done.record()
+
+    def set(self, b: int, img):
+        """One frame -> slot b (and its dims record when the size changed)."""
+        t, H, W = self._checked(b, img)
+        self._wait()
+        with self._guard():
+            self._put(b, t, H, W)
+            self._mark()
+
+    def set_all(self, imgs):
+        """n frames -> the n slots: every frame is checked before the first byte is written."""
+        if len(imgs) != self.n:
+            raise ValueError(f"this arena has {self.n} slots, got {len(imgs)} frames")
+        checked = [self._checked(b, im) for b, im in enumerate(imgs)]
+        self._wait()
+        with self._guard():
+            for b, (t, H, W) in enumerate(checked):
+                self._put(b, t, H, W)
+            self._mark()
+
+
+def _arena_on_gpu(frame):
+    if not frame.data.is_cuda:
+        raise _lib.HdnHipError("the arena must be on the GPU; there is no CPU fallback")
+
+
+def _batch(frame):
+    """Number of frames a call works on: B of [B,H,W,C], n of an arena, 1 for a single frame."""
+    if isinstance(frame, FrameArena):
+        return frame.n
+    return frame.shape[0] if frame.dim() == 4 else 1
+
+
+def is_batched(frame) -> bool:
+    """An arena or a [B,H,W,C] tensor (results carry a leading batch dimension) as opposed to one [H,W,C] frame."""
+    return isinstance(frame, FrameArena) or frame.dim() == 4
+
+
+def _arena_out(frame, out):
+    if out is None:
+        return frame.like()
+    if (not isinstance(out, FrameArena) or (out.n, out.Hmax, out.Wmax, out.C) != (frame.n, frame.Hmax, frame.Wmax, frame.C)
+            or out.dims is not frame.dims or out.device != frame.device):
+        raise ValueError("out must be an arena made by like() of the input arena")
+    return out
+
+
 def _records(t, B, width, what):
     """A float64 device array of B parameter records of `width` doubles -> (tensor to keep alive, pointer, stride in doubles).  The records
     may be a column slice of a wider per-sequence array (state[:, 8:14]): only the rows' stride has to be uniform."""
@@ -84,6 +220,18 @@ def crop_points(pos, original_sz, im_h, im_w):
 
 
 def _subwindow(frame, pos, model_sz, original_sz, avg_chans, mode, params=None):
+    if isinstance(frame, FrameArena):
+        if params is None:
+            raise ValueError("an arena of frames takes its crop parameters as a float64 device tensor [n, 3 + C] (`params`)")
+        _arena_on_gpu(frame)
+        B, C, dev, m = frame.n, frame.C, frame.device, int(model_sz)
+        keep, pp, stride = _records(params, B, 3 + C, "params")
+        out = torch.empty((B, 1 if mode else C, m, m), dtype=torch.float32, device=dev)
+        with _lib.device_guard(dev):
+            rc = _lib.load().hdn_subwindow_ragged_f32(_lib.ptr(frame.data), frame.slot_stride, _lib.ptr(frame.dims), pp, stride, _lib.ptr(out), B,
+                                                      frame.Hmax, frame.Wmax, C, m, mode, _lib.stream_ptr(dev))
+        _lib.check(rc, "get_subwindow")
+        return out
     H, W, C = _check_frame(frame)
     dev = frame.device
     B = frame.shape[0] if frame.dim() == 4 else 1
@@ -105,7 +253,8 @@ def _subwindow(frame, pos, model_sz, original_sz, avg_chans, mode, params=None):
 def get_subwindow(frame, pos, model_sz, original_sz, avg_chans, params=None, islog: int = 0):
     """-> float32 [1, C, model_sz, model_sz] (uint8-valued), on the device; islog=1 appends the C log-polar channels
     (np.concatenate((im_patch, getPolarImg(im_patch)), 2), base_tracker.py:119-126) -> [1, 2C, model_sz, model_sz].
-    A batch of frames [B,H,W,C] with `params` [B, 3 + C] gives [B, ...]: one launch, frame b cut with record b."""
+    A batch of frames [B,H,W,C] (or a FrameArena of n frames of different sizes) with `params` [B, 3 + C] gives [B, ...]: one launch,
+    frame b cut with record b."""
     out = _subwindow(frame, pos, model_sz, original_sz, avg_chans, 0, params)
     if islog == 1:
         return torch.cat([out, get_polar_img(out)], dim=1)
@@ -167,7 +316,7 @@ def get_search_info(frame, pos, original_sz, avg_chans, model_sz: int = 127, par
 def _matrices(frame, M, width, what):
     """M -> (B, keep, pointer, stride).  At B = 1 a device tensor may have any shape holding `width` values ([3, 3], [9],
     [2, 3], ...); a [1, width] row, possibly a column slice of a wider per-sequence array, is passed with its own stride."""
-    B = frame.shape[0] if frame.dim() == 4 else 1
+    B = _batch(frame)
     if isinstance(M, torch.Tensor):
         m = M
         if B == 1:
@@ -183,9 +332,25 @@ def _matrices(frame, M, width, what):
     return (B,) + _records(m, B, width, "M")
 
 
-def warp_perspective(frame, M):
+def _warp_ragged(frame, M, width, what, entry, name, out):
+    _arena_on_gpu(frame)
+    B, keep, mp, stride = _matrices(frame, M, width, what)
+    out = _arena_out(frame, out)
+    with _lib.device_guard(frame.device):
+        rc = getattr(_lib.load(), entry)(_lib.ptr(frame.data), frame.slot_stride, _lib.ptr(frame.dims), mp, stride, _lib.ptr(out.data), B,
+                                         frame.Hmax, frame.Wmax, frame.C, _lib.stream_ptr(frame.device))
+    _lib.check(rc, name)
+    return out
+
+
+def warp_perspective(frame, M, out=None):
     """cv2.warpPerspective(frame, M, (W, H), borderMode=cv2.BORDER_REPLICATE); M: 3x3 (host array or float64 device tensor).
-    A batch [B,H,W,C] takes B matrices [B, 9] (rows of a wider float64 device array are fine) and is one launch."""
+    A batch [B,H,W,C] takes B matrices [B, 9] (rows of a wider float64 device array are fine) and is one launch.
+    A FrameArena takes n matrices the same way, every slot warped at its own size, and returns an arena (`out`, or frame.like())."""
+    if isinstance(frame, FrameArena):
+        return _warp_ragged(frame, M, 9, "3x3", "hdn_frame_warp_perspective_ragged_u8", "warp_perspective", out)
+    if out is not None:
+        raise ValueError("`out` is for arenas")
     H, W, C = _check_frame(frame)
     B, keep, mp, stride = _matrices(frame, M, 9, "3x3")
     out = torch.empty_like(frame)
@@ -195,8 +360,12 @@ def warp_perspective(frame, M):
     return out
 
 
-def warp_affine_cubic(frame, M):
-    """cv2.warpAffine(frame, M, (W, H), flags=cv2.INTER_CUBIC, borderMode=cv2.BORDER_REPLICATE); M: 2x3 (a batch: [B, 6])."""
+def warp_affine_cubic(frame, M, out=None):
+    """cv2.warpAffine(frame, M, (W, H), flags=cv2.INTER_CUBIC, borderMode=cv2.BORDER_REPLICATE); M: 2x3 (a batch or an arena: [B, 6])."""
+    if isinstance(frame, FrameArena):
+        return _warp_ragged(frame, M, 6, "2x3", "hdn_frame_warp_affine_cubic_ragged_u8", "warp_affine_cubic", out)
+    if out is not None:
+        raise ValueError("`out` is for arenas")
     H, W, C = _check_frame(frame)
     B, keep, mp, stride = _matrices(frame, M, 6, "2x3")
     out = torch.empty_like(frame)

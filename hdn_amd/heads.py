@@ -125,17 +125,59 @@ def _param_versions(branches):
     return _versions(refs)
 
 
+_CACHE_ATTRS = ("_hdn_template_cache", "_hdn_packed_head", "_hdn_refs_template", "_hdn_refs_head", "_hdn_packable", "_hdn_template_pack",
+                "_hdn_search_pack")
+
+
 def invalidate_template_cache(head):
     """Drop the cached template-branch features of a MultiBAN / MultiCircBAN.  install() wraps ModelBuilder.template() so that
     every new template calls this for both heads; call it yourself after mutating weights through .data (which bypasses the
     version counters the cache is keyed on) without re-running template()."""
-    object.__setattr__(head, "_hdn_template_cache", None)
-    object.__setattr__(head, "_hdn_packed_head", None)
-    object.__setattr__(head, "_hdn_refs_template", None)
-    object.__setattr__(head, "_hdn_refs_head", None)
-    object.__setattr__(head, "_hdn_packable", None)
-    object.__setattr__(head, "_hdn_template_pack", None)
-    object.__setattr__(head, "_hdn_search_pack", None)
+    for name in _CACHE_ATTRS:
+        object.__setattr__(head, name, None)
+
+
+def template_cache_state(head):
+    """Everything invalidate_template_cache drops, to be handed back with restore_template_cache_state: a captured hipGraph reads the buffers
+    of these objects by address, so code that has to call template() between replays (a tracker slot handed a new video) keeps them alive."""
+    return tuple(getattr(head, name, None) for name in _CACHE_ATTRS)
+
+
+def restore_template_cache_state(head, state):
+    for name, v in zip(_CACHE_ATTRS, state):
+        object.__setattr__(head, name, v)
+
+
+def refresh_template_cache(head, z_fs, rows=None):
+    """After the template features `z_fs` (the tensors the last forward saw) were changed IN PLACE: recompute conv_kernel(z_f) for sample
+    `rows` (an index or a slice; None: all) and write it INTO the cache's existing buffers, then bring the cache's key up to date.
+
+    The cache is consulted by Python code, and a replayed hipGraph runs none: it keeps reading the `kern` buffers that existed at capture.
+    An eager forward would notice the version counters and recompute into NEW buffers; a replay would silently correlate against the old
+    template's features.  Same storage, same path as the forward took (the HDN_HIP_HEADS template pack where it is on, conv_kernel otherwise).
+    Without a cache (no forward yet) there is nothing to refresh: the next forward computes it."""
+    cache = getattr(head, "_hdn_template_cache", None)
+    if cache is None:
+        return False
+    z_fs = list(z_fs)
+    if len(z_fs) != len(cache.z_fs) or not all(a is b for a, b in zip(z_fs, cache.z_fs)):
+        raise ValueError("refresh_template_cache takes the template tensors the cache was computed from, changed in place")
+    n = len(z_fs)
+    sel = slice(None) if rows is None else slice(rows, rows + 1) if isinstance(rows, int) else rows
+    boxes = [getattr(head, "box" + str(i + 2)) for i in range(n)]
+    branches = [br for box in boxes for br in (box.cls, box.loc)]
+    with torch.no_grad():
+        zs = [z[sel] for z in z_fs]
+        tp = getattr(head, "_hdn_template_pack", None) if _hip_heads_on(head) else None
+        if tp is not None and tp.ok and tp.key[0] == _param_versions(branches):
+            y = head_conv_batch(zs, tp.wsp, tp.bsp)           # the pack holds weights only: it serves any batch
+            new = [y[l, g] for l in range(n) for g in range(2)]
+        else:
+            new = [br.conv_kernel(z) for box, z in zip(boxes, zs) for br in (box.cls, box.loc)]
+        for dst, src in zip(cache.kern, new):
+            dst[sel].copy_(src)
+    cache.z_versions = tuple(z._version for z in z_fs)
+    return True
 
 
 _HIP_HEADS = None

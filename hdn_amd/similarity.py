@@ -165,8 +165,8 @@ class DeviceSimilarity:
         channel_average [B,3]; the model then holds B templates (its zf has batch B) and every per-frame call runs at batch B."""
         dev = frame.device
         dec = self.decoder(dev)
-        if frame.dim() == 4:
-            B = frame.shape[0]
+        if FR.is_batched(frame):          # [B,H,W,3], or a FrameArena of B frames of different sizes
+            B = FR._batch(frame)
             pos, sz, szs, avg = (np.asarray(a, np.float64) for a in (init_pos, init_s_z, init_s_z_sm, channel_average))
             if pos.shape != (B, 2) or sz.shape != (B,) or szs.shape != (B,) or avg.shape != (B, 3):
                 raise ValueError(f"a batch of {B} sequences takes init_pos [{B},2], init_s_z / init_s_z_sm [{B}], channel_average [{B},3]")
@@ -176,7 +176,7 @@ class DeviceSimilarity:
             B = 1
             host = sequence_constants(init_pos, init_s_z, init_s_z_sm, channel_average, self.cfg).reshape(1, -1)
             tparams = None
-        self.batch, self.batched = B, frame.dim() == 4
+        self.batch, self.batched = B, FR.is_batched(frame)
         self.seq = torch.from_numpy(host).to(dev)
         if not self.batched:
             self.seq = self.seq.reshape(-1)
@@ -193,13 +193,51 @@ class DeviceSimilarity:
             self.model.template(z_crop)
         return z_crop
 
+    def reinit(self, slot, frame, init_pos, init_s_z, init_s_z_sm, channel_average):
+        """init() for ONE sequence of a batch, written in place into row `slot` of seq / _params0 / state and of the model's template features;
+        no other row is touched and no tensor is replaced, so a captured hipGraph goes on replaying (hdn_amd.batched_tracker.reinit).
+        frame: that sequence's first frame, uint8 [H,W,3] on the device.
+
+        The template is computed at batch 1 by the model's own template(), copied into row `slot` of the tensors the batch's template() left
+        on the model (zf / zf_lp, model_builder_e2e_unconstrained_v2.py:95-96), and those attributes are put back; so is what install()'s
+        template() wrapper drops from the heads (a replayed graph reads those buffers by address).  The heads' cached template-branch features
+        are then refreshed in place (heads.refresh_template_cache) - also where HDN_HIP_HEADS computes them with its template pack."""
+        from . import heads as HD
+        if self.seq is None or not getattr(self, "batched", False):
+            raise RuntimeError("reinit() re-initialises one sequence of a batch: call init() with a batch of frames first")
+        if not 0 <= slot < self.batch:
+            raise IndexError(f"slot {slot} of {self.batch} sequences")
+        dev, m = frame.device, self.model
+        rec = sequence_constants(init_pos, init_s_z, init_s_z_sm, channel_average, self.cfg)
+        self.seq[slot].copy_(torch.from_numpy(rec))
+        self._params0[slot].copy_(torch.from_numpy(np.ascontiguousarray(rec[[0, 1, 3, 5, 6, 7]])))
+        self.state[slot].zero_()
+        z_crop, _ = FR.get_subwindow_for_homo(frame, init_pos, self.cfg.exemplar_size, init_s_z, channel_average, islog=1)
+        zf, zf_lp = m.zf, m.zf_lp
+        heads = [(getattr(m, name), z) for name, z in (("head", zf), ("head_lp", zf_lp)) if hasattr(m, name)]
+        kept = [HD.template_cache_state(h) for h, _ in heads]
+        try:
+            with torch.no_grad():
+                m.template(z_crop)
+                for dst, src in ((zf, m.zf), (zf_lp, m.zf_lp)):
+                    dst, src = (dst, src) if isinstance(dst, (list, tuple)) else ([dst], [src])
+                    for d, t in zip(dst, src):
+                        d[slot:slot + 1].copy_(t)
+        finally:
+            m.zf, m.zf_lp = zf, zf_lp
+            for (h, _), k in zip(heads, kept):
+                HD.restore_template_cache_state(h, k)
+        for h, z in heads:
+            HD.refresh_template_cache(h, z if isinstance(z, (list, tuple)) else [z], slot)
+        return z_crop
+
     def __call__(self, frame):
         if self.seq is None:
             raise RuntimeError("DeviceSimilarity.init() has not been called for this sequence")
         c, dec = self.cfg, self.decoder(frame.device)
         B, batched = getattr(self, "batch", 1), getattr(self, "batched", False)
-        if (frame.shape[0] if frame.dim() == 4 else 1) != B or batched != (frame.dim() == 4):
-            raise ValueError(f"init() was given {B} sequence(s); this call has {frame.shape[0] if frame.dim() == 4 else 1}")
+        if FR._batch(frame) != B or batched != FR.is_batched(frame):
+            raise ValueError(f"init() was given {B} sequence(s); this call has {FR._batch(frame)}")
         seq = self.seq.view(B, -1)
         # 1. translation (:164-186)
         x_crop = FR.get_subwindow(frame, None, c.instance_size, None, None, params=self._params0)

@@ -238,6 +238,24 @@ int hdn_frame_warp_perspective_batch_u8(const unsigned char* src, const double* 
                                         void* stream);
 int hdn_frame_warp_affine_cubic_batch_u8(const unsigned char* src, const double* M, int m_stride, unsigned char* dst, int B, int H, int W, int C,
                                          void* stream);
+/*
+ * The three calls for B frames of DIFFERENT sizes (the videos of a dataset streamed through the slots of the lock-step tracker; the
+ * reference's tools/test.py:91-103 splits such a list by hand across processes, one video at a time in each).  frames / src / dst: an arena
+ * of B slots `slot_stride` bytes apart (>= Hmax * Wmax * C), slot b holding a dense [H_b, W_b, C] frame at its start; dims: DEVICE int32
+ * [B][2] = (H_b, W_b).  The sizes are data, not launch arguments, so a captured hipGraph keeps replaying while slots change their frame
+ * size.  The grid is sized from the capacity (Hmax, Wmax); every workgroup reads its slot's record and runs the single-frame loop over its
+ * own H_b * W_b, with the perspective warp's block width (OpenCV's summation order of x) and the bounds of the 4-byte loads taken from
+ * the slot's own size.  params / M / out (crops, contiguous [B, ...]) as in the batch calls.  Per slot bit-identical to the single-frame
+ * call on that slot's frame.  The host cannot see dims: a slot whose record has H < 1, W < 1, H > Hmax, W > Wmax or H * W * C >
+ * slot_stride is skipped (nothing of it read, nothing written for it), and the bytes of a slot beyond H_b * W_b * C are never written.
+ * HDN_E_SHAPE also for slot_stride < Hmax * Wmax * C; HDN_E_ALIAS when the two arenas (the arena and the crops) overlap anywhere.
+ */
+int hdn_subwindow_ragged_f32(const unsigned char* frames, long long slot_stride, const int* dims, const double* params, int params_stride,
+                             float* out, int B, int Hmax, int Wmax, int C, int model_sz, int mode, void* stream);
+int hdn_frame_warp_perspective_ragged_u8(const unsigned char* src, long long slot_stride, const int* dims, const double* M, int m_stride,
+                                         unsigned char* dst, int B, int Hmax, int Wmax, int C, void* stream);
+int hdn_frame_warp_affine_cubic_ragged_u8(const unsigned char* src, long long slot_stride, const int* dims, const double* M, int m_stride,
+                                          unsigned char* dst, int B, int Hmax, int Wmax, int C, void* stream);
 int hdn_remap_linear_f32(const float* src, const float* mapx, const float* mapy, float* dst, int C, int Hs, int Ws, int Hd, int Wd,
                          void* stream);
 
