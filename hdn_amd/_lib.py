@@ -54,6 +54,7 @@ SIGNATURES = {
     "hdn_similarity_translation_f32": (_i, [_c_float_p] * 6 + [_i, _i, ctypes.c_double, ctypes.c_float, ctypes.c_double, _i, ctypes.c_void_p]),
     "hdn_similarity_logpolar_f32": (_i, [_c_float_p] * 5 + [_i, _i, ctypes.c_float, ctypes.c_double, ctypes.c_float, _i, ctypes.c_void_p]),
     "hdn_simi_track_update_f64": (_i, [_c_float_p] * 4 + [_i, _i, _i, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_void_p]),
+    "hdn_simi_track_update_ragged_f64": (_i, [_c_float_p] * 5 + [_i, _i, _i, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_void_p]),
     "hdn_track_prepare_f64": (_i, [_c_float_p] * 3 + [_i, ctypes.c_void_p]),
     "hdn_track_accumulate_f64": (_i, [_c_float_p] * 6 + [_i] + [_c_float_p] * 2 + [_i, ctypes.c_void_p]),
     "hdn_trunk_stem_f32": (_i, [_c_float_p] * 4 + [_i] * 4 + [ctypes.c_void_p]),

@@ -366,7 +366,8 @@ def track_videos(tracker, videos, on_result=None):
     -> list, in input order, of per-video lists of track_new's dictionaries (one per frame after the first); with on_result, that is called as
     on_result(video_index, frame_index, result) instead and the lists stay empty.
     Plain scheduling over tracker.n / init / track_new / reinit (and tracker.frame_capacity where it has one: a video whose first frame is
-    above it raises before anything is launched)."""
+    above it raises before anything is launched).  So it serves the similarity-only hdn_amd.simi_tracker.BatchedSimiTracker(model, n,
+    frame_capacity=...) as well, whose init reads the last list as the first_points: every video's init then needs its 'first_point'."""
     n = tracker.n
     cap = getattr(tracker, "frame_capacity", None)
     queue = []

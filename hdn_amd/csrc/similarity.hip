@@ -163,12 +163,11 @@ __device__ __forceinline__ void wrap_2pi(double& v, double is_f32, double sign) 
   v = is_f32 != 0.0 ? (double)rn_sub((float)v, (float)(sign * two_pi)) : v - sign * two_pi;
 }
 
-__global__ __launch_bounds__(HDN_WAVE) void simi_track_update_kernel(const double* __restrict__ state, double* __restrict__ tr,
-                                                                     double* __restrict__ seq, double* __restrict__ out, int B, double img_w,
-                                                                     double img_h, double scale_score_thresh, double context_amount,
-                                                                     double ratio) {
-  const int b = blockIdx.x * HDN_WAVE + threadIdx.x;
-  if (b >= B) return;
+// (one body for both kernels: lane b of a batch whose frames have one size - img_w / img_h launch arguments - and of the slots of an arena, each
+// with its own frame size read from device memory)
+__device__ __forceinline__ void simi_track_update_body(const double* __restrict__ state, double* __restrict__ tr, double* __restrict__ seq,
+                                                       double* __restrict__ out, int b, double img_w, double img_h, double scale_score_thresh,
+                                                       double context_amount, double ratio) {
   const double* S = state + size_t(b) * HDN_SIM_STATE_DOUBLES;
   double* T = tr + size_t(b) * HDN_SIMI_TRACK_DOUBLES;
   double* O = out + size_t(b) * HDN_SIMI_OUT_DOUBLES;
@@ -239,6 +238,28 @@ __global__ __launch_bounds__(HDN_WAVE) void simi_track_update_kernel(const doubl
   double* q = seq + size_t(b) * HDN_SIM_SEQ_DOUBLES;
   q[0] = cx; q[1] = cy; q[2] = s_z; q[3] = s_x; q[4] = 0.0; q[5] = T[20]; q[6] = T[21]; q[7] = T[22];
   T[24] = cx; T[25] = cy; T[26] = s_x; T[27] = T[20]; T[28] = T[21]; T[29] = T[22];
+}
+
+__global__ __launch_bounds__(HDN_WAVE) void simi_track_update_kernel(const double* __restrict__ state, double* __restrict__ tr,
+                                                                     double* __restrict__ seq, double* __restrict__ out, int B, double img_w,
+                                                                     double img_h, double scale_score_thresh, double context_amount,
+                                                                     double ratio) {
+  const int b = blockIdx.x * HDN_WAVE + threadIdx.x;
+  if (b >= B) return;
+  simi_track_update_body(state, tr, seq, out, b, img_w, img_h, scale_score_thresh, context_amount, ratio);
+}
+
+// The slots of an arena (hdn_amd.frame.FrameArena): lane b clamps at ITS frame, dims[b] = (H_b, W_b) in device memory, so a captured hipGraph
+// holds no frame size.  A record that does not fit the capacity is skipped as the ragged frame kernels skip it (slot_dims, frame.hip).
+__global__ __launch_bounds__(HDN_WAVE) void simi_track_update_ragged_kernel(const double* __restrict__ state, double* __restrict__ tr,
+                                                                            double* __restrict__ seq, double* __restrict__ out,
+                                                                            const int* __restrict__ dims, int B, int Hmax, int Wmax,
+                                                                            double scale_score_thresh, double context_amount, double ratio) {
+  const int b = blockIdx.x * HDN_WAVE + threadIdx.x;
+  if (b >= B) return;
+  const int H = dims[2 * b], W = dims[2 * b + 1];
+  if (H < 1 || W < 1 || H > Hmax || W > Wmax) return;
+  simi_track_update_body(state, tr, seq, out, b, (double)W, (double)H, scale_score_thresh, context_amount, ratio);
 }
 
 // ---- the tracker's 3x3 bookkeeping (hdn_tracker_proj_e2e.py:150-155 and :251-272), one lane per sequence ----------------------
@@ -347,6 +368,16 @@ extern "C" int hdn_simi_track_update_f64(const double* state, double* tr, double
   if (B <= 0 || img_w <= 0 || img_h <= 0 || !(instance_exemplar_ratio > 0)) return HDN_E_SHAPE;
   hipLaunchKernelGGL(hdn::simi_track_update_kernel, dim3(hdn::cdiv(B, HDN_WAVE)), dim3(HDN_WAVE), 0, (hipStream_t)stream, state, tr, seq, out, B,
                      (double)img_w, (double)img_h, scale_score_thresh, context_amount, instance_exemplar_ratio);
+  return hdn::launch_status();
+}
+
+extern "C" int hdn_simi_track_update_ragged_f64(const double* state, double* tr, double* seq, double* out, const int* dims, int B, int Hmax,
+                                                int Wmax, double scale_score_thresh, double context_amount, double instance_exemplar_ratio,
+                                                void* stream) {
+  if (!state || !tr || !seq || !out || !dims) return HDN_E_NULL;
+  if (B <= 0 || Hmax <= 0 || Wmax <= 0 || !(instance_exemplar_ratio > 0)) return HDN_E_SHAPE;
+  hipLaunchKernelGGL(hdn::simi_track_update_ragged_kernel, dim3(hdn::cdiv(B, HDN_WAVE)), dim3(HDN_WAVE), 0, (hipStream_t)stream, state, tr, seq,
+                     out, dims, B, Hmax, Wmax, scale_score_thresh, context_amount, instance_exemplar_ratio);
   return hdn::launch_status();
 }
 

@@ -19,6 +19,10 @@ host read of 20 doubles — or none (`sync=False`).  The networks are the model'
 around the HIP correlations).  Template features live in static buffers that the refresh overwrites in place, so a frame replays as one
 hipGraph (`graph=True`) and the heads' template cache sees the change through the tensors' version counters.
 
+BatchedSimiTracker runs n sequences in lock step; with frame_capacity=(Hmax, Wmax) every slot has its own frame size (the update kernel's
+clamps read it from device memory: hdn_simi_track_update_ragged_f64), reinit(slot, ...) starts a new video in a slot in place, and
+hdn_amd.track_videos streams a dataset through the slots under one captured hipGraph.
+
 Signatures: the reference's launchers call `init(img, bbox, poly, gt_points, first_point)` / `track_new(idx, img, bbox, poly, gt_points)`
 (tools/test.py:130,153) — one argument more than hdnTracker's own methods take; both spellings are accepted here.
 """
@@ -93,6 +97,7 @@ class SimiTracker:
         self.scale_score_thresh = float(scale_score_thresh)
         self.host_syncs = 0
         self._zf_static = None
+        self._kern_in_graph = True      # (set by _capture: did the heads recompute their template-branch features inside the captured graph?)
         self.n = 1          # sequences advanced per call (BatchedSimiTracker: n > 1)
 
     # -------------------------------------------------------------------------------------------------- template (init + refresh)
@@ -192,14 +197,30 @@ class SimiTracker:
         with torch.no_grad():
             o = m.track_new_lp(x_moved, [0, 0])
         dec.logpolar(o["cls_lp"], o["loc_lp"], self.seq, self.state)                                                  # :241-246
-        with _lib.device_guard(self.dev):                                                                             # :213-227, :247-283 and the next :176-188
-            _lib.check(_lib.load().hdn_simi_track_update_f64(_lib.ptr(self.state), _lib.ptr(self.track), _lib.ptr(self.seq), _lib.ptr(self._out), self.n,
-                                                             self.frame_hw[1], self.frame_hw[0], self.scale_score_thresh, c.context_amount, self.ratio,
-                                                             _lib.stream_ptr(self.dev)), "simi track update")
-        rot_img = FR.warp_affine_cubic(self.init_frame, self.track[:, 32:38])                                          # update_template, :156-162
+        self._update()                                                                                                # :213-227, :247-283 and the next :176-188
+        rot_img = self._rotated_first()                                                                               # update_template, :156-162
         z_crop = FR.get_subwindow(rot_img, None, c.exemplar_size, None, None, params=self.track[:, 40:46], islog=1)
         self._template(z_crop)
         return self._out
+
+    def _update(self):
+        c = self.cfg
+        with _lib.device_guard(self.dev):
+            _lib.check(_lib.load().hdn_simi_track_update_f64(_lib.ptr(self.state), _lib.ptr(self.track), _lib.ptr(self.seq), _lib.ptr(self._out), self.n,
+                                                             self.frame_hw[1], self.frame_hw[0], self.scale_score_thresh, c.context_amount, self.ratio,
+                                                             _lib.stream_ptr(self.dev)), "simi track update")
+
+    def _rotated_first(self):
+        return FR.warp_affine_cubic(self.init_frame, self.track[:, 32:38])
+
+    def _head_caches(self):
+        """The template-branch caches of the model's heads (hdn_amd.heads; None where a head has none)."""
+        return [getattr(getattr(self.model, name), "_hdn_template_cache", None) for name in ("head", "head_lp") if hasattr(self.model, name)]
+
+    def _static_input(self, frame_shape):
+        frame = torch.empty(frame_shape, dtype=torch.uint8, device=self.dev)
+        frame.copy_(self.init_frame)
+        return frame
 
     def _snapshot(self):
         return [self.track.clone(), self.seq.clone(), self.state.clone()] + [t.clone() for f in self._zf_static for t in (f if isinstance(f, list) else [f])]
@@ -212,8 +233,7 @@ class SimiTracker:
     def _capture(self, frame_shape):
         """One hipGraph for the whole body.  The warm-up / capture runs advance the recurrences and refresh the template: everything they
         touched is put back afterwards (track record, seq, state, template features)."""
-        self._static_frame = torch.empty(frame_shape, dtype=torch.uint8, device=self.dev)
-        self._static_frame.copy_(self.init_frame)
+        self._static_frame = self._static_input(frame_shape)
         snap = self._snapshot()
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
@@ -224,7 +244,11 @@ class SimiTracker:
             torch.cuda.current_stream().wait_stream(side)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
+                before = self._head_caches()
                 self._g_out = self._body(self._static_frame)
+                # (the refresh of the step before changed the template tensors in place, so the heads recomputed their template-branch
+                # features INSIDE the capture: they are nodes of the graph and follow the template on every replay)
+                self._kern_in_graph = all(b is None or b is not a for a, b in zip(before, self._head_caches()))
             self._graph = graph
         finally:
             torch.cuda.current_stream().wait_stream(side)
@@ -276,12 +300,25 @@ class BatchedSimiTracker(SimiTracker):
     the rotation of the resident first frames (blockIdx.y = sequence, per-sequence records read out of the [n, 48] arrays), the two decodes, the update
     kernel — and the model's own forward code is batch-general (n templates, refreshed in place every step).  One step = one upload of [n,H,W,3], one
     hipGraph replay, one host read of [n, 20].  Sequence b of a batch runs exactly the code it runs alone: tests/test_gpu_simi_tracker.py holds every
-    sequence to its own B = 1 run and to the CPU loop."""
+    sequence to its own B = 1 run and to the CPU loop.
 
-    def __init__(self, model, n: int, cfg: TrackerConfig = None, graph: bool = False, scale_score_thresh: float = 0.5, batch_template: bool = None):
+    frame_capacity=(Hmax, Wmax): arena mode, as in hdn_amd.batched_tracker.  The frames live in a hdn_amd.frame.FrameArena, every slot at its own
+    size, and so do the resident first frames (a second arena sharing the size table: a slot's video has one size); the crops, the rotation and
+    the update kernel's clamps (hdn_simi_track_update_ragged_f64) read each slot's size from device memory, so the captured hipGraph goes on
+    replaying while reinit(slot, ...) hands a slot a new video of another size.  track_videos(tracker, videos) schedules a dataset through
+    the slots.  init / track_new then take LISTS of n frames."""
+
+    def __init__(self, model, n: int, cfg: TrackerConfig = None, graph: bool = False, scale_score_thresh: float = 0.5, batch_template: bool = None,
+                 frame_capacity=None):
         super().__init__(model, cfg=cfg, graph=graph, scale_score_thresh=scale_score_thresh, batch_template=batch_template)
         if n < 1:
             raise ValueError("n must be >= 1")
+        self.frame_capacity = None
+        if frame_capacity is not None:
+            self.frame_capacity = (int(frame_capacity[0]), int(frame_capacity[1]))
+            if min(self.frame_capacity) < 1:
+                raise ValueError("frame_capacity must be (Hmax, Wmax) >= 1")
+        self._arena = self._first = self._rotated = None      # arena mode: this step's frames, the first frames, their rotation
         self.n = int(n)
         self._staging = self._copy_done = None
 
@@ -299,11 +336,27 @@ class BatchedSimiTracker(SimiTracker):
             raise ValueError(f"init takes {n} bboxes / polys / first_points")
         self.dev = next(self.model.parameters()).device
         self.ratio = float(np.round(c.instance_size / c.exemplar_size))
-        frames = self._upload(imgs)
-        self.init_frame = frames.clone()                              # update_template rotates THESE frames, every step
-        self.channel_average = frames.to(torch.float64).mean(dim=(1, 2)).cpu().numpy()
+        if self.frame_capacity is not None:      # arena mode: first frames of different sizes
+            for b, fp in enumerate(first_points):
+                if fp is None:
+                    raise ValueError(f"slot {b}: the similarity tracker needs the sequence's first_point (the first ground-truth corner)")
+            if not torch.cuda.is_available():
+                raise _lib.HdnHipError("hdn_amd runs on the GPU only; there is no CPU fallback")
+            arena = FR.FrameArena(n, self.frame_capacity[0], self.frame_capacity[1], 3, device=self.dev)
+            self._upload_arena(imgs, same_size=False, arena=arena)
+            frames = self._arena = arena
+            self._first = arena.like()                                # update_template rotates THESE frames, every step
+            self._rotated = arena.like()
+            for b in range(n):
+                self._first.frame(b).copy_(arena.frame(b))
+            self.channel_average = torch.stack([arena.frame(b).to(torch.float64).mean(dim=(0, 1)) for b in range(n)]).cpu().numpy()
+            self.frame_hw = [arena.size(b) for b in range(n)]         # per slot
+        else:
+            frames = self._upload(imgs)
+            self.init_frame = frames.clone()                              # update_template rotates THESE frames, every step
+            self.channel_average = frames.to(torch.float64).mean(dim=(1, 2)).cpu().numpy()
+            self.frame_hw = (int(frames.shape[1]), int(frames.shape[2]))
         self.host_syncs += 1
-        self.frame_hw = (int(frames.shape[1]), int(frames.shape[2]))
         recs = [sequence_records(polys[b], first_points[b], self.channel_average[b], c) for b in range(n)]
         self.track = torch.from_numpy(np.stack([r[0] for r in recs])).to(self.dev).contiguous()
         self.seq = torch.from_numpy(np.stack([r[1] for r in recs])).to(self.dev).contiguous()
@@ -316,9 +369,83 @@ class BatchedSimiTracker(SimiTracker):
         self._template(z_crop, first=True)
         return z_crop
 
+    def _upload_arena(self, imgs, same_size: bool, arena=None):
+        from .batched_tracker import BatchedHomoTracker
+        if arena is not None:                    # (init: the tracker's arena is replaced only once every frame was accepted)
+            if isinstance(imgs, torch.Tensor) or len(imgs) != self.n:
+                raise ValueError(f"this tracker advances {self.n} sequences per step and takes a list of {self.n} frames (each of its slot's size)")
+            return arena.set_all(imgs)
+        return BatchedHomoTracker._upload_arena(self, imgs, same_size)      # (the same checks: a running slot keeps its frame size)
+
+    # -------------------------------------------------------------------------------------------------- arena mode: the parts of a step that see frame sizes
+    def _update(self):
+        if self._arena is None:
+            return super()._update()
+        c, a = self.cfg, self._arena
+        with _lib.device_guard(self.dev):
+            _lib.check(_lib.load().hdn_simi_track_update_ragged_f64(_lib.ptr(self.state), _lib.ptr(self.track), _lib.ptr(self.seq), _lib.ptr(self._out),
+                                                                    _lib.ptr(a.dims), self.n, a.Hmax, a.Wmax, self.scale_score_thresh, c.context_amount,
+                                                                    self.ratio, _lib.stream_ptr(self.dev)), "simi track update (ragged)")
+
+    def _rotated_first(self):
+        if self._arena is None:
+            return super()._rotated_first()
+        return FR.warp_affine_cubic(self._first, self.track[:, 32:38], out=self._rotated)
+
+    def _static_input(self, frame_shape):
+        # (arena mode: the arena IS the static input - its slots hold the sequences' latest frames, their sizes are device data; the first frames
+        # are not copied over them)
+        return self._arena if self._arena is not None else super()._static_input(frame_shape)
+
+    def reinit(self, slot: int, img, bbox, poly, gt_points, first_point=None):
+        """What init does for ONE sequence, written in place into row `slot` of track / seq / state / the result buffer, of every level of the
+        static template buffers (model.zf / zf_lp) and of both arenas: the slot starts a new video (of any frame size up to the capacity) while the
+        other slots keep going.  No other row is touched, no tensor is replaced and the captured hipGraph is kept.  Arena mode only.  One host read
+        (the first frame's channel average).  The slot's template is computed at batch 1 by the form init chose for this model (one backbone pass
+        over both crops, or the model's own template())."""
+        from . import heads as HD
+        if self._arena is None:
+            raise RuntimeError("reinit() needs arena mode (frame_capacity=(Hmax, Wmax)) and an init() before it")
+        if not 0 <= slot < self.n:
+            raise IndexError(f"slot {slot} of {self.n}")
+        if first_point is None:
+            raise ValueError(f"slot {slot}: the similarity tracker needs the sequence's first_point (the first ground-truth corner)")
+        c, m = self.cfg, self.model
+        self._arena.set(slot, img)                   # (raises for a frame above the capacity, before anything is written)
+        frame = self._arena.frame(slot)
+        self._first.frame(slot).copy_(frame)         # (the size table is shared)
+        avg = frame.to(torch.float64).mean(dim=(0, 1)).cpu().numpy()
+        self.host_syncs += 1
+        tr, sq, self.poly_shift_l[slot], self.init_s_z[slot] = sequence_records(poly, first_point, avg, c)
+        self.channel_average[slot], self.frame_hw[slot] = avg, self._arena.size(slot)
+        self.track[slot].copy_(torch.from_numpy(tr))
+        self.seq[slot].copy_(torch.from_numpy(sq))
+        self.state[slot].zero_()
+        self._out[slot].zero_()
+        z_crop = FR.get_subwindow(frame, None, c.exemplar_size, None, None, params=self.track[slot:slot + 1, 40:46], islog=1)
+        # the model's own template() reassigns zf / zf_lp and, behind install(), drops what the heads cached: a replayed graph reads both by address
+        heads = [getattr(m, name) for name in ("head", "head_lp") if hasattr(m, name)]
+        kept = [HD.template_cache_state(h) for h in heads]
+        try:
+            new = self._template_features(z_crop)
+            for dst, src in zip(self._zf_static, new):
+                for d, t in zip(*((dst, src) if isinstance(dst, list) else ([dst], [src]))):
+                    d[slot:slot + 1].copy_(t)
+        finally:
+            m.zf, m.zf_lp = self._zf_static
+            for h, k in zip(heads, kept):
+                HD.restore_template_cache_state(h, k)
+        if self._graph is not None and not self._kern_in_graph:
+            # (the capture found the heads' template-branch features cached, outside the graph: a replay reads those buffers, so bring the row up to date)
+            for h, z in zip(heads, self._zf_static):
+                HD.refresh_template_cache(h, z if isinstance(z, list) else [z], slot)
+        return z_crop
+
     def track_new(self, fr_idx, imgs, gt_box=None, gt_poly=None, gt_points=None, sync: bool = True):
         """One frame of every sequence -> n result dictionaries with hdnTracker.track_new's keys (sync=True: one host read for all), or the float64 device
-        records [n, 20] (sync=False)."""
+        records [n, 20] (sync=False).  Arena mode: a list of n frames, each of its slot's current size."""
+        if self.frame_capacity is not None:
+            return self._track_new_arena(fr_idx, imgs, sync)
         n = self.n
         shape = tuple(imgs.shape) if isinstance(imgs, torch.Tensor) else (len(imgs),) + tuple(np.asarray(imgs[0]).shape)
         if shape[0] != n or tuple(shape[1:3]) != self.frame_hw:
@@ -337,12 +464,35 @@ class BatchedSimiTracker(SimiTracker):
             out = self._g_out
         else:
             out = self._body(self._upload(imgs))
+        return self._results(out, sync)
+
+    def _results(self, out, sync):
         if not sync:
             return {"record": out.clone()}
         h = out.cpu().numpy()
         self.host_syncs += 1
         return [{"bbox": list(h[b, 0:4]), "bbox_aligned": list(h[b, 4:8]), "best_score": np.float32(h[b, 8]), "rot": h[b, 9],
-                 "polygon": h[b, 10:18].reshape(4, 2).copy()} for b in range(n)]
+                 "polygon": h[b, 10:18].reshape(4, 2).copy()} for b in range(self.n)]
+
+    def _track_new_arena(self, fr_idx, imgs, sync):
+        if self._arena is None:
+            raise RuntimeError("track_new() before init()")
+        if not isinstance(imgs, torch.Tensor):
+            imgs = [im if isinstance(im, torch.Tensor) else np.asarray(im) for im in imgs]
+        self._upload_arena(imgs, same_size=True)              # (before a first capture too: a refused step leaves nothing half done)
+        if self.use_graph and self._graph is None:
+            try:
+                self._capture(None)
+            except RuntimeError as e:
+                import warnings
+                warnings.warn(f"hdn_amd: the batched per-frame body could not be captured as a hipGraph ({type(e).__name__}: {e}); running it eagerly")
+                self.use_graph, self._graph = False, None
+        if self._graph is not None:
+            self._graph.replay()
+            out = self._g_out
+        else:
+            out = self._body(self._arena)
+        return self._results(out, sync)
 
     def track_state(self) -> list:
         t = self.track.cpu().numpy()

@@ -316,6 +316,17 @@ int hdn_similarity_logpolar_f32(const float* cls_lp, const float* loc_lp, const 
 #define HDN_SIMI_OUT_DOUBLES 20
 int hdn_simi_track_update_f64(const double* state, double* tr, double* seq, double* out, int B, int img_w, int img_h, double scale_score_thresh,
                               double context_amount, double instance_exemplar_ratio, void* stream);
+/*
+ * hdn_simi_track_update_ragged_f64: the same lines for the B slots of an arena of frames of DIFFERENT sizes (the hdn_*_ragged_* frame calls above;
+ * hdn_amd.simi_tracker.BatchedSimiTracker with frame_capacity).  dims: DEVICE int32 [B][2] = (H_b, W_b), the table those calls read - mind
+ * the order: lane b clamps at img_h = H_b, img_w = W_b.  The frame size is data, not a launch argument, so a captured hipGraph goes on
+ * replaying while a slot is handed a video of another size.  Everything else is hdn_simi_track_update_f64 (one device function is the body
+ * of both kernels): per slot bit-identical to that call on the slot's rows with (img_w, img_h) = (W_b, H_b).  The host cannot see dims: a
+ * slot whose record has H < 1, W < 1, H > Hmax or W > Wmax is skipped, nothing of its tr / seq / out row read or written.
+ * HDN_E_NULL for any null pointer (dims too); HDN_E_SHAPE for B <= 0, Hmax <= 0, Wmax <= 0 or a ratio that is not > 0.
+ */
+int hdn_simi_track_update_ragged_f64(const double* state, double* tr, double* seq, double* out, const int* dims, int B, int Hmax, int Wmax,
+                                     double scale_score_thresh, double context_amount, double instance_exemplar_ratio, void* stream);
 
 /*
  * The tracker's 3x3 float64 bookkeeping, one lane per sequence (BASELINE configs[3]): the numpy lines of
