@@ -28,16 +28,18 @@ are dropped).
 """
 from __future__ import annotations
 
-import os
+import dataclasses
 
 import numpy as np
 import torch
 
 from . import _lib
 from . import frame as FR
+from ._loop import (FrameUploader, capture_graph, env_flag, find_mode, homography_result, prepare_model, reference_config, upload_arena,
+                    validate_frame_capacity)
 from .refine import homo_refine
 from .similarity import DeviceSimilarity, TrackerConfig
-from .tracker import TRACK_CONST_DOUBLES
+from .tracker import _const_row, _geometry, attach_hip_trunk
 
 
 class BatchedHomoTracker:
@@ -49,93 +51,16 @@ class BatchedHomoTracker:
         that capacity, and reinit() is available."""
         if n < 1:
             raise ValueError("n must be >= 1")
-        self.frame_capacity = None
-        if frame_capacity is not None:
-            self.frame_capacity = (int(frame_capacity[0]), int(frame_capacity[1]))
-            if min(self.frame_capacity) < 1:
-                raise ValueError("frame_capacity must be (Hmax, Wmax) >= 1")
+        self.frame_capacity = validate_frame_capacity(frame_capacity)
         self._arena = None
         self.net, self.n = hm_net, int(n)
         self.cfg = cfg or (similarity.cfg if similarity is not None and hasattr(similarity, "cfg") else TrackerConfig())
         self.use_graph, self._graph = bool(graph), None
         self.iterations, self.similarity, self.score_gate = int(iterations), similarity, float(score_gate)
         self.host_syncs = 0
-        self._staging = self._copy_done = None
-
-    # ------------------------------------------------------------------------------------------------ frames: one upload per step
-    def _upload(self, imgs, into=None):
-        """n frames -> uint8 device tensor [n,H,W,3].  A list of numpy frames goes through ONE pinned staging buffer and one
-        asynchronous copy; a stacked uint8 tensor (pageable, pinned or already on the device) is copied / used as it is."""
-        n = self.n
-        if isinstance(imgs, torch.Tensor):
-            t = imgs
-            if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[0] != n:
-                raise TypeError(f"expected a uint8 [{n},H,W,C] tensor of frames, got {t.dtype} {tuple(t.shape)}")
-        else:
-            if len(imgs) != n:
-                raise ValueError(f"this tracker advances {n} sequences per step, got {len(imgs)} frames")
-            a0 = np.asarray(imgs[0])
-            if a0.dtype != np.uint8 or a0.ndim != 3:
-                raise TypeError(f"expected uint8 [H,W,C] frames, got {a0.dtype} {a0.shape}")
-            shape = (n,) + a0.shape
-            if self._staging is None or tuple(self._staging.shape) != shape:
-                self._staging = torch.empty(shape, dtype=torch.uint8).pin_memory()
-                self._copy_done = None
-            if self._copy_done is not None:
-                self._copy_done.synchronize()          # the previous step's copy has left the staging buffer
-            host = self._staging.numpy()
-            for b, im in enumerate(imgs):
-                im = np.asarray(im)
-                if im.shape != a0.shape or im.dtype != np.uint8:
-                    raise ValueError(f"all frames of a step must be uint8 {a0.shape} (they share one buffer); frame {b} is {im.dtype} {im.shape}")
-                host[b] = im
-            t = self._staging
-        if not torch.cuda.is_available():
-            raise _lib.HdnHipError("hdn_amd runs on the GPU only; there is no CPU fallback")
-        if into is not None:
-            if tuple(t.shape) != tuple(into.shape):
-                raise ValueError(f"graph mode was captured for uint8 frames of shape {tuple(into.shape)}, got {tuple(t.shape)}")
-            into.copy_(t, non_blocking=True)
-            dst = into
-        else:
-            dst = t.contiguous() if t.is_cuda else t.contiguous().to(self.dev, non_blocking=True)
-        if t is self._staging:
-            self._copy_done = torch.cuda.Event()
-            self._copy_done.record()
-        return dst
-
-    def _upload_arena(self, imgs, same_size: bool):
-        """n frames -> the arena's slots (arena mode); same_size: every frame must have its slot's current size (a step of running sequences)."""
-        n = self.n
-        if isinstance(imgs, torch.Tensor) or len(imgs) != n:
-            raise ValueError(f"this tracker advances {n} sequences per step and takes a list of {n} frames (each of its slot's size)")
-        if same_size:
-            for b, im in enumerate(imgs):
-                if tuple(im.shape[:2]) != self._arena.size(b):
-                    raise ValueError(f"slot {b} runs a sequence of {self._arena.size(b)} frames, got a frame of {tuple(im.shape[:2])}; "
-                                     "a slot changes its frame size in reinit() only")
-        self._arena.set_all(imgs)
-        return self._arena
+        self._upload = FrameUploader(self.n)      # (one pinned staging buffer, one asynchronous copy per step)
 
     # -------------------------------------------------------------------------------------------------- init
-    @staticmethod
-    def _geometry(poly, cfg):
-        """(init_pos [2], size [2], init_s_z, init_s_z_sm) of one sequence from its poly (cx, cy, w, h, ...) (hdn_tracker_proj_e2e.py:66-84)."""
-        p = np.asarray(poly, np.float64).reshape(-1)[:4]
-        pos, size = p[0:2].copy(), p[2:4].copy()
-        ctx = cfg.context_amount * size.sum()
-        return pos, size, np.floor(np.sqrt((size[0] + ctx) * (size[1] + ctx))), np.floor(np.sqrt(size[0] * size[1]))
-
-    def _const_row(self, zp):
-        """One row of _consts (:251-258, as HomoTracker.init builds them: float32 matrices, float32 inverses)."""
-        E, row = self.cfg.exemplar_size, np.zeros(TRACK_CONST_DOUBLES, np.float64)
-        S = np.diag([E / (zp[2] - zp[0] + 1), E / (zp[3] - zp[1] + 1), 1.0]).astype(np.float32)
-        Sh = np.array([[1, 0, -zp[0]], [0, 1, -zp[1]], [0, 0, 1]], np.float32)
-        row[0:9], row[9:18] = np.linalg.inv(S).astype(np.float64).reshape(-1), S.astype(np.float64).reshape(-1)
-        row[18:27], row[27:36] = np.linalg.inv(Sh).astype(np.float64).reshape(-1), Sh.astype(np.float64).reshape(-1)
-        row[36] = self.score_gate
-        return row
-
     def init(self, imgs, bboxes, polys, gt_points, first_points=None):
         """Per sequence what hdnTrackerHomo.init takes (hdn_tracker_proj_e2e.py:60): imgs n x BGR uint8 [H,W,3]; bboxes n x (x, y, w, h);
         polys n x (cx, cy, w, h, theta); gt_points n x the initial corners (the same number of points for every sequence)."""
@@ -143,18 +68,18 @@ class BatchedHomoTracker:
         if not (len(bboxes) == len(polys) == len(gt_points) == n):
             raise ValueError(f"init takes {n} bboxes / polys / gt_points")
         self.dev = next(self.net.parameters()).device
-        geo = [self._geometry(p, c) for p in polys]
+        geo = [_geometry(p, c) for p in polys]
         self.init_pos, self.size = np.stack([g[0] for g in geo]), np.stack([g[1] for g in geo])
         self.init_s_z, self.init_s_z_sm = np.array([g[2] for g in geo], np.float64), np.array([g[3] for g in geo], np.float64)
         if self.frame_capacity is not None:      # arena mode: first frames of different sizes
             if not torch.cuda.is_available():
                 raise _lib.HdnHipError("hdn_amd runs on the GPU only; there is no CPU fallback")
             self._arena = FR.FrameArena(n, self.frame_capacity[0], self.frame_capacity[1], 3, device=self.dev)
-            frames = self._upload_arena(imgs, same_size=False)
+            frames = upload_arena(self._arena, imgs, same_size=False)
             self.channel_average = torch.stack([frames.frame(b).to(torch.float64).mean(dim=(0, 1)) for b in range(n)]).cpu().numpy()
             sizes = [frames.size(b) for b in range(n)]
         else:
-            frames = self._upload(imgs)
+            frames = self._upload(imgs, self.dev)
             # np.mean(img, axis=(0, 1)) of every first frame: one reduction on the device, read once
             self.channel_average = frames.to(torch.float64).mean(dim=(1, 2)).cpu().numpy()
             sizes = [tuple(frames.shape[1:3])] * n
@@ -176,7 +101,7 @@ class BatchedHomoTracker:
         self._Ht, self._Hinv = (torch.empty((n, 9), dtype=torch.float64, device=self.dev) for _ in range(2))
         self._out = torch.empty((n, 2 * self.n_points + 1), dtype=torch.float32, device=self.dev)
         self._graph = None
-        consts = np.stack([self._const_row(zp) for zp in self.z_crop_points_sm])
+        consts = np.stack([_const_row(zp, c.exemplar_size, self.score_gate) for zp in self.z_crop_points_sm])
         self._consts = torch.from_numpy(consts).to(self.dev)
 
     def reinit(self, slot: int, img, bbox, poly, gt_points, first_point=None):
@@ -193,7 +118,7 @@ class BatchedHomoTracker:
         if pts.shape[0] != self.n_points:
             raise ValueError(f"this tracker follows {self.n_points} points per sequence, got {pts.shape[0]}")
         c = self.cfg
-        pos, size, s_z, s_z_sm = self._geometry(poly, c)
+        pos, size, s_z, s_z_sm = _geometry(poly, c)
         self._arena.set(slot, img)                   # (raises for a frame above the capacity, before anything is written)
         frame = self._arena.frame(slot)
         avg = frame.to(torch.float64).mean(dim=(0, 1)).cpu().numpy()
@@ -209,7 +134,7 @@ class BatchedHomoTracker:
             self.similarity.reinit(slot, frame, pos, s_z, s_z_sm, avg)
         self.init_points[slot].copy_(torch.from_numpy(pts))
         self.H_total[slot].copy_(torch.eye(3, dtype=torch.float64))
-        self._consts[slot].copy_(torch.from_numpy(self._const_row(zp)))
+        self._consts[slot].copy_(torch.from_numpy(_const_row(zp, c.exemplar_size, self.score_gate)))
 
     # -------------------------------------------------------------------------------------------------- one step = one frame of every sequence
     def _body(self, frames):
@@ -238,23 +163,13 @@ class BatchedHomoTracker:
         return self._out, score
 
     def _capture(self, frame_shape):
+        """One hipGraph per step, as HomoTracker._capture (the warm-up also runs MIOpen's find at this batch size)."""
         # (arena mode: the arena IS the static input - its slots hold the sequences' latest frames, their sizes are device data)
         self._static_frames = self._arena if self._arena is not None else torch.empty(frame_shape, dtype=torch.uint8, device=self.dev)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        H0 = self.H_total.clone()
-        try:
-            with torch.cuda.stream(side):
-                for _ in range(3):      # warm-up on the side stream (MIOpen find at this batch size, lazy initialisations)
-                    self._body(self._static_frames)
-            torch.cuda.current_stream().wait_stream(side)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                self._g_out, self._g_score = self._body(self._static_frames)
-            self._graph = graph
-        finally:
-            torch.cuda.current_stream().wait_stream(side)
-            self.H_total.copy_(H0)
+        got = capture_graph(lambda: self._body(self._static_frames), [self.H_total], "batched per-frame")
+        self.use_graph = got is not None
+        if got is not None:
+            self._graph, (self._g_out, self._g_score) = got
 
     def track_new(self, fr_idx, imgs, sync: bool = True):
         """One frame of every sequence.  -> list of n result dictionaries with hdnTrackerHomo.track_new's keys (sync=True; one host read
@@ -263,38 +178,26 @@ class BatchedHomoTracker:
         arena = self._arena is not None
         if arena:
             imgs = [np.asarray(im) if not isinstance(im, torch.Tensor) else im for im in imgs] if not isinstance(imgs, torch.Tensor) else imgs
-            self._upload_arena(imgs, same_size=True)          # (before a first capture too: a refused step leaves nothing half done)
+            upload_arena(self._arena, imgs, same_size=True)   # (before a first capture too: a refused step leaves nothing half done)
+        if self.use_graph and self._graph is None:
+            shape = None if arena else tuple(imgs.shape) if isinstance(imgs, torch.Tensor) else (n,) + tuple(np.asarray(imgs[0]).shape)
+            self._capture(shape)                              # (may switch use_graph off)
         if self.use_graph:
-            if self._graph is None:
-                shape = None if arena else tuple(imgs.shape) if isinstance(imgs, torch.Tensor) else (n,) + tuple(np.asarray(imgs[0]).shape)
-                try:
-                    self._capture(shape)
-                except RuntimeError as e:
-                    import warnings
-                    warnings.warn(f"hdn_amd: the batched per-frame body could not be captured as a hipGraph ({type(e).__name__}: {e}); running it eagerly")
-                    self.use_graph, self._graph = False, None
-                    return self.track_new(fr_idx, imgs, sync=sync)
             if not arena:
-                self._upload(imgs, into=self._static_frames)
+                self._upload(imgs, self.dev, into=self._static_frames)
             self._graph.replay()
             out, score = self._g_out, self._g_score
             if not sync:
                 out, score = out.clone(), score.clone()
         else:
-            out, score = self._body(self._arena if arena else self._upload(imgs))
+            out, score = self._body(self._arena if arena else self._upload(imgs, self.dev))
             out = out.clone()
         self.last_points, self.last_score = out[:, :2 * P].view(n, P, 2), score
         if not sync:
             return {"points": self.last_points, "polygon": self.last_points, "best_score": out[:, 2 * P]}
         host = out.cpu().numpy()
         self.host_syncs += 1
-        res = []
-        for b in range(n):
-            pn, best = host[b, :2 * P].reshape(P, 2), host[b, 2 * P]
-            mx, mn = pn.max(0), pn.min(0)
-            bbox = [mn[0], mn[1], mx[0] - mn[0], mx[1] - mn[1]]
-            res.append({"bbox_aligned": bbox, "best_score": best, "polygon": pn, "points": pn, "bbox": bbox})
-        return res
+        return [homography_result(host[b], P) for b in range(n)]
 
     def track(self, imgs):
         return self.track_new(None, imgs)
@@ -309,50 +212,36 @@ class BatchedDeviceTracker(BatchedHomoTracker):
     def __init__(self, model, n: int, graph: bool = None, iterations: int = 1, cfg: TrackerConfig = None, fold_backbone: bool = None,
                  hip_trunk: bool = None, frame_capacity=None):
         if cfg is None:
-            cfg = TrackerConfig()
-            try:
-                from hdn.core.config import cfg as ref_cfg
-                cfg = TrackerConfig.from_reference(ref_cfg)
-            except ImportError:
-                pass
+            cfg, _ = reference_config()
         if graph is None:
-            graph = os.environ.get("HDN_TRACKER_GRAPH", "1") not in ("", "0")
-        model.eval()
+            graph = env_flag("HDN_TRACKER_GRAPH")
         self.model = model
-        self.miopen_find = os.environ.get("HDN_MIOPEN_FIND", "1") not in ("", "0") and next(model.parameters()).is_cuda
-        from . import backbone as BB
-        self.folded = BB.optimize_similarity_model(model) if (BB.enabled() if fold_backbone is None else fold_backbone) else []
-        from .tracker import attach_hip_trunk
+        self.miopen_find, self.folded = prepare_model(model, fold_backbone)
         self.hip_trunk = attach_hip_trunk(model, hip_trunk)
         super().__init__(model.hm_net, n, iterations=iterations, similarity=DeviceSimilarity(model, cfg), graph=graph, cfg=cfg,
                          frame_capacity=frame_capacity)
 
-    def _find_mode(self):
-        import contextlib
-        if not self.miopen_find:
-            return contextlib.nullcontext()
-
-        @contextlib.contextmanager
-        def only_benchmark():        # (only this flag: torch.backends.cudnn.flags() would reset the others to its defaults)
-            before = torch.backends.cudnn.benchmark
-            torch.backends.cudnn.benchmark = True
-            try:
-                yield
-            finally:
-                torch.backends.cudnn.benchmark = before
-        return only_benchmark()
-
     def init(self, imgs, bboxes, polys, gt_points, first_points=None):
-        with self._find_mode():
+        with find_mode(self.miopen_find):
             return super().init(imgs, bboxes, polys, gt_points, first_points)
 
     def track_new(self, fr_idx, imgs, sync: bool = True):
-        with self._find_mode():
+        with find_mode(self.miopen_find):
             return super().track_new(fr_idx, imgs, sync=sync)
 
     def reinit(self, slot, img, bbox, poly, gt_points, first_point=None):
-        with self._find_mode():
+        with find_mode(self.miopen_find):
             return super().reinit(slot, img, bbox, poly, gt_points, first_point)
+
+
+@dataclasses.dataclass
+class _Slot:
+    """What track_videos knows of one slot of the tracker."""
+    video: object        # index of the video the slot runs; None: idle (its results are dropped)
+    frames: object       # iterator over the video's remaining frames
+    last: object         # the last frame fed (fed again while the slot idles)
+    fed: int             # frames fed after the first
+    init: dict           # the video's init dictionary
 
 
 def track_videos(tracker, videos, on_result=None):
@@ -384,36 +273,35 @@ def track_videos(tracker, videos, on_result=None):
     if not queue:
         return results
     queue.reverse()                                  # pop() from the end = input order
-    # slot state: [video index or None (idle), frame iterator, last frame fed, frames fed after the first]
     slots = []
     for b in range(n):
         if queue:
             k, first, it, init = queue.pop()
-            slots.append([k, it, first, 0, init])
+            slots.append(_Slot(k, it, first, 0, init))
         else:                                        # fewer videos than slots: an idle copy of the last one
-            slots.append([None, iter(()), slots[-1][2], 0, slots[-1][4]])
-    tracker.init([s[2] for s in slots], [s[4]["bbox"] for s in slots], [s[4]["poly"] for s in slots], [s[4]["gt_points"] for s in slots],
-                 [s[4].get("first_point") for s in slots])
+            slots.append(_Slot(None, iter(()), slots[-1].last, 0, slots[-1].init))
+    tracker.init([s.last for s in slots], [s.init["bbox"] for s in slots], [s.init["poly"] for s in slots], [s.init["gt_points"] for s in slots],
+                 [s.init.get("first_point") for s in slots])
     while True:
         # a slot whose video has no further frame takes the next video, or goes idle
         for b, s in enumerate(slots):
-            while s[0] is not None:
-                nxt = next(s[1], None)
+            while s.video is not None:
+                nxt = next(s.frames, None)
                 if nxt is not None:
-                    s[2], s[3] = nxt, s[3] + 1
+                    s.last, s.fed = nxt, s.fed + 1
                     break
                 if not queue:
-                    s[0] = None
+                    s.video = None
                     break
                 k, first, it, init = queue.pop()
                 tracker.reinit(b, first, init["bbox"], init["poly"], init["gt_points"], init.get("first_point"))
-                s[0], s[1], s[2], s[3], s[4] = k, it, first, 0, init
-        if all(s[0] is None for s in slots):
+                s.video, s.frames, s.last, s.fed, s.init = k, it, first, 0, init
+        if all(s.video is None for s in slots):
             return results
-        res = tracker.track_new(None, [s[2] for s in slots])
+        res = tracker.track_new(None, [s.last for s in slots])
         for b, s in enumerate(slots):
-            if s[0] is not None:
+            if s.video is not None:
                 if on_result is not None:
-                    on_result(s[0], s[3], res[b])
+                    on_result(s.video, s.fed, res[b])
                 else:
-                    results[s[0]].append(res[b])
+                    results[s.video].append(res[b])

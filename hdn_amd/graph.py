@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import torch
 
+from ._loop import capture_graph
 from .homo_model import homo_stages, track_proj
 
 
@@ -29,15 +30,8 @@ class GraphedTrackProj:
         self._patch_1 = None
         if self.template_constant:
             self._patch_1 = homo_stages(net, self.static)["patch_1"].contiguous().clone()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                track_proj(net, self.static, None, self._patch_1)
-        torch.cuda.current_stream().wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            self.out = track_proj(net, self.static, None, self._patch_1)
+        # (nothing to put back: track_proj carries no state; a body that cannot be captured is an error here, there is no eager form of this object)
+        self.graph, self.out = capture_graph(lambda: track_proj(net, self.static, None, self._patch_1), fallback=False, warmup=warmup)
 
     def __call__(self, data: dict):
         for k, buf in self.static.items():

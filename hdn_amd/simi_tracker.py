@@ -28,13 +28,13 @@ Signatures: the reference's launchers call `init(img, bbox, poly, gt_points, fir
 """
 from __future__ import annotations
 
-import os
-
 import numpy as np
 import torch
 
 from . import _lib
 from . import frame as FR
+from ._loop import (FrameUploader, capture_graph, env_flag, find_mode, prepare_model, reference_config, similarity_result, track_state_row,
+                    upload_arena, validate_frame_capacity)
 from .similarity import SEQ_DOUBLES, SimilarityDecoder, TrackerConfig
 
 TRACK_DOUBLES, OUT_DOUBLES = 48, 20     # HDN_SIMI_TRACK_DOUBLES / HDN_SIMI_OUT_DOUBLES
@@ -84,13 +84,15 @@ def sequence_records(poly, first_point, channel_average, cfg: TrackerConfig):
 
 
 class SimiTracker:
+    _label = "per-frame"       # (how the warning of a failed capture names the body)
+
     def __init__(self, model, cfg: TrackerConfig = None, graph: bool = False, scale_score_thresh: float = 0.5, batch_template: bool = None):
         """model: the reference's ModelBuilder interface (template / track_new / track_new_lp) in eval mode on the GPU.
         scale_score_thresh: cfg.TRACK.SCALE_SCORE_THRESH (0.5 in hdn/core/config.py:527 and every shipped YAML).
         batch_template: refresh the template with one backbone pass over (crop, log-polar crop) instead of template()'s two (checked against
         template() at init; default: HDN_SIMI_BATCH_TEMPLATE, on)."""
         self.model = model
-        self.batch_template = (os.environ.get("HDN_SIMI_BATCH_TEMPLATE", "1") not in ("", "0")) if batch_template is None else bool(batch_template)
+        self.batch_template = env_flag("HDN_SIMI_BATCH_TEMPLATE") if batch_template is None else bool(batch_template)
         self._batched_ok = False
         self.cfg = cfg or TrackerConfig()
         self.use_graph, self._graph = bool(graph), None
@@ -222,53 +224,33 @@ class SimiTracker:
         frame.copy_(self.init_frame)
         return frame
 
-    def _snapshot(self):
-        return [self.track.clone(), self.seq.clone(), self.state.clone()] + [t.clone() for f in self._zf_static for t in (f if isinstance(f, list) else [f])]
-
-    def _restore(self, snap):
-        live = [self.track, self.seq, self.state] + [t for f in self._zf_static for t in (f if isinstance(f, list) else [f])]
-        for d, s in zip(live, snap):
-            d.copy_(s)
+    def _captured_body(self, body):
+        before = self._head_caches()
+        out = body()
+        # (the refresh of the step before changed the template tensors in place, so the heads recomputed their template-branch
+        # features INSIDE the capture: they are nodes of the graph and follow the template on every replay)
+        self._kern_in_graph = all(b is None or b is not a for a, b in zip(before, self._head_caches()))
+        return out
 
     def _capture(self, frame_shape):
         """One hipGraph for the whole body.  The warm-up / capture runs advance the recurrences and refresh the template: everything they
-        touched is put back afterwards (track record, seq, state, template features)."""
+        touched is put back afterwards (track record, seq, state, template features).  A body that cannot be captured: use_graph goes False."""
         self._static_frame = self._static_input(frame_shape)
-        snap = self._snapshot()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        try:
-            with torch.cuda.stream(side):
-                for _ in range(3):
-                    self._body(self._static_frame)
-            torch.cuda.current_stream().wait_stream(side)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                before = self._head_caches()
-                self._g_out = self._body(self._static_frame)
-                # (the refresh of the step before changed the template tensors in place, so the heads recomputed their template-branch
-                # features INSIDE the capture: they are nodes of the graph and follow the template on every replay)
-                self._kern_in_graph = all(b is None or b is not a for a, b in zip(before, self._head_caches()))
-            self._graph = graph
-        finally:
-            torch.cuda.current_stream().wait_stream(side)
-            self._restore(snap)
+        live = [self.track, self.seq, self.state] + [t for f in self._zf_static for t in (f if isinstance(f, list) else [f])]
+        got = capture_graph(lambda: self._body(self._static_frame), live, self._label, hook=self._captured_body)
+        self.use_graph = got is not None
+        if got is not None:
+            self._graph, self._g_out = got
 
     def track_new(self, fr_idx, img, gt_box=None, gt_poly=None, gt_points=None, sync: bool = True):
         """-> {'bbox', 'bbox_aligned', 'best_score', 'rot', 'polygon'} as hdnTracker.track_new (:295-301); sync=False: the float64 device record
         [20] (include/hdn_hip.h: hdn_simi_track_update_f64's `out`) without any host read."""
         if tuple(img.shape[:2]) != self.frame_hw:
             raise ValueError(f"frames of a sequence have one size: init saw {self.frame_hw}, this one is {tuple(img.shape[:2])}")
+        if self.use_graph and self._graph is None:
+            self._capture(tuple(img.shape))                   # (may switch use_graph off)
         if self.use_graph:
             t = img if isinstance(img, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(img))
-            if self._graph is None:
-                try:
-                    self._capture(tuple(t.shape))
-                except RuntimeError as e:
-                    import warnings
-                    warnings.warn(f"hdn_amd: the per-frame body could not be captured as a hipGraph ({type(e).__name__}: {e}); running it eagerly")
-                    self.use_graph, self._graph = False, None
-                    return self.track_new(fr_idx, img, gt_box, gt_poly, gt_points, sync=sync)
             self._static_frame.copy_(t, non_blocking=True)
             self._graph.replay()
             out = self._g_out
@@ -278,8 +260,7 @@ class SimiTracker:
             return {"record": out.clone().view(-1)}
         h = out.view(-1).cpu().numpy()
         self.host_syncs += 1
-        return {"bbox": [h[0], h[1], h[2], h[3]], "bbox_aligned": [h[4], h[5], h[6], h[7]], "best_score": np.float32(h[8]), "rot": h[9],
-                "polygon": h[10:18].reshape(4, 2).copy()}
+        return similarity_result(h)
 
     def track(self, img):
         return self.track_new(None, img)
@@ -289,9 +270,7 @@ class SimiTracker:
         demand (one device->host read, counted)."""
         t = self.track.view(-1).cpu().numpy()
         self.host_syncs += 1
-        return {"center_pos": t[0:2].copy(), "size": t[2:4].copy(), "rot": float(t[4]), "lp_shift": [0, float(t[5])], "scale": float(t[6]), "v": float(t[7]),
-                "window_scale_factor": float(t[8]), "lost_count": int(t[9]), "last_lost": bool(t[10]), "rot_is_float32": bool(t[11]),
-                "lp_shift_is_float32": bool(t[12]), "frames": int(t[13])}
+        return track_state_row(t)
 
 
 class BatchedSimiTracker(SimiTracker):
@@ -308,23 +287,17 @@ class BatchedSimiTracker(SimiTracker):
     replaying while reinit(slot, ...) hands a slot a new video of another size.  track_videos(tracker, videos) schedules a dataset through
     the slots.  init / track_new then take LISTS of n frames."""
 
+    _label = "batched per-frame"
+
     def __init__(self, model, n: int, cfg: TrackerConfig = None, graph: bool = False, scale_score_thresh: float = 0.5, batch_template: bool = None,
                  frame_capacity=None):
         super().__init__(model, cfg=cfg, graph=graph, scale_score_thresh=scale_score_thresh, batch_template=batch_template)
         if n < 1:
             raise ValueError("n must be >= 1")
-        self.frame_capacity = None
-        if frame_capacity is not None:
-            self.frame_capacity = (int(frame_capacity[0]), int(frame_capacity[1]))
-            if min(self.frame_capacity) < 1:
-                raise ValueError("frame_capacity must be (Hmax, Wmax) >= 1")
+        self.frame_capacity = validate_frame_capacity(frame_capacity)
         self._arena = self._first = self._rotated = None      # arena mode: this step's frames, the first frames, their rotation
         self.n = int(n)
-        self._staging = self._copy_done = None
-
-    def _upload(self, imgs, into=None):
-        from .batched_tracker import BatchedHomoTracker
-        return BatchedHomoTracker._upload(self, imgs, into)          # (one pinned staging buffer, one asynchronous copy; the same checks)
+        self._upload = FrameUploader(self.n)      # (one pinned staging buffer, one asynchronous copy per step)
 
     def init(self, imgs, bboxes, polys, *rest):
         """imgs n x BGR uint8 [H,W,3] (one size); bboxes, polys (cx, cy, w, h, theta) and first_points per sequence (hdnTracker.init's arguments; the
@@ -343,8 +316,7 @@ class BatchedSimiTracker(SimiTracker):
             if not torch.cuda.is_available():
                 raise _lib.HdnHipError("hdn_amd runs on the GPU only; there is no CPU fallback")
             arena = FR.FrameArena(n, self.frame_capacity[0], self.frame_capacity[1], 3, device=self.dev)
-            self._upload_arena(imgs, same_size=False, arena=arena)
-            frames = self._arena = arena
+            frames = self._arena = upload_arena(arena, imgs, same_size=False)    # (replaced only once every frame was accepted)
             self._first = arena.like()                                # update_template rotates THESE frames, every step
             self._rotated = arena.like()
             for b in range(n):
@@ -352,7 +324,7 @@ class BatchedSimiTracker(SimiTracker):
             self.channel_average = torch.stack([arena.frame(b).to(torch.float64).mean(dim=(0, 1)) for b in range(n)]).cpu().numpy()
             self.frame_hw = [arena.size(b) for b in range(n)]         # per slot
         else:
-            frames = self._upload(imgs)
+            frames = self._upload(imgs, self.dev)
             self.init_frame = frames.clone()                              # update_template rotates THESE frames, every step
             self.channel_average = frames.to(torch.float64).mean(dim=(1, 2)).cpu().numpy()
             self.frame_hw = (int(frames.shape[1]), int(frames.shape[2]))
@@ -368,14 +340,6 @@ class BatchedSimiTracker(SimiTracker):
         z_crop = FR.get_subwindow(frames, None, c.exemplar_size, None, None, params=self.track[:, 40:46], islog=1)
         self._template(z_crop, first=True)
         return z_crop
-
-    def _upload_arena(self, imgs, same_size: bool, arena=None):
-        from .batched_tracker import BatchedHomoTracker
-        if arena is not None:                    # (init: the tracker's arena is replaced only once every frame was accepted)
-            if isinstance(imgs, torch.Tensor) or len(imgs) != self.n:
-                raise ValueError(f"this tracker advances {self.n} sequences per step and takes a list of {self.n} frames (each of its slot's size)")
-            return arena.set_all(imgs)
-        return BatchedHomoTracker._upload_arena(self, imgs, same_size)      # (the same checks: a running slot keeps its frame size)
 
     # -------------------------------------------------------------------------------------------------- arena mode: the parts of a step that see frame sizes
     def _update(self):
@@ -445,60 +409,35 @@ class BatchedSimiTracker(SimiTracker):
         """One frame of every sequence -> n result dictionaries with hdnTracker.track_new's keys (sync=True: one host read for all), or the float64 device
         records [n, 20] (sync=False).  Arena mode: a list of n frames, each of its slot's current size."""
         if self.frame_capacity is not None:
-            return self._track_new_arena(fr_idx, imgs, sync)
-        n = self.n
-        shape = tuple(imgs.shape) if isinstance(imgs, torch.Tensor) else (len(imgs),) + tuple(np.asarray(imgs[0]).shape)
-        if shape[0] != n or tuple(shape[1:3]) != self.frame_hw:
-            raise ValueError(f"a step takes {n} frames of {self.frame_hw}, got {shape}")
+            if self._arena is None:
+                raise RuntimeError("track_new() before init()")
+            if not isinstance(imgs, torch.Tensor):
+                imgs = [im if isinstance(im, torch.Tensor) else np.asarray(im) for im in imgs]
+            upload_arena(self._arena, imgs, same_size=True)   # (before a first capture too: a refused step leaves nothing half done)
+            shape = None
+        else:
+            shape = tuple(imgs.shape) if isinstance(imgs, torch.Tensor) else (len(imgs),) + tuple(np.asarray(imgs[0]).shape)
+            if shape[0] != self.n or tuple(shape[1:3]) != self.frame_hw:
+                raise ValueError(f"a step takes {self.n} frames of {self.frame_hw}, got {shape}")
+        if self.use_graph and self._graph is None:
+            self._capture(shape)                              # (may switch use_graph off)
         if self.use_graph:
-            if self._graph is None:
-                try:
-                    self._capture(shape)
-                except RuntimeError as e:
-                    import warnings
-                    warnings.warn(f"hdn_amd: the batched per-frame body could not be captured as a hipGraph ({type(e).__name__}: {e}); running it eagerly")
-                    self.use_graph, self._graph = False, None
-                    return self.track_new(fr_idx, imgs, sync=sync)
-            self._upload(imgs, into=self._static_frame)
+            if shape is not None:
+                self._upload(imgs, self.dev, into=self._static_frame)
             self._graph.replay()
             out = self._g_out
         else:
-            out = self._body(self._upload(imgs))
-        return self._results(out, sync)
-
-    def _results(self, out, sync):
+            out = self._body(self._arena if shape is None else self._upload(imgs, self.dev))
         if not sync:
             return {"record": out.clone()}
         h = out.cpu().numpy()
         self.host_syncs += 1
-        return [{"bbox": list(h[b, 0:4]), "bbox_aligned": list(h[b, 4:8]), "best_score": np.float32(h[b, 8]), "rot": h[b, 9],
-                 "polygon": h[b, 10:18].reshape(4, 2).copy()} for b in range(self.n)]
-
-    def _track_new_arena(self, fr_idx, imgs, sync):
-        if self._arena is None:
-            raise RuntimeError("track_new() before init()")
-        if not isinstance(imgs, torch.Tensor):
-            imgs = [im if isinstance(im, torch.Tensor) else np.asarray(im) for im in imgs]
-        self._upload_arena(imgs, same_size=True)              # (before a first capture too: a refused step leaves nothing half done)
-        if self.use_graph and self._graph is None:
-            try:
-                self._capture(None)
-            except RuntimeError as e:
-                import warnings
-                warnings.warn(f"hdn_amd: the batched per-frame body could not be captured as a hipGraph ({type(e).__name__}: {e}); running it eagerly")
-                self.use_graph, self._graph = False, None
-        if self._graph is not None:
-            self._graph.replay()
-            out = self._g_out
-        else:
-            out = self._body(self._arena)
-        return self._results(out, sync)
+        return [similarity_result(h[b]) for b in range(self.n)]
 
     def track_state(self) -> list:
         t = self.track.cpu().numpy()
         self.host_syncs += 1
-        return [{"center_pos": r[0:2].copy(), "size": r[2:4].copy(), "rot": float(r[4]), "lp_shift": [0, float(r[5])], "scale": float(r[6]), "v": float(r[7]),
-                 "lost_count": int(r[9]), "frames": int(r[13])} for r in t]
+        return [track_state_row(r) for r in t]
 
 
 class DeviceTrackerSimi(SimiTracker):
@@ -508,40 +447,17 @@ class DeviceTrackerSimi(SimiTracker):
     def __init__(self, model, graph: bool = None, cfg: TrackerConfig = None, fold_backbone: bool = None, batch_template: bool = None):
         thresh = 0.5
         if cfg is None:
-            cfg = TrackerConfig()
-            try:
-                from hdn.core.config import cfg as ref_cfg
-                cfg = TrackerConfig.from_reference(ref_cfg)
-                thresh = float(ref_cfg.TRACK.SCALE_SCORE_THRESH)
-            except (ImportError, AttributeError):
-                pass
+            cfg, ref_cfg = reference_config()
+            thresh = float(getattr(getattr(ref_cfg, "TRACK", None), "SCALE_SCORE_THRESH", thresh))
         if graph is None:
-            graph = os.environ.get("HDN_TRACKER_GRAPH", "1") not in ("", "0")
-        model.eval()
-        self.miopen_find = os.environ.get("HDN_MIOPEN_FIND", "1") not in ("", "0") and next(model.parameters()).is_cuda
-        from . import backbone as BB
-        self.folded = BB.optimize_similarity_model(model) if (BB.enabled() if fold_backbone is None else fold_backbone) else []
+            graph = env_flag("HDN_TRACKER_GRAPH")
+        self.miopen_find, self.folded = prepare_model(model, fold_backbone)
         super().__init__(model, cfg=cfg, graph=graph, scale_score_thresh=thresh, batch_template=batch_template)
 
-    def _find_mode(self):
-        import contextlib
-        if not self.miopen_find:
-            return contextlib.nullcontext()
-
-        @contextlib.contextmanager
-        def only_benchmark():
-            before = torch.backends.cudnn.benchmark
-            torch.backends.cudnn.benchmark = True
-            try:
-                yield
-            finally:
-                torch.backends.cudnn.benchmark = before
-        return only_benchmark()
-
     def init(self, img, bbox, poly, *rest):
-        with self._find_mode():
+        with find_mode(self.miopen_find):
             return super().init(img, bbox, poly, *rest)
 
     def track_new(self, fr_idx, img, gt_box=None, gt_poly=None, gt_points=None, sync: bool = True):
-        with self._find_mode():
+        with find_mode(self.miopen_find):
             return super().track_new(fr_idx, img, gt_box, gt_poly, gt_points, sync=sync)

@@ -24,17 +24,36 @@ similarity branch.  Sequences are independent: N GPUs run N sequences (replicas 
 """
 from __future__ import annotations
 
-import os
-
 import numpy as np
 import torch
 
 from . import _lib
 from . import frame as FR
+from ._loop import capture_graph, env_flag, find_mode, homography_result, prepare_model, reference_config
 from .refine import homo_refine
 from .similarity import DeviceSimilarity, TrackerConfig
 
 TRACK_CONST_DOUBLES = 40     # HDN_TRACK_CONST_DOUBLES
+
+
+def _geometry(poly, cfg):
+    """(init_pos [2], size [2], init_s_z, init_s_z_sm) of one sequence from its poly (cx, cy, w, h, ...) (hdn_tracker_proj_e2e.py:66-84)."""
+    p = np.asarray(poly, np.float64).reshape(-1)[:4]
+    pos, size = p[0:2].copy(), p[2:4].copy()
+    ctx = cfg.context_amount * size.sum()
+    return pos, size, np.floor(np.sqrt((size[0] + ctx) * (size[1] + ctx))), np.floor(np.sqrt(size[0] * size[1]))
+
+
+def _const_row(zp, exemplar_size, score_gate):
+    """One sequence's row of _consts: the un-scale / un-shift of the residual (:251-258) - four matrices that are constants of the sequence
+    (float32 as the reference builds them, their inverses float32 by numpy's dtype rule) - handed to hdn_track_accumulate_f64 with the gate."""
+    E, row = exemplar_size, np.zeros(TRACK_CONST_DOUBLES, np.float64)
+    S = np.diag([E / (zp[2] - zp[0] + 1), E / (zp[3] - zp[1] + 1), 1.0]).astype(np.float32)
+    Sh = np.array([[1, 0, -zp[0]], [0, 1, -zp[1]], [0, 0, 1]], np.float32)
+    row[0:9], row[9:18] = np.linalg.inv(S).astype(np.float64).reshape(-1), S.astype(np.float64).reshape(-1)
+    row[18:27], row[27:36] = np.linalg.inv(Sh).astype(np.float64).reshape(-1), Sh.astype(np.float64).reshape(-1)
+    row[36] = score_gate
+    return row
 
 
 class HomoTracker:
@@ -58,13 +77,8 @@ class HomoTracker:
         """img: BGR uint8 [H,W,3]; bbox (x, y, w, h); poly (cx, cy, w, h, theta); gt_points: the 4 corners."""
         c = self.cfg
         self.dev = next(self.net.parameters()).device
-        self.init_pos = np.array([poly[0], poly[1]], np.float64)
-        self.center_pos = self.init_pos.copy()
-        self.size = np.array([poly[2], poly[3]], np.float64)
-        w_z = self.size[0] + c.context_amount * np.sum(self.size)
-        h_z = self.size[1] + c.context_amount * np.sum(self.size)
-        self.init_s_z = float(np.floor(np.sqrt(w_z * h_z)))
-        self.init_s_z_sm = float(np.floor(np.sqrt(self.size[0] * self.size[1])))
+        self.init_pos, self.size, s_z, s_z_sm = _geometry(poly, c)
+        self.center_pos, self.init_s_z, self.init_s_z_sm = self.init_pos.copy(), float(s_z), float(s_z_sm)
         frame = FR.upload(img)
         # np.mean(img, axis=(0, 1)) of the first frame: one reduction on the device, read once per sequence
         self.channel_average = frame.to(torch.float64).mean(dim=(0, 1)).cpu().numpy()
@@ -83,18 +97,7 @@ class HomoTracker:
         self._out = torch.empty((1, 2 * self.init_points.shape[1] + 1), dtype=torch.float32, device=self.dev)
         self._const_params = FR._dev_f64([self.init_pos[0], self.init_pos[1], self.init_s_z_sm] + [float(a) for a in self.channel_average], self.dev)
         self._graph = None
-        # un-scale / un-shift of the residual (:251-258): the four matrices are constants of the sequence (float32 as the reference
-        # builds them, their inverses float32 by numpy's dtype rule), handed to hdn_track_accumulate_f64 with the gate
-        cw = self.z_crop_points_sm[2] - self.z_crop_points_sm[0] + 1
-        ch = self.z_crop_points_sm[3] - self.z_crop_points_sm[1] + 1
-        E = c.exemplar_size
-        S = np.diag([E / cw, E / ch, 1.0]).astype(np.float32)
-        Sh = np.array([[1, 0, -self.z_crop_points_sm[0]], [0, 1, -self.z_crop_points_sm[1]], [0, 0, 1]], np.float32)
-        consts = np.zeros(TRACK_CONST_DOUBLES, np.float64)
-        consts[0:9], consts[9:18] = np.linalg.inv(S).astype(np.float64).reshape(-1), S.astype(np.float64).reshape(-1)
-        consts[18:27], consts[27:36] = np.linalg.inv(Sh).astype(np.float64).reshape(-1), Sh.astype(np.float64).reshape(-1)
-        consts[36] = self.score_gate
-        self._consts = torch.from_numpy(consts).to(self.dev)
+        self._consts = torch.from_numpy(_const_row(self.z_crop_points_sm, c.exemplar_size, self.score_gate)).to(self.dev)
 
     # -------------------------------------------------------------------------------------------------- one frame
     def _body(self, frame):
@@ -129,40 +132,21 @@ class HomoTracker:
         return self.H_total, self._out.view(-1), homo_score
 
     def _capture(self, frame_shape):
-        """hipGraph of the whole per-frame body.  The frame lands in a static device buffer; H_total is carried in a static
-        tensor updated by the graph itself; the similarity state record is a static tensor of the DeviceSimilarity."""
+        """hipGraph of the whole per-frame body.  The frame lands in a static device buffer; H_total is carried in a static tensor updated
+        in place by the graph itself (the recurrence lives inside the graph; the warm-up's advance of it is put back); the similarity state
+        record is a static tensor of the DeviceSimilarity.  A body that cannot be captured: use_graph goes False, eager from here on."""
         self._static_frame = torch.empty(frame_shape, dtype=torch.uint8, device=self.dev)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        H0 = self.H_total.clone()
-        try:
-            with torch.cuda.stream(side):
-                for _ in range(3):  # warm-up on the side stream (MIOpen find, lazy initialisations); H_total is put back below
-                    self._body(self._static_frame)
-            torch.cuda.current_stream().wait_stream(side)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                H, out, score = self._body(self._static_frame)      # (H_total is updated in place: the recurrence lives inside the graph)
-                self._g_out, self._g_score = out, score
-            self._graph = graph
-        finally:
-            torch.cuda.current_stream().wait_stream(side)
-            self.H_total.copy_(H0)
+        got = capture_graph(lambda: self._body(self._static_frame), [self.H_total], "per-frame")
+        self.use_graph = got is not None
+        if got is not None:
+            self._graph, (_, self._g_out, self._g_score) = got
 
     def track_new(self, fr_idx, img, gt_box=None, gt_poly=None, gt_points=None, sync: bool = True):
         if self.use_graph:
             t = img if isinstance(img, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(img))
             if self._graph is None:
-                try:
-                    self._capture(tuple(t.shape))
-                except RuntimeError as e:
-                    # stream capture reports what it cannot hold (e.g. a model whose forward makes host round trips) as a
-                    # RuntimeError; the same kernels are then launched one by one.  Anything else is a real error and propagates,
-                    # as does whatever the eager retry raises.
-                    import warnings
-                    warnings.warn(f"hdn_amd: the per-frame body could not be captured as a hipGraph ({type(e).__name__}: {e}); running it eagerly")
-                    self.use_graph, self._graph = False, None
-                    return self.track_new(fr_idx, img, gt_box, gt_poly, gt_points, sync=sync)
+                self._capture(tuple(t.shape))          # (may switch use_graph off)
+        if self.use_graph:
             if tuple(t.shape) != tuple(self._static_frame.shape) or t.dtype != torch.uint8:
                 raise ValueError(f"graph mode was captured for uint8 frames of shape {tuple(self._static_frame.shape)}, got {t.dtype} {tuple(t.shape)}")
             self._static_frame.copy_(t, non_blocking=True)
@@ -180,11 +164,7 @@ class HomoTracker:
             return {"points": pts, "polygon": pts, "best_score": out[2 * n]}
         host = out.cpu().numpy()
         self.host_syncs += 1
-        pn, best_score = host[:2 * n].reshape(n, 2), host[2 * n]
-        mx, mn = pn.max(0), pn.min(0)
-        bbox = [mn[0], mn[1], mx[0] - mn[0], mx[1] - mn[1]]
-        return {"bbox_aligned": bbox, "best_score": best_score, "polygon": pn, "points": pn, "bbox": bbox}
-
+        return homography_result(host, n)
 
     def track(self, img):
         """BaseTracker.track (hdn/tracker/base_tracker.py:28-37, abstract there): the next frame, nothing else known."""
@@ -207,7 +187,7 @@ class HomoTracker:
 
 def hip_trunk_enabled() -> bool:
     """HDN_HIP_TRUNK (default 0): do the device trackers attach the folded HIP trunk to model.hm_net when `hip_trunk` is not given?"""
-    return os.environ.get("HDN_HIP_TRUNK", "0") not in ("", "0")
+    return env_flag("HDN_HIP_TRUNK", "0")
 
 
 def attach_hip_trunk(model, hip_trunk) -> bool:
@@ -232,25 +212,11 @@ class DeviceTrackerHomo(HomoTracker):
 
     def __init__(self, model, graph: bool = None, iterations: int = 1, cfg: TrackerConfig = None, fold_backbone: bool = None, hip_trunk: bool = None):
         if cfg is None:
-            cfg = TrackerConfig()
-            try:
-                from hdn.core.config import cfg as ref_cfg     # the reference's node, after tools/test.py merged the YAML
-                cfg = TrackerConfig.from_reference(ref_cfg)    # (incl. cfg.BAN.KWARGS.cls_out_channels: 2 = softmax, 1 = sigmoid decode)
-            except ImportError:
-                pass
+            cfg, _ = reference_config()
         if graph is None:
-            graph = os.environ.get("HDN_TRACKER_GRAPH", "1") not in ("", "0")
-        model.eval()
+            graph = env_flag("HDN_TRACKER_GRAPH")
         self.model = model
-        # The backbone's convolutions are PyTorch-ROCm's, and their shapes are fixed for a whole sequence: let MIOpen search for its kernels once
-        # (find mode; the search runs in the first frames / the capture warm-up).  Measured with the production-shaped model: 2.9 against 4.5 ms
-        # per frame (profiles/round4_experiments.txt item 11).  The reference's inference scripts leave torch's default (off); HDN_MIOPEN_FIND=0 does too.
-        # The flag is process-global in torch, so it is raised only AROUND this tracker's own calls (init / track_new, incl. the graph
-        # capture) and put back afterwards: other models in the process keep the setting they had (round-4 ADVICE).
-        self.miopen_find = os.environ.get("HDN_MIOPEN_FIND", "1") not in ("", "0") and next(model.parameters()).is_cuda
-        # backbone + necks stay PyTorch-ROCm's convolutions; their BatchNorm / ReLU / add launches (a third of the B = 1 frame) are folded away
-        from . import backbone as BB
-        self.folded = BB.optimize_similarity_model(model) if (BB.enabled() if fold_backbone is None else fold_backbone) else []
+        self.miopen_find, self.folded = prepare_model(model, fold_backbone)
         self.hip_trunk = attach_hip_trunk(model, hip_trunk)
         super().__init__(model.hm_net, iterations=iterations, similarity=DeviceSimilarity(model, cfg), graph=graph, cfg=cfg)
         if (self.folded or self.miopen_find or self.hip_trunk) and not DeviceTrackerHomo._announced:
@@ -267,29 +233,10 @@ class DeviceTrackerHomo(HomoTracker):
 
     _announced = False
 
-    def _find_mode(self):
-        import contextlib
-        if not self.miopen_find:
-            return contextlib.nullcontext()
-
-        @contextlib.contextmanager
-        def only_benchmark():
-            # torch.backends.cudnn.flags() sets EVERY flag (the ones not named fall to its defaults: deterministic=False,
-            # allow_tf32=True), which would override a user's settings for the backbone's convolutions and bake them into the
-            # captured graph (round-5 ADVICE).  Only `benchmark` is touched here.
-            before = torch.backends.cudnn.benchmark
-            torch.backends.cudnn.benchmark = True
-            try:
-                yield
-            finally:
-                torch.backends.cudnn.benchmark = before
-
-        return only_benchmark()
-
     def init(self, img, bbox, poly, gt_points, first_point=None):
-        with self._find_mode():
+        with find_mode(self.miopen_find):
             return super().init(img, bbox, poly, gt_points, first_point)
 
     def track_new(self, fr_idx, img, gt_box=None, gt_poly=None, gt_points=None, sync: bool = True):
-        with self._find_mode():
+        with find_mode(self.miopen_find):
             return super().track_new(fr_idx, img, gt_box, gt_poly, gt_points, sync=sync)
