@@ -84,22 +84,7 @@ __global__ __launch_bounds__(256) void conv1x1_kernel(const float* __restrict__ 
 #pragma unroll
       for (int q = 0; q < 4; ++q) wv[j][q] = wa[j][q];
     if (c + 1 < cpk) load(c + 1);
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      unsigned q0[4], q1[4];                                                // the two pieces of channels 16 g + 8 t + [0, 8)
-      const f4 u = xv[2 * t], v = xv[2 * t + 1];
-      split2<SD>(f2{u.x, u.y}, q0[0], q1[0]);
-      split2<SD>(f2{u.z, u.w}, q0[1], q1[1]);
-      split2<SD>(f2{v.x, v.y}, q0[2], q1[2]);
-      split2<SD>(f2{v.z, v.w}, q0[3], q1[3]);
-      const u32x4 a0{q0[0], q0[1], q0[2], q0[3]}, a1{q1[0], q1[1], q1[2], q1[3]};
-#pragma unroll
-      for (int j = 0; j < NT; ++j) {
-        hi[j] = mfma(a0, wv[j][2 * t], hi[j]);
-        lo[j] = mfma(a0, wv[j][2 * t + 1], lo[j]);
-        lo[j] = mfma(a1, wv[j][2 * t], lo[j]);
-      }
-    }
+    mma_chunk<SD>(xv, wv, hi, lo);
   }
 
   // joined partial sums; with K split over the waves, the slices 1 .. KW - 1 hand theirs to slice 0 through the LDS
@@ -126,14 +111,14 @@ __global__ __launch_bounds__(256) void conv1x1_kernel(const float* __restrict__ 
         for (int r = 0; r < 16; ++r) p[j][r] += red[(((grp * (KW - 1) + s) * NT + j) * 16 + r) * 64 + lane];
   }
 
-  // epilogue: register r of a lane is pixel m0 + (r & 3) + 8 (r >> 2) + 4 g, output channel 32 (nt0 + j) + li
+  // epilogue: register r of a lane is pixel m0 + d_row(r, g), output channel 32 (nt0 + j) + li
 #pragma unroll
   for (int j = 0; j < NT; ++j) {
     const int co = (nt0 + j) * 32 + li;
     const float bv = bias[co];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int mm = m0 + (r & 3) + 8 * (r >> 2) + 4 * g;
+      const int mm = m0 + d_row(r, g);
       if (mm < M) {
         const size_t o = (size_t)mm * CO + co;
         float v = p[j][r] + bv;
@@ -197,7 +182,8 @@ extern "C" int hdn_conv1x1_f32(const float* x, const void* wpacked, const float*
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (const int rr = hdn::check_fp16_range(x, nx, s, act_domain)) return rr;
   return hdn::c1::dispatch((int)(B * So * So), CI, CO, [&](auto cfg) {
-    return act_domain ? hdn::c1::launch<decltype(cfg), true>(x, wpacked, bias, residual, out, B, S, CI, CO, stride, relu, s)
-                      : hdn::c1::launch<decltype(cfg), false>(x, wpacked, bias, residual, out, B, S, CI, CO, stride, relu, s);
+    return hdn::mc::by_domain(act_domain, [&](auto sd) {
+      return hdn::c1::launch<decltype(cfg), decltype(sd)::value>(x, wpacked, bias, residual, out, B, S, CI, CO, stride, relu, s);
+    });
   });
 }

@@ -257,14 +257,11 @@ __global__ __launch_bounds__(2 * HDN_BLOCK) void conv3x3_kernel(const float* __r
       const int item = tid + q * HDN_BLOCK;
       if (item < Cf::AITEMS) {
         const int px = item / (2 * KS), sub = item % (2 * KS);   // sub = k step * 2 + k half
-        unsigned q0[4], q1[4];
-        split2x2<SD>(av[q][0].x, av[q][0].y, q0[0], q1[0]);
-        split2x2<SD>(av[q][0].z, av[q][0].w, q0[1], q1[1]);
-        split2x2<SD>(av[q][1].x, av[q][1].y, q0[2], q1[2]);
-        split2x2<SD>(av[q][1].z, av[q][1].w, q0[3], q1[3]);
+        u32x4 p0, p1;
+        split8<SD>(av[q][0], av[q][1], p0, p1);
         unsigned char* dst = sA + ab * Cf::A_BYTES + sub * Cf::KG_BYTES + px * 16;
-        *reinterpret_cast<u32x4*>(dst) = u32x4{q0[0], q0[1], q0[2], q0[3]};
-        *reinterpret_cast<u32x4*>(dst + Cf::PIECE_BYTES) = u32x4{q1[0], q1[1], q1[2], q1[3]};
+        *reinterpret_cast<u32x4*>(dst) = p0;
+        *reinterpret_cast<u32x4*>(dst + Cf::PIECE_BYTES) = p1;
       }
     }
   };
@@ -293,21 +290,17 @@ __global__ __launch_bounds__(2 * HDN_BLOCK) void conv3x3_kernel(const float* __r
         sum_slices(x + off, MX, lz.zx, s0, s1);
         s0 = s0 + b0v; s1 = s1 + b1v;
         if (lz.res) { s0 = s0 + r0; s1 = s1 + r1; }
-        s0.x = fmaxf(s0.x, 0.f); s0.y = fmaxf(s0.y, 0.f); s0.z = fmaxf(s0.z, 0.f); s0.w = fmaxf(s0.w, 0.f);
-        s1.x = fmaxf(s1.x, 0.f); s1.y = fmaxf(s1.y, 0.f); s1.z = fmaxf(s1.z, 0.f); s1.w = fmaxf(s1.w, 0.f);
+        s0 = relu4(s0); s1 = relu4(s1);
         if (lz.xout && nb == 0 && ry >= 1 && ry <= Cf::PH - (ST == 1 ? 2 : 1)) {   // the tile's own input rows (not the halo)
           *reinterpret_cast<f4*>(lz.xout + off) = s0;
           *reinterpret_cast<f4*>(lz.xout + off + 4) = s1;
         }
       }
-      unsigned q0[4], q1[4];
-      split2x2<SD>(s0.x, s0.y, q0[0], q1[0]);
-      split2x2<SD>(s0.z, s0.w, q0[1], q1[1]);
-      split2x2<SD>(s1.x, s1.y, q0[2], q1[2]);
-      split2x2<SD>(s1.z, s1.w, q0[3], q1[3]);
+      u32x4 p0, p1;
+      split8<SD>(s0, s1, p0, p1);
       unsigned char* dst = sA + chunk * Cf::A_BYTES + sub * Cf::KG_BYTES + px * 16;
-      *reinterpret_cast<u32x4*>(dst) = u32x4{q0[0], q0[1], q0[2], q0[3]};
-      *reinterpret_cast<u32x4*>(dst + Cf::PIECE_BYTES) = u32x4{q1[0], q1[1], q1[2], q1[3]};
+      *reinterpret_cast<u32x4*>(dst) = p0;
+      *reinterpret_cast<u32x4*>(dst + Cf::PIECE_BYTES) = p1;
     }
   }
 
@@ -446,19 +439,18 @@ __global__ __launch_bounds__(2 * HDN_BLOCK) void conv3x3_kernel(const float* __r
     if (c2 < nchunk) static_for<3>([&](auto Jc) { stage_c(c2, Jc); });
   }
 
-  // ---- epilogue.  C/D layout of v_mfma_f32_32x32x16_f16: col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5).
-  // The tile goes through LDS once ([pixel][BN] fp32) so that the residual is read and the result written as 16 bytes per lane,
+  // ---- epilogue.  The tile goes through LDS once ([pixel][BN] fp32) so that the residual is read and the result written as 16 bytes per lane,
   // a pixel's BN channels (contiguous in NHWC) by BN / 4 consecutive lanes.
   __syncthreads();  // every wave is done with the A / W images
   HDN_ABL_CONV3X3_7()
   float* const sO = reinterpret_cast<float*>(smem);
-  // (the pixel of accumulator row r is a compile-time constant for each of the two half waves: one multiply-add per store instead of
+  // (the pixel of accumulator row d_row(r, g) is a compile-time constant for each of the two half waves: one multiply-add per store instead of
   //  the mapping's dozen integer operations - round 5)
   if (consume) {
     float* const obase = sO + wm * MT * 32 * Cf::EPI_STRIDE + wn * NT * 32 + li;
     static_for<MT>([&](auto MTc) {
       static_for<16>([&](auto Rc) {
-        constexpr int mt = decltype(MTc)::value, r = decltype(Rc)::value, i0 = (r & 3) + 8 * (r >> 2);
+        constexpr int mt = decltype(MTc)::value, r = decltype(Rc)::value, i0 = d_row(r);
         constexpr int row0 = mt * 32 + mrow_to_pixel<Cf>(i0), row1 = mt * 32 + mrow_to_pixel<Cf>(i0 + 4);
         float* const q = obase + (row0 + g * (row1 - row0)) * Cf::EPI_STRIDE;
 #pragma unroll
@@ -490,8 +482,7 @@ __global__ __launch_bounds__(2 * HDN_BLOCK) void conv3x3_kernel(const float* __r
       } else {
         v = v + *reinterpret_cast<const f4*>(bias + nb * BN + c4 * 4);
         if (RES) v = v + rv[q];
-        v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-        *reinterpret_cast<f4*>(out + m * C + nb * BN + c4 * 4) = v;
+        *reinterpret_cast<f4*>(out + m * C + nb * BN + c4 * 4) = relu4(v);
       }
     }
   }
@@ -501,7 +492,7 @@ __global__ __launch_bounds__(2 * HDN_BLOCK) void conv3x3_kernel(const float* __r
       float* const obase = sO + wm * MT * 32 * Cf::EPI_STRIDE + wn * NT * 32 + li;
       static_for<MT>([&](auto MTc) {
         static_for<16>([&](auto Rc) {
-          constexpr int mt = decltype(MTc)::value, r = decltype(Rc)::value, i0 = (r & 3) + 8 * (r >> 2);
+          constexpr int mt = decltype(MTc)::value, r = decltype(Rc)::value, i0 = d_row(r);
           constexpr int row0 = mt * 32 + mrow_to_pixel<Cf>(i0), row1 = mt * 32 + mrow_to_pixel<Cf>(i0 + 4);
           float* const q = obase + (row0 + g * (row1 - row0)) * Cf::EPI_STRIDE;
 #pragma unroll
@@ -522,7 +513,7 @@ __global__ __launch_bounds__(2 * HDN_BLOCK) void conv3x3_kernel(const float* __r
 }
 
 // out = relu(bias + sum over the K slices, in slice order (deterministic) (+ residual)): 16 bytes per lane.  ACT = false: the plain
-// sum (the downsample branch).
+// sum (the downsample branch).  Deliberately not finish_slices (epilogue.hip): sixteen slice loads in flight for the B = 1 chain, residual slices, a capped grid.
 template <bool RES, bool ACT>
 __global__ __launch_bounds__(HDN_BLOCK) void conv3x3_reduce_kernel(const f4* __restrict__ ws, const f4* __restrict__ bias, const f4* __restrict__ res,
                                                                    f4* __restrict__ out, unsigned n4, unsigned c4n, int slices, int res_slices) {
@@ -547,7 +538,7 @@ __global__ __launch_bounds__(HDN_BLOCK) void conv3x3_reduce_kernel(const f4* __r
     if (ACT) {
       v = v + bv;
       if (RES) v = v + rv;
-      v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+      v = relu4(v);
     }
     out[i] = v;
   }
@@ -750,14 +741,11 @@ __global__ __launch_bounds__(2 * HDN_BLOCK) void conv3x3_v2_kernel(const float* 
         const int item = tid + q * HDN_BLOCK;
         if (item < Cf::AITEMS) {
           const int px = item / (2 * KS), sub = item % (2 * KS);
-          unsigned q0[4], q1[4];
-          split2x2<SD>(av[q][0].x, av[q][0].y, q0[0], q1[0]);
-          split2x2<SD>(av[q][0].z, av[q][0].w, q0[1], q1[1]);
-          split2x2<SD>(av[q][1].x, av[q][1].y, q0[2], q1[2]);
-          split2x2<SD>(av[q][1].z, av[q][1].w, q0[3], q1[3]);
+          u32x4 p0, p1;
+          split8<SD>(av[q][0], av[q][1], p0, p1);
           unsigned char* dst = smem + ab * Cf::A_BYTES + sub * Cf::KG_BYTES + px * 16;
-          *reinterpret_cast<u32x4*>(dst) = u32x4{q0[0], q0[1], q0[2], q0[3]};
-          *reinterpret_cast<u32x4*>(dst + Cf::PIECE_BYTES) = u32x4{q1[0], q1[1], q1[2], q1[3]};
+          *reinterpret_cast<u32x4*>(dst) = p0;
+          *reinterpret_cast<u32x4*>(dst + Cf::PIECE_BYTES) = p1;
         }
       }
     };
@@ -790,8 +778,7 @@ __global__ __launch_bounds__(2 * HDN_BLOCK) void conv3x3_v2_kernel(const float* 
           } else {
             v = v + *reinterpret_cast<const f4*>(bias + nb * BN + c4 * 4);
             if (RES) v = v + rv[q];
-            v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-            *reinterpret_cast<f4*>(out + m * C + nb * BN + c4 * 4) = v;
+            *reinterpret_cast<f4*>(out + m * C + nb * BN + c4 * 4) = relu4(v);
           }
         }
       }
@@ -935,13 +922,13 @@ __global__ __launch_bounds__(2 * HDN_BLOCK) void conv3x3_v2_kernel(const float* 
     }
     // ---- this wave's partial tile -> LDS.  One tile per workgroup: over the images (every consumer has passed the last chunk's barrier after
     // its last read); several: into their own region, which the producers emptied during this tile's first chunk.
-    // C/D layout of v_mfma_f32_32x32x16_f16: col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5).  The pixel of accumulator row r
-    // is a compile-time constant for each of the two half waves: one multiply-add per store, not the mapping's dozen integer operations.
+    // The pixel of accumulator row d_row(r, g) is a compile-time constant for each of the two half waves: one multiply-add per store, not the
+    // mapping's dozen integer operations.
     HDN_ABL_CONV3X3_14_BEGIN
     float* const rbase = red + (wk * BM + wm * 64) * Cf::EPI_STRIDE + li;
     static_for<2>([&](auto MTc) {
       static_for<16>([&](auto Rc) {
-        constexpr int mt = decltype(MTc)::value, r = decltype(Rc)::value, i0 = (r & 3) + 8 * (r >> 2);
+        constexpr int mt = decltype(MTc)::value, r = decltype(Rc)::value, i0 = d_row(r);
         constexpr int row0 = mt * 32 + mrow_to_pixel_s1<S>(i0), row1 = mt * 32 + mrow_to_pixel_s1<S>(i0 + 4);
         float* const q = rbase + (row0 + g * (row1 - row0)) * Cf::EPI_STRIDE;
 #pragma unroll
@@ -1068,8 +1055,9 @@ extern "C" int hdn_conv3x3_bias_relu_f32(const float* x, const void* wpacked, co
   if (const int rr = hdn::check_fp16_range(x, (long long)B * S * S * C, s, act_domain)) return rr;
   return cv_dispatch(S, C, 1, B, [&](auto cfg) {
     const size_t wb = workspace_bytes > 0 ? (size_t)workspace_bytes : 0;
-    return act_domain ? hdn::cv::launch<decltype(cfg), true>(x, wpacked, bias, residual, out, nullptr, workspace, wb, B, s)
-                      : hdn::cv::launch<decltype(cfg), false>(x, wpacked, bias, residual, out, nullptr, workspace, wb, B, s);
+    return hdn::mc::by_domain(act_domain, [&](auto sd) {
+      return hdn::cv::launch<decltype(cfg), decltype(sd)::value>(x, wpacked, bias, residual, out, nullptr, workspace, wb, B, s);
+    });
   });
 }
 
@@ -1085,8 +1073,9 @@ extern "C" int hdn_conv3x3s2_ds_f32(const float* x, const void* wpacked, const f
   if (const int rr = hdn::check_fp16_range(x, (long long)B * S * S * CI * 4, s, act_domain)) return rr;
   return cv_dispatch(S, CI, 2, B, [&](auto cfg) {
     const size_t wb = workspace_bytes > 0 ? (size_t)workspace_bytes : 0;
-    return act_domain ? hdn::cv::launch<decltype(cfg), true>(x, wpacked, bias, nullptr, out, out_ds, workspace, wb, B, s)
-                      : hdn::cv::launch<decltype(cfg), false>(x, wpacked, bias, nullptr, out, out_ds, workspace, wb, B, s);
+    return hdn::mc::by_domain(act_domain, [&](auto sd) {
+      return hdn::cv::launch<decltype(cfg), decltype(sd)::value>(x, wpacked, bias, nullptr, out, out_ds, workspace, wb, B, s);
+    });
   });
 }
 
@@ -1140,8 +1129,9 @@ extern "C" int hdn_conv3x3_v2_f32(const float* x, const void* wpacked, const flo
   if (const int rr = hdn::check_fp16_range(x, (long long)B * S * S * C, s, act_domain)) return rr;
   return cv2_dispatch(S, C, [&](auto cfg) {
     const size_t wb = workspace_bytes > 0 ? (size_t)workspace_bytes : 0;
-    return act_domain ? hdn::cv::launch_v2<decltype(cfg), true>(x, wpacked, bias, residual, out, workspace, wb, B, s)
-                      : hdn::cv::launch_v2<decltype(cfg), false>(x, wpacked, bias, residual, out, workspace, wb, B, s);
+    return hdn::mc::by_domain(act_domain, [&](auto sd) {
+      return hdn::cv::launch_v2<decltype(cfg), decltype(sd)::value>(x, wpacked, bias, residual, out, workspace, wb, B, s);
+    });
   });
 }
 
@@ -1170,8 +1160,9 @@ extern "C" int hdn_conv3x3_chain_f32(const float* x, int x_slices, const float* 
     if (const int rr = hdn::check_fp16_range(x, n_in, s, act_domain)) return rr;
   const hdn::cv::LazyIn lz{x_bias, x_res, x_out, x_slices, res_slices};
   return cv_dispatch(S, CI, stride, B, [&](auto cfg) {
-    return act_domain ? hdn::cv::launch_chain<decltype(cfg), true>(x, lz, wpacked, out_slices, out_ds_slices, B, s)
-                      : hdn::cv::launch_chain<decltype(cfg), false>(x, lz, wpacked, out_slices, out_ds_slices, B, s);
+    return hdn::mc::by_domain(act_domain, [&](auto sd) {
+      return hdn::cv::launch_chain<decltype(cfg), decltype(sd)::value>(x, lz, wpacked, out_slices, out_ds_slices, B, s);
+    });
   });
 }
 

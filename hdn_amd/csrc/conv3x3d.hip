@@ -22,7 +22,7 @@
 //   B  Cfg<1, 2, 4, 1>   128 pixels x  64 channels   problems that would not give form C one workgroup per CU
 //   C  Cfg<2, 2, 2, 2>   128 pixels x 128 channels   CO a multiple of 128 and at least FILL such workgroups (64 x 64 per wave: half the loads per MFMA)
 // A and B with fewer than FILL workgroups (the tracker's B = 1) split K over grid.y into Z slices of whole steps; every slice writes its joined partial
-// tile to `workspace` [z][M][CO] and conv3x3d_finish_kernel adds the slices in slice order with the bias and the ReLU: deterministic, no atomics.
+// tile to `workspace` [z][M][CO] and finish_slices (epilogue.hip) adds the slices in slice order with the bias and the ReLU: deterministic, no atomics.
 //
 // hdn_conv3x3v_f32 (further down) is the same kernel with another pixel map (template parameter VALID): padding 0, stride s = 1 / 2,
 //   out[B,So,So,CO] = epilogue( conv3x3(x[B,S,S,CI]; stride s, dilation 1, no padding) ),   So = (S - 3) / s + 1,   M = B So^2
@@ -125,24 +125,10 @@ __global__ __launch_bounds__(256) void conv3x3d_kernel(const float* __restrict__
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
-      for (int i = 0; i < MT; ++i) {
-        unsigned q0[4], q1[4];                                              // the two pieces of channels 16 g + 8 t + [0, 8)
-        const f4 u = xv[i][2 * t], v = xv[i][2 * t + 1];
-        split2<SD>(f2{u.x, u.y}, q0[0], q1[0]);
-        split2<SD>(f2{u.z, u.w}, q0[1], q1[1]);
-        split2<SD>(f2{v.x, v.y}, q0[2], q1[2]);
-        split2<SD>(f2{v.z, v.w}, q0[3], q1[3]);
-        const u32x4 a0{q0[0], q0[1], q0[2], q0[3]}, a1{q1[0], q1[1], q1[2], q1[3]};
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-          hi[i][j] = mfma(a0, wv[j][2 * t], hi[i][j]);
-          lo[i][j] = mfma(a0, wv[j][2 * t + 1], lo[i][j]);
-          lo[i][j] = mfma(a1, wv[j][2 * t], lo[i][j]);
-        }
-      }
+      for (int i = 0; i < MT; ++i) mma_kstep<SD>(t, xv[i], wv, hi[i], lo[i]);
   }
 
-  // epilogue: register r of a lane is pixel m0 + 32 i + (r & 3) + 8 (r >> 2) + 4 g, output channel 32 (nt0 + j) + li
+  // epilogue: register r of a lane is pixel m0 + 32 i + d_row(r, g), output channel 32 (nt0 + j) + li
   float* o = FINAL ? dst : dst + (size_t)blockIdx.y * M * CO;
 #pragma unroll
   for (int j = 0; j < NT; ++j) {
@@ -152,7 +138,7 @@ __global__ __launch_bounds__(256) void conv3x3d_kernel(const float* __restrict__
     for (int i = 0; i < MT; ++i)
 #pragma unroll
       for (int rr = 0; rr < 16; ++rr) {
-        const int mm = m0 + 32 * i + (rr & 3) + 8 * (rr >> 2) + 4 * g;
+        const int mm = m0 + 32 * i + d_row(rr, g);
         if (mm < M) {
           float v = join<SD>(hi[i][j][rr], lo[i][j][rr]);
           if (FINAL) {
@@ -163,18 +149,6 @@ __global__ __launch_bounds__(256) void conv3x3d_kernel(const float* __restrict__
         }
       }
   }
-}
-
-// out = [relu](slice 0 + slice 1 + ... (+ bias)), in slice order; n4 = M CO / 4 (16-byte items), CO a multiple of 4
-__global__ __launch_bounds__(HDN_BLOCK) void conv3x3d_finish_kernel(const f4* __restrict__ ws, const float* __restrict__ bias, f4* __restrict__ out,
-                                                                   long long n4, int CO, int Z, int relu) {
-  const long long i = (long long)blockIdx.x * HDN_BLOCK + threadIdx.x;
-  if (i >= n4) return;
-  f4 v = ws[i];
-  for (int z = 1; z < Z; ++z) v = v + ws[(long long)z * n4 + i];
-  if (bias) v = v + *reinterpret_cast<const f4*>(bias + (int)((i * 4) % CO));
-  if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-  out[i] = v;
 }
 
 // K steps per slice for a form that gives `wgs` workgroups over `steps` K steps (steps: one slice, no workspace)
@@ -209,10 +183,7 @@ static int launch(const float* x, const void* wp, const float* bias, float* out,
   }
   hipLaunchKernelGGL((conv3x3d_kernel<C, SD, false, VALID>), grid, dim3(256), 0, s, x, w, bias, ws, M, S, So, d, CI, CO, relu, tm, sps);
   if (const int rc = launch_status()) return rc;
-  const long long n4 = (long long)M * CO / 4;
-  hipLaunchKernelGGL(conv3x3d_finish_kernel, dim3((unsigned)((n4 + HDN_BLOCK - 1) / HDN_BLOCK)), dim3(HDN_BLOCK), 0, s, reinterpret_cast<const f4*>(ws),
-                     bias, reinterpret_cast<f4*>(out), n4, CO, Z, relu);
-  return launch_status();
+  return finish_slices(ws, Z, bias, relu, out, (long long)M * CO, CO, s);
 }
 
 // HDN_OK, or what the entry points answer for a shape they do not take.  step: the dilation (1 / 2 / 4: stride 1, padding = dilation) or, VALID, the stride
@@ -258,18 +229,14 @@ static int run(const float* x, const void* wpacked, const float* bias, float* ou
   const long long nout = M * CO;
   if (bytes_overlap(out, nout * 4, x, nx * 4)) return HDN_E_ALIAS;
   if (!aligned16(x) || !aligned16(wpacked) || !aligned16(out) || (bias && !aligned16(bias))) return HDN_E_LIMIT;
-  const long long need = workspace(VALID, B, S, CI, CO, step);
-  if (need > 0) {
-    if (!ws) return HDN_E_NULL;
-    if (!aligned16(ws) || ws_bytes < need) return HDN_E_LIMIT;
-    if (bytes_overlap(ws, need, x, nx * 4) || bytes_overlap(ws, need, out, nout * 4)) return HDN_E_ALIAS;
-  }
+  if (const int rc = check_workspace(ws, ws_bytes, workspace(VALID, B, S, CI, CO, step), x, nx * 4, out, nout * 4)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (const int rr = check_fp16_range(x, nx, s, act_domain)) return rr;
   return (int)dispatch(M, CI, CO, [&](auto cfg, int sps) -> long long {
     using C = decltype(cfg);
-    return act_domain ? launch<C, true, VALID>(x, wpacked, bias, out, static_cast<float*>(ws), (int)M, S, So, step, CI, CO, relu, sps, s)
-                      : launch<C, false, VALID>(x, wpacked, bias, out, static_cast<float*>(ws), (int)M, S, So, step, CI, CO, relu, sps, s);
+    return by_domain(act_domain, [&](auto sd) {
+      return launch<C, decltype(sd)::value, VALID>(x, wpacked, bias, out, static_cast<float*>(ws), (int)M, S, So, step, CI, CO, relu, sps, s);
+    });
   });
 }
 

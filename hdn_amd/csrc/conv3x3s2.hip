@@ -34,14 +34,14 @@
 #endif
 
 namespace hdn {
-namespace cvs {
+namespace s2 {
 using namespace hdn::mc;
 
-template <int SO_, int CI_>
-struct CfgS {
-  static constexpr int SO = SO_, CI = CI_, CO = 2 * CI_, SI = 2 * SO_;
-  static constexpr int BM = 64, BN = 64, NT = 2, KS = 2, WK = 2, WM = 2, NP = 2;
-  static_assert(SO == 16 || SO == 8 || SO == 4, "the trunk's three stride-2 stages");
+// The LDS image of both kernels of this file: a chunk of 16 KS input channels of the (2R + 1) x (2 SO + 1) input patch of a tile of 64 output pixels,
+// as [piece][k step][k half][pixel slot] x 16 B, the even padded columns of a row before the odd ones.
+template <int SO_, int KS_>
+struct Image {
+  static constexpr int SO = SO_, SI = 2 * SO_, KS = KS_, BM = 64, BN = 64;
   static constexpr int IMGS = BM > SO * SO ? BM / (SO * SO) : 1;     // images per tile (4 x 4 outputs: four)
   static constexpr int R = BM / (SO * IMGS);                         // output rows of an image in the tile
   static constexpr int PH = 2 * R + 1;                               // padded input rows (one row of padding above, none needed below)
@@ -51,28 +51,100 @@ struct CfgS {
   static constexpr int PW = SO == 16 ? 33 : SO == 8 ? 20 : 10;
   static_assert(PW >= NE + NO, "row pitch");
   static constexpr int IPITCH = PH * PW, LPV = IMGS * IPITCH;
-  static constexpr int LP = LPV + (4 - LPV % 16 + 16) % 16;          // = 4 mod 16: the four k groups a producer pass writes land on distinct banks
-  static constexpr int KG_BYTES = LP * 16, KSTEP_BYTES = 2 * KG_BYTES, PIECE_BYTES = KS * KSTEP_BYTES, A_BYTES = NP * PIECE_BYTES;
-  static constexpr int NCHUNK = CI / (16 * KS), NB = CO / BN;
+  static constexpr int LP = LPV + (4 - LPV % 16 + 16) % 16;          // = 4 mod 16: the four k groups a staging pass writes land on distinct banks
+  static constexpr int KG_BYTES = LP * 16, KSTEP_BYTES = 2 * KG_BYTES, PIECE_BYTES = KS * KSTEP_BYTES, A_BYTES = 2 * PIECE_BYTES;
+  static constexpr int EPI_STRIDE = BN + 4;
+  // byte offset in an image of tile pixel p's tap (0, 0) = padded (2 yy, 2 xx), k half g (MFMA row = lane & 31: p = 32 x the wave's pixel half + li)
+  static __device__ __forceinline__ int aoff(int p, int g) {
+    const int img = p / (R * SO), yy = (p / SO) % R, xx = p % SO;
+    return g * KG_BYTES + (img * IPITCH + 2 * yy * PW + xx) * 16;
+  }
+};
+
+// HDN_BLOCK threads stage a chunk: global -> registers (load_a) -> split -> image (store_a).  An item = (pixel slot, 8-channel group of the chunk): its
+// source offset, validity and LDS address do not depend on the chunk and are worked out once (two divisions by constants per item and chunk otherwise:
+// with producer waves, their instruction stream is what paces a chunk, not the loads' latency).  What the two kernels choose (Cf):
+//   PAD_SLOTS  the items cover the LP - LPV padding slots as well (stored as zeros) and are addressed by item; otherwise by the (clamped) pixel slot
+//   ASETS      register sets: a chunk's pixels may be asked for ASETS chunks before they are split
+template <class Cf, bool SD>
+struct Stager {
+  static constexpr int KS = Cf::KS, AITEMS = (Cf::PAD_SLOTS ? Cf::LP : Cf::LPV) * 2 * KS, AITER = cdiv(AITEMS, HDN_BLOCK);
+  using Set0 = std::integral_constant<int, 0>;
+  uint32_t a_src[AITER], a_dst[AITER];
+  bool a_ok[AITER];
+  f4 av[Cf::ASETS][AITER][2];
+  const int tid;
+
+  // the tile's first image b0 and output row y0 of B images
+  __device__ __forceinline__ Stager(int tid_, int b0, int y0, int B) : tid(tid_) {
+#pragma unroll
+    for (int q = 0; q < AITER; ++q) {
+      const int item = tid + q * HDN_BLOCK, slot = item / (2 * KS), sub = item % (2 * KS);
+      const int px = min(slot, Cf::LPV - 1);
+      const int img = px / Cf::IPITCH, ry = (px % Cf::IPITCH) / Cf::PW, sl = px % Cf::IPITCH % Cf::PW;
+      const int pc = sl < Cf::NE ? 2 * sl : 2 * (sl - Cf::NE) + 1;                 // padded column of the slot
+      const int b = b0 + img, y = 2 * y0 + ry - 1, xx = pc - 1;
+      a_ok[q] = item < AITEMS && (!Cf::PAD_SLOTS || slot < Cf::LPV) && sl < Cf::NE + Cf::NO && b < B && y >= 0 && y < Cf::SI && xx >= 0 && xx < Cf::SI;
+      a_src[q] = a_ok[q] ? (uint32_t)(((b * Cf::SI + y) * Cf::SI + xx) * Cf::CI + sub * 8) : 0u;   // (floats; the whole input is < 2^31 of them)
+      a_dst[q] = (uint32_t)(sub * Cf::KG_BYTES + (Cf::PAD_SLOTS ? slot : px) * 16);
+    }
+  }
+  template <class SetC = Set0>
+  __device__ __forceinline__ void load_a(const float* __restrict__ x, int chunk, SetC = {}) {
+    HDN_ABL_CONV3X3S2_0()
+#pragma unroll
+    for (int q = 0; q < AITER; ++q) {
+      const f4* src = reinterpret_cast<const f4*>(x + a_src[q] + chunk * (16 * KS));
+      av[SetC::value][q][0] = a_ok[q] ? src[0] : f4{0.f, 0.f, 0.f, 0.f};
+      av[SetC::value][q][1] = a_ok[q] ? src[1] : f4{0.f, 0.f, 0.f, 0.f};
+    }
+  }
+  template <class SetC = Set0>
+  __device__ __forceinline__ void store_a(unsigned char* image, SetC = {}) {
+#pragma unroll
+    for (int q = 0; q < AITER; ++q) {
+      if (tid + q * HDN_BLOCK < AITEMS) {
+        u32x4 p0, p1;
+        split8<SD>(av[SetC::value][q][0], av[SetC::value][q][1], p0, p1);
+        unsigned char* dst = image + a_dst[q];
+        *reinterpret_cast<u32x4*>(dst) = p0;
+        *reinterpret_cast<u32x4*>(dst + Cf::PIECE_BYTES) = p1;
+      }
+    }
+  }
+};
+
+}  // namespace s2
+
+namespace cvs {
+using namespace hdn::mc;
+
+template <int SO_, int CI_>
+struct CfgS : s2::Image<SO_, 2> {
+  using Img = s2::Image<SO_, 2>;
+  static constexpr int CI = CI_, CO = 2 * CI_;
+  static constexpr int NT = 2, WK = 2, WM = 2, NP = 2;
+  static_assert(SO_ == 16 || SO_ == 8 || SO_ == 4, "the trunk's three stride-2 stages");
+  static constexpr bool PAD_SLOTS = true;
+  static constexpr int ASETS = 2;
+  static constexpr int NCHUNK = CI / (16 * Img::KS), NB = CO / Img::BN;
   static constexpr int NS = 10;                                      // steps of a wave per chunk: nine taps + the downsample branch
   static constexpr int BSETS = 5, PF = BSETS - 1;                    // B register sets: a step's fragments travel PF steps ahead
   static_assert(NS % BSETS == 0 && NS % 2 == 0, "register sets rotate with the step");
   static constexpr int WSTEP = NT * NP * 64;                         // 16-byte words of one wave step: [n tile][piece][lane]
   static constexpr int WCHUNK = WK * NS * WSTEP;                     // ... of one (channel block, chunk): [k step][step]
-  static constexpr int EPI_STRIDE = BN + 4;
-  static constexpr int RED_FLOATS = WK * BM * EPI_STRIDE;            // one output's partial tiles
+  static constexpr int RED_FLOATS = WK * Img::BM * Img::EPI_STRIDE;  // one output's partial tiles
   static constexpr int RED_BYTES = 2 * RED_FLOATS * 4;
-  static constexpr int LDS_BYTES = 2 * A_BYTES > RED_BYTES ? 2 * A_BYTES : RED_BYTES;
-  static_assert(LDS_BYTES <= 160 * 1024 && 2 * A_BYTES < 65536 * 2, "LDS");
-  static constexpr int AITEMS = LP * 2 * KS, AITER = cdiv(AITEMS, HDN_BLOCK);
-  static constexpr int E4 = BM * (BN / 4), EITER = E4 / HDN_BLOCK;
+  static constexpr int LDS_BYTES = 2 * Img::A_BYTES > RED_BYTES ? 2 * Img::A_BYTES : RED_BYTES;
+  static_assert(LDS_BYTES <= 160 * 1024 && 2 * Img::A_BYTES < 65536 * 2, "LDS");
+  static constexpr int E4 = Img::BM * (Img::BN / 4), EITER = E4 / HDN_BLOCK;
   static_assert(E4 % HDN_BLOCK == 0, "epilogue items");
 };
 
 template <class Cf, bool SD = false>
 __global__ __launch_bounds__(2 * HDN_BLOCK) void conv3x3s2_v2_kernel(const float* __restrict__ x, const u32x4* __restrict__ wp, const float* __restrict__ bias,
                                                                  float* __restrict__ out, float* __restrict__ out_ds, int B) {
-  constexpr int SO = Cf::SO, SI = Cf::SI, CI = Cf::CI, CO = Cf::CO, BM = Cf::BM, BN = Cf::BN, KS = Cf::KS, WK = Cf::WK, NS = Cf::NS, NT = Cf::NT, PF = Cf::PF;
+  constexpr int SO = Cf::SO, CO = Cf::CO, BM = Cf::BM, BN = Cf::BN, WK = Cf::WK, NS = Cf::NS, NT = Cf::NT, PF = Cf::PF;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x & (HDN_BLOCK - 1), lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -89,61 +161,20 @@ __global__ __launch_bounds__(2 * HDN_BLOCK) void conv3x3s2_v2_kernel(const float
     // two register sets: a chunk's pixels are asked for TWO chunks before they are split into the LDS image (a chunk is 10 steps of 6 MFMAs = under a
     // microsecond, less than a round trip to the previous launch's output).  Measured: no change against one set - what a chunk costs here is the
     // producers' own instruction stream (address arithmetic + 32 conversions per item, 6 items per thread: ablations in profiles/round5_conv3x3.txt)
-    f4 av[2][Cf::AITER][2];
-    // an item = (pixel slot, 8-channel group of the chunk): its source offset, validity and LDS address do not depend on the chunk - worked out once
-    // (two divisions by constants per item and chunk otherwise: the producers' instruction stream is what paces a chunk, not the loads' latency)
-    uint32_t a_src[Cf::AITER], a_dst[Cf::AITER];
-    bool a_ok[Cf::AITER];
-#pragma unroll
-    for (int q = 0; q < Cf::AITER; ++q) {
-      const int item = tid + q * HDN_BLOCK;
-      const int px = min(item / (2 * KS), Cf::LPV - 1), sub = item % (2 * KS);
-      const int img = px / Cf::IPITCH, ry = (px % Cf::IPITCH) / Cf::PW, sl = px % Cf::IPITCH % Cf::PW;
-      const int pc = sl < Cf::NE ? 2 * sl : 2 * (sl - Cf::NE) + 1;                 // padded column of the slot
-      const int b = b0 + img, y = 2 * y0 + ry - 1, xx = pc - 1;
-      a_ok[q] = item < Cf::AITEMS && item / (2 * KS) < Cf::LPV && sl < Cf::NE + Cf::NO && b < B && y >= 0 && y < SI && xx >= 0 && xx < SI;
-      a_src[q] = a_ok[q] ? (uint32_t)(((b * SI + y) * SI + xx) * CI + sub * 8) : 0u;       // (floats; the whole input is < 2^31 of them)
-      a_dst[q] = (uint32_t)((item % (2 * KS)) * Cf::KG_BYTES + (item / (2 * KS)) * 16);
-    }
-    auto load_a = [&](int chunk, auto SETc) {
-      constexpr int set = decltype(SETc)::value;
-      HDN_ABL_CONV3X3S2_0()
-#pragma unroll
-      for (int q = 0; q < Cf::AITER; ++q) {
-        const f4* src = reinterpret_cast<const f4*>(x + a_src[q] + chunk * (16 * KS));
-        av[set][q][0] = a_ok[q] ? src[0] : f4{0.f, 0.f, 0.f, 0.f};
-        av[set][q][1] = a_ok[q] ? src[1] : f4{0.f, 0.f, 0.f, 0.f};
-      }
-    };
-    auto store_a = [&](int ab, auto SETc) {
-      constexpr int set = decltype(SETc)::value;
-#pragma unroll
-      for (int q = 0; q < Cf::AITER; ++q) {
-        if (tid + q * HDN_BLOCK < Cf::AITEMS) {
-          unsigned q0[4], q1[4];
-          split2x2<SD>(av[set][q][0].x, av[set][q][0].y, q0[0], q1[0]);
-          split2x2<SD>(av[set][q][0].z, av[set][q][0].w, q0[1], q1[1]);
-          split2x2<SD>(av[set][q][1].x, av[set][q][1].y, q0[2], q1[2]);
-          split2x2<SD>(av[set][q][1].z, av[set][q][1].w, q0[3], q1[3]);
-          unsigned char* dst = smem + ab * Cf::A_BYTES + a_dst[q];
-          *reinterpret_cast<u32x4*>(dst) = u32x4{q0[0], q0[1], q0[2], q0[3]};
-          *reinterpret_cast<u32x4*>(dst + Cf::PIECE_BYTES) = u32x4{q1[0], q1[1], q1[2], q1[3]};
-        }
-      }
-    };
+    s2::Stager<Cf, SD> stager(tid, b0, y0, B);
     using S0 = std::integral_constant<int, 0>;
     using S1 = std::integral_constant<int, 1>;
-    load_a(0, S0{});
-    if (Cf::NCHUNK > 1) load_a(1, S1{});
-    store_a(0, S0{});
-    if (Cf::NCHUNK > 2) load_a(2, S0{});
+    stager.load_a(x, 0, S0{});
+    if (Cf::NCHUNK > 1) stager.load_a(x, 1, S1{});
+    stager.store_a(smem, S0{});
+    if (Cf::NCHUNK > 2) stager.load_a(x, 2, S0{});
     __syncthreads();                                   // chunk 0 is staged
     static_for<Cf::NCHUNK>([&](auto Cc) {              // chunk c + 1 -> its image (read last in chunk c - 1, one barrier ago); chunk c + 3 on its way
       constexpr int c = decltype(Cc)::value;
       using Set = std::integral_constant<int, (c + 1) & 1>;
       if constexpr (c + 1 < Cf::NCHUNK) {
-        store_a((c + 1) & 1, Set{});
-        if constexpr (c + 3 < Cf::NCHUNK) load_a(c + 3, Set{});
+        stager.store_a(smem + ((c + 1) & 1) * Cf::A_BYTES, Set{});
+        if constexpr (c + 3 < Cf::NCHUNK) stager.load_a(x, c + 3, Set{});
       }
       __syncthreads();                                 // chunk c + 1 is staged; the consumers have read the last fragment of chunk c
     });
@@ -162,10 +193,7 @@ __global__ __launch_bounds__(2 * HDN_BLOCK) void conv3x3s2_v2_kernel(const float
           f4 v = *reinterpret_cast<const f4*>(rd + px * Cf::EPI_STRIDE + c4 * 4);
 #pragma unroll
           for (int w = 1; w < WK; ++w) v = v + *reinterpret_cast<const f4*>(rd + (w * BM + px) * Cf::EPI_STRIDE + c4 * 4);
-          if (o == 0) {
-            v = v + *reinterpret_cast<const f4*>(bias + nb * BN + c4 * 4);
-            v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-          }
+          if (o == 0) v = relu4(v + *reinterpret_cast<const f4*>(bias + nb * BN + c4 * 4));
           *reinterpret_cast<f4*>(dst + m * CO + nb * BN + c4 * 4) = v;
         }
       }
@@ -175,12 +203,7 @@ __global__ __launch_bounds__(2 * HDN_BLOCK) void conv3x3s2_v2_kernel(const float
 
   // -------------------------------------------------------------------------------------------------- consumers
   const int wm = wave / WK, wk = wave % WK;
-  uint32_t aoff;
-  {
-    const int p = wm * 32 + li;                               // pixel inside the workgroup's tile (MFMA row = lane & 31)
-    const int img = p / (Cf::R * SO), yy = (p / SO) % Cf::R, xx = p % SO;
-    aoff = lds_addr(smem) + g * Cf::KG_BYTES + wk * Cf::KSTEP_BYTES + (img * Cf::IPITCH + 2 * yy * Cf::PW + xx) * 16;   // tap (0, 0): padded (2 yy, 2 xx)
-  }
+  const uint32_t aoff = lds_addr(smem) + wk * Cf::KSTEP_BYTES + Cf::aoff(wm * 32 + li, g);   // this lane's A row, tap (0, 0), the wave's k step
   f32x16 acc[NT], accl[NT], dacc[NT], daccl[NT];
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt)
@@ -258,10 +281,9 @@ __global__ __launch_bounds__(2 * HDN_BLOCK) void conv3x3s2_v2_kernel(const float
     });
   }
   // ---- this wave's two partial tiles -> LDS, over the images (every consumer has passed the last chunk's barrier after its last read).
-  // C/D layout of v_mfma_f32_32x32x16_f16: col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5).
   float* const rbase = red + (wk * BM + wm * 32 + 4 * g) * Cf::EPI_STRIDE + li;
   static_for<16>([&](auto Rc) {
-    constexpr int r = decltype(Rc)::value, row = (r & 3) + 8 * (r >> 2);
+    constexpr int r = decltype(Rc)::value, row = d_row(r);
     float* const q = rbase + row * Cf::EPI_STRIDE;
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
@@ -308,7 +330,7 @@ extern "C" int hdn_conv3x3s2_v2_f32(const float* x, const void* wpacked, const f
   if (const int rr = hdn::check_fp16_range(x, n_in, s, act_domain)) return rr;
   auto go = [&](auto cfg) {
     using Cf = decltype(cfg);
-    return act_domain ? hdn::cvs::launch<Cf, true>(x, wpacked, bias, out, out_ds, B, s) : hdn::cvs::launch<Cf, false>(x, wpacked, bias, out, out_ds, B, s);
+    return hdn::mc::by_domain(act_domain, [&](auto sd) { return hdn::cvs::launch<Cf, decltype(sd)::value>(x, wpacked, bias, out, out_ds, B, s); });
   };
   if (S == 16 && CI == 64) return go(hdn::cvs::CfgS<16, 64>{});
   if (S == 8 && CI == 128) return go(hdn::cvs::CfgS<8, 128>{});
@@ -328,7 +350,7 @@ extern "C" int hdn_conv3x3s2_v2_f32(const float* x, const void* wpacked, const f
 // workgroups share a CU: 192-202 VGPRs + 32 AGPRs per lane, no scratch, 39-48 KB of LDS each).  Weights go L2 -> registers in fragment order, one kernel row (3 taps) ahead.  The tile leaves through
 // the LDS as 16-byte stores.
 // K slices: when the output tiles alone give fewer than FILL workgroups (the tracker's B = 1: 8 / 4 / 8 tiles; S = 8 / 4 even at B = 64) grid.z splits K —
-// first by chunks, then by kernel row — each slice writes its raw partial tile to `workspace` [z][M][C] and conv3x3s2_finish_kernel adds the slices
+// first by chunks, then by kernel row — each slice writes its raw partial tile to `workspace` [z][M][C] and finish_slices (epilogue.hip) adds the slices
 // in slice order with the bias and the ReLU: a fixed summation order, no atomics.
 // FILL = two workgroups for each of the 256 CUs (what the registers allow to be resident).  Measured with it, rocprofv3 kernel time: docs/KERNELS.md "conv3x3s2".
 #ifndef HDN_S2_FILL
@@ -340,27 +362,18 @@ namespace cb {
 using namespace hdn::mc;
 
 template <int SO_, int C_>
-struct CfgB {
-  static constexpr int SO = SO_, C = C_, SI = 2 * SO_;
-  static constexpr int BM = 64, BN = 64, KS = 2;
-  static_assert((SO == 16 && C == 128) || (SO == 8 && C == 256) || (SO == 4 && C == 512), "the three stride-2 Bottlenecks of the trunk");
-  static constexpr int IMGS = BM > SO * SO ? BM / (SO * SO) : 1;     // images per tile (4 x 4 outputs: four)
-  static constexpr int R = BM / (SO * IMGS);                         // output rows of an image in the tile
-  static constexpr int PH = 2 * R + 1;                               // padded input rows (one row of padding above, none needed below)
-  static constexpr int NE = SO + 1, NO = SO, PWH = NE;               // even / odd padded columns of a row; slot of the first odd one
-  static constexpr int PW = SO == 16 ? 33 : SO == 8 ? 20 : 10;       // row pitch in slots (bank groups: CfgS above)
-  static_assert(PW >= NE + NO, "row pitch");
-  static constexpr int IPITCH = PH * PW, LPV = IMGS * IPITCH;
-  static constexpr int LP = LPV + (4 - LPV % 16 + 16) % 16;          // = 4 mod 16: the four k groups of a pixel land on distinct banks
-  static constexpr int KG_BYTES = LP * 16, KSTEP_BYTES = 2 * KG_BYTES, PIECE_BYTES = KS * KSTEP_BYTES, A_BYTES = 2 * PIECE_BYTES;
-  static constexpr int NCHUNK = C / (16 * KS), NB = C / BN;
-  static constexpr int WTAP = 2 * KS * 2 * 64;                       // 16-byte words of one (channel block, chunk, tap): [n tile][k step][piece][lane]
-  static constexpr int EPI_STRIDE = BN + 4;
-  static constexpr int RED_BYTES = BM * EPI_STRIDE * 4;
-  static constexpr int LDS_BYTES = A_BYTES > RED_BYTES ? A_BYTES : RED_BYTES;
+struct CfgB : s2::Image<SO_, 2> {
+  using Img = s2::Image<SO_, 2>;
+  static constexpr int C = C_, CI = C_;
+  static_assert((SO_ == 16 && C == 128) || (SO_ == 8 && C == 256) || (SO_ == 4 && C == 512), "the three stride-2 Bottlenecks of the trunk");
+  static constexpr bool PAD_SLOTS = false;
+  static constexpr int ASETS = 1;
+  static constexpr int NCHUNK = C / (16 * Img::KS), NB = C / Img::BN;
+  static constexpr int WTAP = 2 * Img::KS * 2 * 64;                  // 16-byte words of one (channel block, chunk, tap): [n tile][k step][piece][lane]
+  static constexpr int RED_BYTES = Img::BM * Img::EPI_STRIDE * 4;
+  static constexpr int LDS_BYTES = Img::A_BYTES > RED_BYTES ? Img::A_BYTES : RED_BYTES;
   static_assert(LDS_BYTES <= 64 * 1024, "static LDS");
-  static constexpr int AITEMS = LPV * 2 * KS, AITER = cdiv(AITEMS, HDN_BLOCK);
-  static constexpr int EITER = BM * (BN / 4) / HDN_BLOCK;
+  static constexpr int EITER = Img::BM * (Img::BN / 4) / HDN_BLOCK;
 };
 
 // the K slices of a problem: ZC slices of the chunks x ZT (1 or 3) of the kernel rows
@@ -380,7 +393,7 @@ static Slices slices_for(long long M) {
 template <class Cf, bool SD, bool FUSED>
 __global__ __launch_bounds__(HDN_BLOCK) void conv3x3s2_kernel(const float* __restrict__ x, const u32x4* __restrict__ wp, const float* __restrict__ bias,
                                                              float* __restrict__ dst, int B, int ZC, int ZT) {
-  constexpr int SO = Cf::SO, SI = Cf::SI, C = Cf::C, BM = Cf::BM, BN = Cf::BN, KS = Cf::KS;
+  constexpr int SO = Cf::SO, C = Cf::C, BM = Cf::BM, BN = Cf::BN, KS = Cf::KS;
   __shared__ __attribute__((aligned(16))) unsigned char smem[Cf::LDS_BYTES];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 31, g = lane >> 5, wm = wave >> 1, wn = wave & 1;
@@ -392,52 +405,8 @@ __global__ __launch_bounds__(HDN_BLOCK) void conv3x3s2_kernel(const float* __res
   const int cpz = Cf::NCHUNK / ZC, c0 = zc * cpz;             // this slice's chunks [c0, c0 + cpz) and kernel rows [ky0, ky1)
   const int ky0 = ZT == 3 ? zt : 0, ky1 = ZT == 3 ? zt + 1 : 3;
 
-  // an item = (pixel slot, 8-channel group of the chunk): source offset, validity and LDS address do not depend on the chunk
-  uint32_t a_src[Cf::AITER], a_dst[Cf::AITER];
-  bool a_ok[Cf::AITER];
-#pragma unroll
-  for (int q = 0; q < Cf::AITER; ++q) {
-    const int item = tid + q * HDN_BLOCK;
-    const int px = min(item / (2 * KS), Cf::LPV - 1), sub = item % (2 * KS);
-    const int img = px / Cf::IPITCH, ry = (px % Cf::IPITCH) / Cf::PW, sl = px % Cf::IPITCH % Cf::PW;
-    const int pc = sl < Cf::NE ? 2 * sl : 2 * (sl - Cf::NE) + 1;                 // padded column of the slot
-    const int b = b0 + img, y = 2 * y0 + ry - 1, xx = pc - 1;
-    a_ok[q] = item < Cf::AITEMS && sl < Cf::NE + Cf::NO && b < B && y >= 0 && y < SI && xx >= 0 && xx < SI;
-    a_src[q] = a_ok[q] ? (uint32_t)(((b * SI + y) * SI + xx) * C + sub * 8) : 0u;          // (floats; the whole input is < 2^31 of them)
-    a_dst[q] = (uint32_t)(sub * Cf::KG_BYTES + px * 16);
-  }
-  f4 av[Cf::AITER][2];
-  auto load_a = [&](int chunk) {
-#pragma unroll
-    for (int q = 0; q < Cf::AITER; ++q) {
-      const f4* src = reinterpret_cast<const f4*>(x + a_src[q] + chunk * (16 * KS));
-      av[q][0] = a_ok[q] ? src[0] : f4{0.f, 0.f, 0.f, 0.f};
-      av[q][1] = a_ok[q] ? src[1] : f4{0.f, 0.f, 0.f, 0.f};
-    }
-  };
-  auto store_a = [&]() {
-#pragma unroll
-    for (int q = 0; q < Cf::AITER; ++q) {
-      if (tid + q * HDN_BLOCK < Cf::AITEMS) {
-        unsigned q0[4], q1[4];
-        split2x2<SD>(av[q][0].x, av[q][0].y, q0[0], q1[0]);
-        split2x2<SD>(av[q][0].z, av[q][0].w, q0[1], q1[1]);
-        split2x2<SD>(av[q][1].x, av[q][1].y, q0[2], q1[2]);
-        split2x2<SD>(av[q][1].z, av[q][1].w, q0[3], q1[3]);
-        unsigned char* d = smem + a_dst[q];
-        *reinterpret_cast<u32x4*>(d) = u32x4{q0[0], q0[1], q0[2], q0[3]};
-        *reinterpret_cast<u32x4*>(d + Cf::PIECE_BYTES) = u32x4{q1[0], q1[1], q1[2], q1[3]};
-      }
-    }
-  };
-
-  // this lane's A row: pixel wm * 32 + li of the tile; tap (0, 0) = padded (2 yy, 2 xx)
-  int aoff;
-  {
-    const int p = wm * 32 + li;
-    const int img = p / (Cf::R * SO), yy = (p / SO) % Cf::R, xx = p % SO;
-    aoff = g * Cf::KG_BYTES + (img * Cf::IPITCH + 2 * yy * Cf::PW + xx) * 16;
-  }
+  s2::Stager<Cf, SD> stager(tid, b0, y0, B);
+  const int aoff = Cf::aoff(wm * 32 + li, g);                 // this lane's A row: pixel wm * 32 + li of the tile, tap (0, 0)
   // this wave's weight stream: [channel block][chunk][tap][n tile][k step][piece][lane] x 16 B
   const u32x4* const wbase = wp + (size_t)nb * Cf::NCHUNK * 9 * Cf::WTAP + wn * (Cf::WTAP / 2) + lane;
   u32x4 wnx[3][KS][2];
@@ -455,12 +424,12 @@ __global__ __launch_bounds__(HDN_BLOCK) void conv3x3s2_kernel(const float* __res
 #pragma unroll
   for (int r = 0; r < 16; ++r) hi[r] = lo[r] = 0.f;
 
-  load_a(c0);
+  stager.load_a(x, c0);
   load_w(c0, ky0);
   for (int c = 0; c < cpz; ++c) {
-    store_a();
+    stager.store_a(smem);
     __syncthreads();                                          // chunk c is staged
-    if (c + 1 < cpz) load_a(c0 + c + 1);
+    if (c + 1 < cpz) stager.load_a(x, c0 + c + 1);
     for (int ky = ky0; ky < ky1; ++ky) {
       u32x4 wv[3][KS][2];
 #pragma unroll
@@ -488,10 +457,10 @@ __global__ __launch_bounds__(HDN_BLOCK) void conv3x3s2_kernel(const float* __res
     __syncthreads();                                          // every wave has read chunk c's image
   }
 
-  // the tile -> LDS (over the dead image).  C/D layout of v_mfma_f32_32x32x16_f16: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+  // the tile -> LDS (over the dead image)
   float* const red = reinterpret_cast<float*>(smem);
 #pragma unroll
-  for (int r = 0; r < 16; ++r) red[(wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * g) * Cf::EPI_STRIDE + wn * 32 + li] = join<SD>(hi[r], lo[r]);
+  for (int r = 0; r < 16; ++r) red[(wm * 32 + d_row(r, g)) * Cf::EPI_STRIDE + wn * 32 + li] = join<SD>(hi[r], lo[r]);
   __syncthreads();
   float* const o = FUSED ? dst : dst + (size_t)z * (size_t)M * C;
 #pragma unroll
@@ -500,25 +469,10 @@ __global__ __launch_bounds__(HDN_BLOCK) void conv3x3s2_kernel(const float* __res
     const long long m = m0 + px;
     if (m < M) {
       f4 v = *reinterpret_cast<const f4*>(red + px * Cf::EPI_STRIDE + c4 * 4);
-      if constexpr (FUSED) {
-        v = v + *reinterpret_cast<const f4*>(bias + nb * BN + c4 * 4);
-        v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-      }
+      if constexpr (FUSED) v = relu4(v + *reinterpret_cast<const f4*>(bias + nb * BN + c4 * 4));
       *reinterpret_cast<f4*>(o + m * C + nb * BN + c4 * 4) = v;
     }
   }
-}
-
-// out = relu(slice 0 + slice 1 + ... + bias), in slice order; n4 = M C / 4 (16-byte items), C a multiple of 4
-__global__ __launch_bounds__(HDN_BLOCK) void conv3x3s2_finish_kernel(const f4* __restrict__ ws, const float* __restrict__ bias, f4* __restrict__ out,
-                                                                    long long n4, int C, int Z) {
-  const long long i = (long long)blockIdx.x * HDN_BLOCK + threadIdx.x;
-  if (i >= n4) return;
-  f4 v = ws[i];
-  for (int z = 1; z < Z; ++z) v = v + ws[(long long)z * n4 + i];
-  v = v + *reinterpret_cast<const f4*>(bias + (int)((i * 4) % C));
-  v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-  out[i] = v;
 }
 
 template <class Cf>
@@ -541,10 +495,7 @@ static int launch(const float* x, const void* wp, const float* bias, float* out,
   }
   hipLaunchKernelGGL((conv3x3s2_kernel<Cf, SD, false>), grid, blk, 0, stream, x, w, bias, ws, B, sl.zc, sl.zt);
   if (const int rc = launch_status()) return rc;
-  const long long n4 = M * Cf::C / 4;
-  hipLaunchKernelGGL(conv3x3s2_finish_kernel, dim3((unsigned)((n4 + HDN_BLOCK - 1) / HDN_BLOCK)), blk, 0, stream, reinterpret_cast<const f4*>(ws), bias,
-                     reinterpret_cast<f4*>(out), n4, Cf::C, sl.z());
-  return launch_status();
+  return finish_slices(ws, sl.z(), bias, 1, out, M * Cf::C, Cf::C, stream);
 }
 
 // f(CfgB<...>{}) for a supported (S, C), HDN_E_LIMIT otherwise
@@ -577,17 +528,11 @@ extern "C" int hdn_conv3x3s2_f32(const float* x, const void* wpacked, const floa
   if (hdn::bytes_overlap(out, n_out * 4, x, n_in * 4)) return HDN_E_ALIAS;
   for (const void* p : {(const void*)x, wpacked, (const void*)bias, (const void*)out})
     if (!hdn::aligned16(p)) return HDN_E_LIMIT;
-  const long long need = hdn_conv3x3s2_workspace_bytes(B, S, C);
-  if (need > 0) {
-    if (!workspace) return HDN_E_NULL;
-    if (!hdn::aligned16(workspace) || workspace_bytes < need) return HDN_E_LIMIT;
-    if (hdn::bytes_overlap(workspace, need, x, n_in * 4) || hdn::bytes_overlap(workspace, need, out, n_out * 4)) return HDN_E_ALIAS;
-  }
+  if (const int rc = hdn::check_workspace(workspace, workspace_bytes, hdn_conv3x3s2_workspace_bytes(B, S, C), x, n_in * 4, out, n_out * 4)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (const int rr = hdn::check_fp16_range(x, n_in, s, act_domain)) return rr;
   return (int)hdn::cb::with_cfg(S, C, [&](auto cfg) -> long long {
     using Cf = decltype(cfg);
-    return act_domain ? hdn::cb::launch<Cf, true>(x, wpacked, bias, out, workspace, B, s)
-                      : hdn::cb::launch<Cf, false>(x, wpacked, bias, out, workspace, B, s);
+    return hdn::mc::by_domain(act_domain, [&](auto sd) { return hdn::cb::launch<Cf, decltype(sd)::value>(x, wpacked, bias, out, workspace, B, s); });
   });
 }

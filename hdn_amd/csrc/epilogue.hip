@@ -37,8 +37,7 @@ __global__ __launch_bounds__(HDN_BLOCK) void bias_act_kernel(f4* __restrict__ y,
     }
     v = v + b;
     if (RES) v = v + res[i];
-    v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-    y[i] = v;
+    y[i] = mc::relu4(v);
   }
 }
 
@@ -61,6 +60,26 @@ static void launch_vec(float* y, const float* res, const float* bias, unsigned n
   const f4* r4 = reinterpret_cast<const f4*>(res);
   if (res) hipLaunchKernelGGL((bias_act_kernel<NHWC, true>), dim3(blocks), dim3(HDN_BLOCK), 0, s, y4, r4, bias, n4, C, HW4);
   else hipLaunchKernelGGL((bias_act_kernel<NHWC, false>), dim3(blocks), dim3(HDN_BLOCK), 0, s, y4, r4, bias, n4, C, HW4);
+}
+
+// finish_slices (hdn_common.h): the finish pass of a convolution whose K was split over workgroups (conv3x3s2.hip, conv3x3d.hip).
+// out = [relu](slice 0 + slice 1 + ... (+ bias)), in slice order; n4 = n / 4 (16-byte items), C a multiple of 4
+__global__ __launch_bounds__(HDN_BLOCK) void finish_slices_kernel(const f4* __restrict__ ws, const float* __restrict__ bias, f4* __restrict__ out,
+                                                                 long long n4, int C, int Z, int relu) {
+  const long long i = (long long)blockIdx.x * HDN_BLOCK + threadIdx.x;
+  if (i >= n4) return;
+  f4 v = ws[i];
+  for (int z = 1; z < Z; ++z) v = v + ws[(long long)z * n4 + i];
+  if (bias) v = v + *reinterpret_cast<const f4*>(bias + (int)((i * 4) % C));
+  if (relu) v = mc::relu4(v);
+  out[i] = v;
+}
+
+int finish_slices(const float* ws, int Z, const float* bias, int relu, float* out, long long n, int C, hipStream_t stream) {
+  const long long n4 = n / 4;
+  hipLaunchKernelGGL(finish_slices_kernel, dim3((unsigned)((n4 + HDN_BLOCK - 1) / HDN_BLOCK)), dim3(HDN_BLOCK), 0, stream, reinterpret_cast<const f4*>(ws),
+                     bias, reinterpret_cast<f4*>(out), n4, C, Z, relu);
+  return launch_status();
 }
 
 // AdaptiveAvgPool2d(1) + flatten + Linear(C, O) of the regressor's tail (homo_model_builder.py:161-165) as one launch: one

@@ -37,6 +37,10 @@ struct PerDeviceOnce {
 // hdn_set_check_range; a no-op otherwise and inside stream captures)
 int check_fp16_range(const float* x, long long n, hipStream_t stream, int act_domain = 0);   // act_domain 1: x is already x_real * 2^-8
 
+// epilogue.hip: out[n] = [relu](slice 0 + slice 1 + ... + slice Z - 1 (+ bias[i % C])) of the K slices ws[Z][n], added in slice order (deterministic);
+// bias may be NULL; n and C multiples of 4, everything 16-byte aligned.  The finish pass of the K-split forms of conv3x3s2.hip and conv3x3d.hip.
+int finish_slices(const float* ws, int Z, const float* bias, int relu, float* out, long long n, int C, hipStream_t stream);
+
 inline int launch_status() {
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? HDN_OK : -(1000 + (int)e);
@@ -142,6 +146,16 @@ __host__ __device__ __forceinline__ bool aligned16(const void* p) { return (rein
 inline bool bytes_overlap(const void* a, long long na, const void* b, long long nb) {
   const char *pa = static_cast<const char*>(a), *pb = static_cast<const char*>(b);
   return pa < pb + nb && pb < pa + na;
+}
+
+// the entry points' checks of a K-slice workspace of `need` bytes (need <= 0: none is used, nothing is checked) beside the input x and the output:
+// NULL -> HDN_E_NULL, unaligned or too small -> HDN_E_LIMIT, overlapping x or out -> HDN_E_ALIAS, in that order
+inline int check_workspace(const void* ws, long long ws_bytes, long long need, const void* x, long long x_bytes, const void* out, long long out_bytes) {
+  if (need <= 0) return HDN_OK;
+  if (!ws) return HDN_E_NULL;
+  if (!aligned16(ws) || ws_bytes < need) return HDN_E_LIMIT;
+  if (bytes_overlap(ws, need, x, x_bytes) || bytes_overlap(ws, need, out, out_bytes)) return HDN_E_ALIAS;
+  return HDN_OK;
 }
 
 typedef float float2v __attribute__((ext_vector_type(2)));

@@ -162,8 +162,8 @@ __global__ __launch_bounds__(2 * H) void head_tail_kernel(const float* __restric
       lo = mfma(a1[s][0], b1v, lo);
     }
     if (more) load_half<HK>(a1, wnext + HALF_WORDS);
-    // ---- bias + ReLU, then this lane's share of the second product.  C/D layout of v_mfma_f32_32x32x16_f16: register r of a lane holds row
-    // (r & 3) + 8 (r >> 2) + 4 g, i.e. registers 4 q .. 4 q + 3 are 4 CONSECUTIVE channels: b1 and a row of Wf are read 16 bytes at a time.
+    // ---- bias + ReLU, then this lane's share of the second product.  Register r of a lane holds row d_row(r, g) (mfma_split.h), i.e. registers
+    // 4 q .. 4 q + 3 are 4 CONSECUTIVE channels: b1 and a row of Wf are read 16 bytes at a time.
     const f4* b1l = reinterpret_cast<const f4*>(b1s + l * H + wave * 32 + 4 * g);            // + 2 q float4s: channels 8 q + 4 g ...
     const f4* wfl = reinterpret_cast<const f4*>(wfs + l * H + wave * 32 + 4 * g);            // row o of the level: + o * (n H / 4)
     f4 hv[4];

@@ -142,7 +142,7 @@ __global__ __launch_bounds__(THREADS) void simi_stem_kernel(const float* __restr
   for (int cr = 0; cr < 3; ++cr) rin[cr] = 2 * p - 1 + cr >= 0 && 2 * p - 1 + cr < Sc;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int i = 32 * ct + (r & 3) + 8 * (r >> 2) + 4 * g, col = i - 1;
+    const int i = 32 * ct + d_row(r, g), col = i - 1;
     float m = 0.f;
 #pragma unroll
     for (int cr = 0; cr < 3; ++cr) {
