@@ -199,8 +199,9 @@ def test_xcorr_unaligned_and_strided_inputs(dev):
 
 @pytest.mark.parametrize("shape,circ", [((3, 7, 61, 61, 31, 31), False), ((5, 3, 13, 13, 13, 13), True), ((2, 9, 35, 35, 5, 5), False)])
 def test_xcorr_specialised_kernels_on_unaligned_pointers(dev, shape, circ):
-    """4-byte-aligned (not 16-byte) x / k / out base pointers and ragged plane counts through every specialised kernel:
-    the all-in-flight 16-byte staging paths must fall back correctly."""
+    """4-byte-aligned (not 16-byte) x / k base pointers and ragged plane counts through every specialised kernel:
+    the all-in-flight 16-byte staging paths must fall back correctly.  (out is a fresh, 16-byte aligned allocation here;
+    unaligned results are what tests/test_gpu_xcorr_forms.py writes into.)"""
     B, C, Hx, Wx, Hk, Wk = shape
     r = np.random.default_rng(sum(shape) + 7)
     xb = relu_normal(r, (B, C, Hx, Wx)) if not circ else r.standard_normal((B, C, Hx, Wx), dtype=np.float32)
