@@ -30,6 +30,8 @@ SIGNATURES = {
         _i,
         [ctypes.POINTER(ctypes.c_void_p)] * 3 + [_i, _i] + [_i] * 6 + [ctypes.c_void_p],
     ),
+    "hdn_xcorr_depthwise_bwd_f32": (_i, [_c_float_p] * 5 + [_i] * 7 + [ctypes.c_void_p]),
+    "hdn_xcorr_bwd_form": (_i, [_i] * 5),
     "hdn_xcorr_fast_f32": (_i, [_c_float_p] * 3 + [_i] * 7 + [ctypes.c_void_p]),
     "hdn_share_feature_f32": (_i, [_c_float_p] * 3 + [_i] * 3 + [ctypes.c_void_p]),
     "hdn_dlt_solve_f32": (_i, [_c_float_p] * 3 + [_i, ctypes.c_void_p]),

@@ -610,7 +610,8 @@ def fused_forward(self, z_fs, x_fs, circular=None):
     cached template-branch features.  `self` needs box2.., (cls|loc)_weight, loc_scale, weighted.
 
     Inference only (runs under no_grad, BN in eval mode): in training mode it defers to the class's original forward
-    when install() saved one (`_hdn_orig_forward`), and raises otherwise, rather than silently dropping gradients."""
+    when install() saved one (`_hdn_orig_forward`), and raises otherwise, rather than silently dropping gradients.  The deferred
+    forward trains: the xcorr_depthwise / xcorr_depthwise_circular it resolves are differentiable (hdn_amd/xcorr.py)."""
     if self.training:
         orig = getattr(type(self), "_hdn_orig_forward", None)
         if orig is not None:

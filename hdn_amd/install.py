@@ -20,6 +20,13 @@ attribute the reference resolves at call time:
                                                          host->device copy per frame, which a hipGraph capture cannot hold)
     ModelBuilder.template                                unchanged, then drops the heads' cached template-branch features
     hdn.tracker.tracker_builder.TRACKS['hdnTrackerHomoProje2e']   (install(tracker=True)) the device-resident tracker loop
+
+Training under install(): of the drop-ins only xcorr_depthwise and xcorr_depthwise_circular are differentiable (hdn_amd/xcorr.py).  The rebound head
+forwards defer to the classes' own forward in .train() mode, so code that trains the correlation heads alone (MultiBAN / MultiCircBAN and what feeds
+them) receives every gradient.  The reference's own training forward (tools/train.py -> ModelBuilder.forward, model_builder...:333-390) does NOT run
+under install(): it passes a polar that carries the graph of the first head through STN_Polar, and the STN_Polar drop-in has no backward - it raises
+there rather than detach.  DLT_solve / transform / transformer, the fused track_proj and xcorr_fast / xcorr_slow are inference-only as well (they
+detach).  uninstall() before tools/train.py and before training the homography estimator.
 """
 from __future__ import annotations
 
@@ -128,7 +135,9 @@ def _rebind(owner, attr, value, item=False):
 
 def uninstall() -> int:
     """Undo every rebinding install() made (most recent first): the reference runs on its own PyTorch ops again, e.g.
-    for training, which the HIP drop-ins (inference only, no autograd) do not support.  Folded trunks that install(trunk=True) attached are
+    for the reference's tools/train.py or for training the homography estimator (of the drop-ins only the two depthwise correlations are
+    differentiable; STN_Polar raises on a grad-carrying input, DLT_solve / transform / transformer, the fused track_proj and xcorr_fast carry no
+    autograd graph).  Folded trunks that install(trunk=True) attached are
     detached (optimize_trunk(net, enable=False)).  Returns the number of rebindings undone."""
     n = 0
     while _trunk_nets:

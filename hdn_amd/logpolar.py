@@ -5,6 +5,9 @@
 Same constructor / forward signature and return values as the reference module.  The reference rebuilds the
 sampling grid on the CPU and uploads it on every call (logpolar.py:121,110-111); here the 1-D factors of the grid
 are cached on the device per rotation offset and the grid point is formed inside the sampling kernel.
+
+Inference only: the kernel has no backward.  With autograd recording, an x or polar that requires grad raises instead of being detached (the
+reference's module is differentiable in both, and its training forward relies on that).
 """
 from __future__ import annotations
 
@@ -29,6 +32,12 @@ def logpolar_sample(x: torch.Tensor, polar: torch.Tensor, tabs, want_grid: bool 
     """x [B,C,H,W], polar [B,2], tabs = device tensors (rho, cos, sin) of length S -> (x_lp [B,C,S,S], grid or None)."""
     if x.dim() != 4:
         raise ValueError(f"x must be [B,C,H,W], got {tuple(x.shape)}")
+    if torch.is_grad_enabled() and (x.requires_grad or polar.requires_grad):
+        # the reference's STN_Polar is differentiable in both (grid = indices + polar, then F.grid_sample), and its training forward
+        # (model_builder_e2e_unconstrained_v2.py:377-379) passes a polar that carries the graph of the first head: detaching here would let that
+        # training step run and silently lose the log-polar losses' gradient
+        raise RuntimeError("hdn_amd.STN_Polar is inference-only (its kernel has no backward) but x or polar requires grad: run inference under "
+                           "torch.no_grad(), or call hdn_amd.install.uninstall() before training so that the reference's own STN_Polar is used")
     B, C, H, W = x.shape
     rho, c, s = tabs
     S = rho.numel()
@@ -51,7 +60,7 @@ def logpolar_sample(x: torch.Tensor, polar: torch.Tensor, tabs, want_grid: bool 
 
 
 class STN_Polar(nn.Module):
-    """Drop-in for hdn.models.logpolar.STN_Polar (inference)."""
+    """Drop-in for hdn.models.logpolar.STN_Polar (inference; raises when autograd is recording and x or polar requires grad)."""
 
     def __init__(self, image_sz):
         super().__init__()

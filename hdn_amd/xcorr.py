@@ -3,9 +3,13 @@
     xcorr_depthwise(x, kernel)            <- hdn/core/xcorr.py:37-46
     xcorr_depthwise_circular(x, kernel)   <- hdn/core/xcorr.py:48-61
     xcorr_depthwise_multi(xs, kernels)    (one launch for a frame's 6 correlations)
+    xcorr_depthwise_backward(x, kernel, grad_out, circular)   the gradients of the first two (csrc/xcorr_bwd.hip)
 
-Same names, argument order and output shapes as the reference.  Inference only: results
-carry no autograd graph (the reference's inference loop never uses one).
+Same names, argument order and output shapes as the reference.  xcorr_depthwise and xcorr_depthwise_circular are
+differentiable: when autograd is recording and an input requires grad they go through a torch.autograd.Function whose forward
+is the same launch and whose backward is hdn_xcorr_depthwise_bwd_f32 (first order only: a double backward raises).  Under
+no_grad, or with inputs that require no grad, they run exactly what they ran before and the result carries no graph.
+xcorr_depthwise_multi, xcorr_fast and xcorr_slow are inference only: their results never carry an autograd graph.
 """
 from __future__ import annotations
 
@@ -53,20 +57,72 @@ def _xcorr(x: torch.Tensor, kernel: torch.Tensor, circular: bool) -> torch.Tenso
     return out
 
 
+def xcorr_depthwise_backward(x: torch.Tensor, kernel: torch.Tensor, grad_out: torch.Tensor, circular: bool = False,
+                             need_x: bool = True, need_k: bool = True):
+    """(gx | None, gk | None): the gradients of xcorr_depthwise (circular: of xcorr_depthwise_circular) with respect to x and kernel for
+    grad_out = d loss / d out, one launch of hdn_xcorr_depthwise_bwd_f32 (formulas: include/hdn_hip.h).  A gradient that is not needed is
+    neither computed nor allocated.  grad_out may be expanded or permuted; all three inputs are made contiguous."""
+    if not (need_x or need_k):
+        raise ValueError("xcorr_depthwise_backward: neither gradient is asked for")
+    shape = out_shape(x.shape, kernel.shape, circular)
+    if tuple(grad_out.shape) != tuple(shape):
+        raise ValueError(f"grad_out {tuple(grad_out.shape)} does not have the correlation's shape {tuple(shape)}")
+    dev = _lib.require_device(x, kernel, grad_out)
+    xc, kc, gc = x.detach().contiguous(), kernel.detach().contiguous(), grad_out.detach().contiguous()
+    gx = torch.empty_like(xc) if need_x else None
+    gk = torch.empty_like(kc) if need_k else None
+    B, C, Hx, Wx = xc.shape
+    Hk, Wk = kc.shape[2:]
+    with _lib.device_guard(dev):
+        rc = _lib.load().hdn_xcorr_depthwise_bwd_f32(_lib.ptr(xc), _lib.ptr(kc), _lib.ptr(gc), _lib.ptr(gx) if need_x else None,
+                                                     _lib.ptr(gk) if need_k else None, int(bool(circular)), B, C, Hx, Wx, Hk, Wk,
+                                                     _lib.stream_ptr(dev))
+    _lib.check(rc, "xcorr_depthwise_backward")
+    return gx, gk
+
+
+class _XcorrDepthwise(torch.autograd.Function):
+    """_xcorr with a backward: the forward is the same launch (same bits), the backward hdn_xcorr_depthwise_bwd_f32 for the inputs that need it."""
+
+    @staticmethod
+    def forward(ctx, x, kernel, circular):
+        ctx.circular = circular
+        ctx.save_for_backward(x, kernel)
+        return _xcorr(x, kernel, circular)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        x, kernel = ctx.saved_tensors
+        need_x, need_k = ctx.needs_input_grad[:2]
+        if not (need_x or need_k):
+            return None, None, None
+        gx, gk = xcorr_depthwise_backward(x, kernel, grad_out, ctx.circular, need_x, need_k)
+        return gx, gk, None
+
+
+def _xcorr_autograd(x: torch.Tensor, kernel: torch.Tensor, circular: bool) -> torch.Tensor:
+    if torch.is_grad_enabled() and (x.requires_grad or kernel.requires_grad):
+        return _XcorrDepthwise.apply(x, kernel, circular)
+    return _xcorr(x, kernel, circular)
+
+
 def xcorr_depthwise(x: torch.Tensor, kernel: torch.Tensor) -> torch.Tensor:
-    """depthwise cross correlation: out[b,c,i,j] = sum_uv x[b,c,i+u,j+v] * kernel[b,c,u,v]."""
-    return _xcorr(x, kernel, False)
+    """depthwise cross correlation: out[b,c,i,j] = sum_uv x[b,c,i+u,j+v] * kernel[b,c,u,v].  Differentiable (first order) when autograd is
+    recording and an input requires grad; otherwise the result carries no graph."""
+    return _xcorr_autograd(x, kernel, False)
 
 
 def xcorr_depthwise_circular(x: torch.Tensor, kernel: torch.Tensor) -> torch.Tensor:
-    """depthwise cross correlation for log-polar maps: rows wrap, columns replicate, pad = size//2."""
-    return _xcorr(x, kernel, True)
+    """depthwise cross correlation for log-polar maps: rows wrap, columns replicate, pad = size//2.  Differentiable like xcorr_depthwise."""
+    return _xcorr_autograd(x, kernel, True)
 
 
 def xcorr_depthwise_multi(xs: Sequence[torch.Tensor], kernels: Sequence[torch.Tensor], circular: bool = False,
                           outs: Sequence[torch.Tensor] = None) -> List[torch.Tensor]:
     """n same-shaped correlations in one launch (n <= 8).  `outs`: n preallocated contiguous float32 result tensors (e.g. the
-    slices of one stacked buffer) instead of fresh ones."""
+    slices of one stacked buffer) instead of fresh ones.  Inference only: the inputs are detached and the results carry no autograd
+    graph (the heads call it under no_grad only)."""
     if len(xs) != len(kernels) or not xs:
         raise ValueError("xs and kernels must be non-empty and of equal length")
     n = len(xs)
@@ -106,7 +162,8 @@ def xcorr_depthwise_multi(xs: Sequence[torch.Tensor], kernels: Sequence[torch.Te
 
 def xcorr_fast(x: torch.Tensor, kernel: torch.Tensor) -> torch.Tensor:
     """group conv2d to calculate cross correlation (hdn/core/xcorr.py:26-34): x [B,C,H,W], kernel [B,O*C,h,w] ->
-    [B,O,H-h+1,W-w+1], contracting the channels.  Only the unselected UPChannelBAN head uses it (O = 2 or 4)."""
+    [B,O,H-h+1,W-w+1], contracting the channels.  Only the unselected UPChannelBAN head uses it (O = 2 or 4).  Inference only: the
+    result carries no autograd graph."""
     if x.dim() != 4 or kernel.dim() != 4 or x.shape[0] != kernel.shape[0]:
         raise ValueError(f"expected x [B,C,H,W] and kernel [B,O*C,h,w], got {tuple(x.shape)} and {tuple(kernel.shape)}")
     B, C, Hx, Wx = x.shape
@@ -129,7 +186,8 @@ def xcorr_fast(x: torch.Tensor, kernel: torch.Tensor) -> torch.Tensor:
 
 def xcorr_slow(x: torch.Tensor, kernel: torch.Tensor) -> torch.Tensor:
     """for-loop cross correlation (hdn/core/xcorr.py:10-23): per batch element conv2d(x[i], kernel[i]) with ALL kernel
-    channels contracted, i.e. kernel must be [B,C,h,w] and the result is [B,1,Ho,Wo] (= xcorr_fast with O = 1)."""
+    channels contracted, i.e. kernel must be [B,C,h,w] and the result is [B,1,Ho,Wo] (= xcorr_fast with O = 1).  Inference only, like
+    xcorr_fast."""
     if x.dim() == 4 and kernel.dim() == 4 and kernel.shape[1] != x.shape[1]:
         raise ValueError(f"xcorr_slow contracts every kernel channel: kernel {tuple(kernel.shape)} vs x {tuple(x.shape)}")
     return xcorr_fast(x, kernel)

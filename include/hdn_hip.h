@@ -88,6 +88,35 @@ int hdn_xcorr_depthwise_multi_f32(const float* const* xs, const float* const* ks
                                   int circular, int B, int C, int Hx, int Wx, int Hk, int Wk, void* stream);
 
 /*
+ * Backward of the two depthwise correlations above (csrc/xcorr_bwd.hip): the gradients of a loss with respect to x and k,
+ * given gout = d loss / d out.  The functions it differentiates are xcorr_depthwise / xcorr_depthwise_circular,
+ * hdn/core/xcorr.py:37-61.  Per plane (b, c), with ph = Hx/2, pw = Wx/2 when `circular` (both 0 otherwise),
+ * HP = Hx + 2 ph, WP = Wx + 2 pw, Ho = HP - Hk + 1, Wo = WP - Wk + 1 and the padded plane
+ *   xp[P][Q] = x[(P - ph) mod Hx][clamp(Q - pw, 0, Wx - 1)]          (rows wrap first, then columns replicate)
+ *   out[i][j] = sum_{u,v} xp[i+u][j+v] k[u][v]                        (the forward)
+ * the gradients are
+ *   gk[u][v]  = sum_{i,j} gout[i][j] xp[i+u][j+v]
+ *   gxp[P][Q] = sum_{u,v} gout[P-u][Q-v] k[u][v]   over the (u, v) with 0 <= P-u < Ho and 0 <= Q-v < Wo
+ *   gx[r][s]  = sum of gxp[P][Q] over the padded positions that are copies of (r, s):
+ *                 rows    P in {r + ph - Hx, r + ph, r + ph + Hx} intersected with [0, HP);
+ *                 columns Q in [0, pw] if s == 0, joined with [pw + Wx - 1, WP) if s == Wx - 1, else Q = s + pw
+ *               (plain variant: gx = gxp).
+ *   x[B,C,Hx,Wx], k[B,C,Hk,Wk], gout[B,C,Ho,Wo] -> gx[B,C,Hx,Wx], gk[B,C,Hk,Wk]
+ * gx or gk may be NULL: that gradient is then neither computed nor written (both NULL: HDN_E_NULL).  fp32 fused multiply-adds in a
+ * fixed order and no atomics: two calls are bit-equal and a plane's result does not depend on the number of planes.  The pad is never
+ * materialised in HBM.  Checked before any launch, in this order: x, k, gout NULL or both outputs NULL -> HDN_E_NULL; the forward's
+ * shape rules -> HDN_E_SHAPE / HDN_E_LIMIT; an output equal to an input or to the other output -> HDN_E_ALIAS; the forward's
+ * plane-count limits -> HDN_E_LIMIT.
+ */
+int hdn_xcorr_depthwise_bwd_f32(const float* x, const float* k, const float* gout,
+                                float* gx, float* gk, int circular,
+                                int B, int C, int Hx, int Wx, int Hk, int Wk, void* stream);
+
+/* Pure host query: the launch form hdn_xcorr_depthwise_bwd_f32 takes for a plane shape.  0: the LDS form,
+ * (HP WP + Hk Wk + Ho Wo) 4 bytes <= 60 KiB; 1: the form that reads global memory; HDN_E_SHAPE / HDN_E_LIMIT as the entry point. */
+int hdn_xcorr_bwd_form(int circular, int Hx, int Wx, int Hk, int Wk);
+
+/*
  * Channel-contracting correlation of the alternative UPChannelBAN head (not on the production path):
  *   out[b,o,i,j] = sum_c sum_{u,v} x[b,c,i+u,j+v] * k[b,o*C+c,u,v]
  *   x[B,C,Hx,Wx], k[B,O*C,Hk,Wk] -> out[B,O,Hx-Hk+1,Wx-Wk+1],  1 <= O <= 8
