@@ -90,6 +90,17 @@ def prepare_model(model, fold_backbone=None):
     return miopen_find, folded
 
 
+def device_setup(model, cfg, graph, fold_backbone):
+    """What the Device* constructors do first -> (cfg, the reference's cfg node or None, graph, miopen_find, folded): cfg None = the reference's
+    configuration (the node is looked up only then), graph None = HDN_TRACKER_GRAPH, then prepare_model."""
+    ref_cfg = None
+    if cfg is None:
+        cfg, ref_cfg = reference_config()
+    if graph is None:
+        graph = env_flag("HDN_TRACKER_GRAPH")
+    return (cfg, ref_cfg, graph) + prepare_model(model, fold_backbone)
+
+
 def validate_frame_capacity(frame_capacity):
     """None, or (Hmax, Wmax) as a pair of ints >= 1."""
     if frame_capacity is None:

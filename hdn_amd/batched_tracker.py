@@ -3,6 +3,10 @@
     BatchedHomoTracker(hm_net, n, ...)       N x HomoTracker        <- hdnTrackerHomo, hdn/tracker/hdn_tracker_proj_e2e.py:60-285
     BatchedDeviceTracker(model, n)           N x DeviceTrackerHomo  (the reference's ModelBuilder interface; BN-folded backbone, MIOpen find mode)
 
+BatchedHomoTracker derives from HomoTracker and inherits its _body, _capture and _step: the frame body exists once.  Here are only the parts that
+see n frames - init / reinit (row b of every per-sequence buffer), _static_input / _frames (one [N,H,W,3] tensor through the pinned uploader, or
+the arena) and track_new's list of results - and the class attribute that asks for per-sequence scores.
+
 Why.  The reference's only inference-time parallelism is "several videos at once": tools/test.py pins one GPU (:49) and its authors
 split the video list by hand across processes (:91-103).  One sequence is a B = 1 latency problem — 2.9 ms per frame on an MI355X of
 which 2.1 ms are a ResNet-50 at batch 1 using < 5 % of the chip (profiles/round5_bench_line.json `sequence`) — and the H_total
@@ -35,14 +39,15 @@ import torch
 
 from . import _lib
 from . import frame as FR
-from ._loop import (FrameUploader, capture_graph, env_flag, find_mode, homography_result, prepare_model, reference_config, upload_arena,
-                    validate_frame_capacity)
-from .refine import homo_refine
+from ._loop import FrameUploader, device_setup, find_mode, homography_result, upload_arena, validate_frame_capacity
 from .similarity import DeviceSimilarity, TrackerConfig
-from .tracker import _const_row, _geometry, attach_hip_trunk
+from .tracker import HomoTracker, _const_row, _geometry, attach_hip_trunk
 
 
-class BatchedHomoTracker:
+class BatchedHomoTracker(HomoTracker):
+    _label = "batched per-frame"
+    _per_sample = True           # every sequence its own gate (at n = 1 too: hdn_l1_score2_batch_f32)
+
     def __init__(self, hm_net, n: int, iterations: int = 1, similarity=None, score_gate: float = 2.5, graph: bool = False, cfg: TrackerConfig = None,
                  frame_capacity=None):
         """hm_net: hdn_amd.HomoModelBuilder (or the reference's, after install()) in eval mode on the GPU; n: sequences per step.
@@ -52,12 +57,9 @@ class BatchedHomoTracker:
         if n < 1:
             raise ValueError("n must be >= 1")
         self.frame_capacity = validate_frame_capacity(frame_capacity)
+        super().__init__(hm_net, iterations=iterations, similarity=similarity, score_gate=score_gate, graph=graph, cfg=cfg)
         self._arena = None
-        self.net, self.n = hm_net, int(n)
-        self.cfg = cfg or (similarity.cfg if similarity is not None and hasattr(similarity, "cfg") else TrackerConfig())
-        self.use_graph, self._graph = bool(graph), None
-        self.iterations, self.similarity, self.score_gate = int(iterations), similarity, float(score_gate)
-        self.host_syncs = 0
+        self.n = int(n)
         self._upload = FrameUploader(self.n)      # (one pinned staging buffer, one asynchronous copy per step)
 
     # -------------------------------------------------------------------------------------------------- init
@@ -88,10 +90,11 @@ class BatchedHomoTracker:
         # get_template_info(get_subwindow_for_homo(...)[:, 0:3]): the normalised gray templates, constant for the sequences
         self._const_params = torch.from_numpy(np.concatenate([self.init_pos, self.init_s_z_sm[:, None], self.channel_average], axis=1)).to(self.dev)
         self.init_homo_tmp = FR.get_search_info(frames, None, None, None, model_sz=c.exemplar_size, params=self._const_params)
-        with torch.no_grad():
-            self.init_patch_1 = self.net.ShareFeature(self.init_homo_tmp).detach()
-        if self.similarity is not None:
-            self.similarity.init(frames, self.init_pos, self.init_s_z, self.init_s_z_sm, self.channel_average)
+        with find_mode(self.miopen_find):
+            with torch.no_grad():
+                self.init_patch_1 = self.net.ShareFeature(self.init_homo_tmp).detach()
+            if self.similarity is not None:
+                self.similarity.init(frames, self.init_pos, self.init_s_z, self.init_s_z_sm, self.channel_average)
         pts = [np.asarray(g, np.float64).reshape(-1, 2) for g in gt_points]
         if any(p.shape != pts[0].shape for p in pts):
             raise ValueError("every sequence must have the same number of initial points")
@@ -128,71 +131,37 @@ class BatchedHomoTracker:
         self._const_params[slot].copy_(torch.from_numpy(np.concatenate([pos, [s_z_sm], avg])))
         tmp = FR.get_search_info(frame, None, None, None, model_sz=c.exemplar_size, params=self._const_params[slot])
         self.init_homo_tmp[slot:slot + 1].copy_(tmp)
-        with torch.no_grad():
-            self.init_patch_1[slot:slot + 1].copy_(self.net.ShareFeature(tmp))
-        if self.similarity is not None:
-            self.similarity.reinit(slot, frame, pos, s_z, s_z_sm, avg)
+        with find_mode(self.miopen_find):
+            with torch.no_grad():
+                self.init_patch_1[slot:slot + 1].copy_(self.net.ShareFeature(tmp))
+            if self.similarity is not None:
+                self.similarity.reinit(slot, frame, pos, s_z, s_z_sm, avg)
         self.init_points[slot].copy_(torch.from_numpy(pts))
         self.H_total[slot].copy_(torch.eye(3, dtype=torch.float64))
         self._consts[slot].copy_(torch.from_numpy(_const_row(zp, c.exemplar_size, self.score_gate)))
 
     # -------------------------------------------------------------------------------------------------- one step = one frame of every sequence
-    def _body(self, frames):
-        """HomoTracker._body at batch n: no host reads, no data-dependent allocations -> capturable as one hipGraph.
-        -> (out float32 [n, 2 * points + 1] = corners (x, y) + best_score per sequence, homo_score [n])."""
-        lib, st, n = _lib.load(), _lib.stream_ptr(self.dev), self.n
-        with _lib.device_guard(self.dev):
-            _lib.check(lib.hdn_track_prepare_f64(_lib.ptr(self.H_total), _lib.ptr(self._Ht), _lib.ptr(self._Hinv), n, st), "track prepare")
-        frames = FR.warp_perspective(frames, self._Hinv)                            # :150-155, every sequence by its own inv(H_total)
-        sim_state = None
-        if self.similarity is not None:
-            sim = self.similarity(frames)                                           # :157-214
-            sim_state = self.similarity.state
-            params = sim["params_homo"]
-            rot_img = FR.warp_affine_cubic(frames, sim["rot_matrix"])               # :223
-        else:
-            params, rot_img = self._const_params, frames
-        search = FR.get_search_info(rot_img, None, None, None, model_sz=self.cfg.exemplar_size, params=params)     # :224-239
-        H_comp, homo_score, _ = homo_refine(self.net, self.init_homo_tmp, search, iterations=self.iterations, patch_1=self.init_patch_1,
-                                            per_sample=True)                        # :242-250
-        score = homo_score.detach().reshape(-1).to(torch.float32).contiguous()
-        with _lib.device_guard(self.dev):                                           # :251-272
-            _lib.check(lib.hdn_track_accumulate_f64(_lib.ptr(self._Ht), _lib.ptr(sim_state) if sim_state is not None else None, _lib.ptr(H_comp),
-                                                    _lib.ptr(score), _lib.ptr(self._consts), _lib.ptr(self.init_points), self.n_points,
-                                                    _lib.ptr(self.H_total), _lib.ptr(self._out), n, st), "track accumulate")
-        return self._out, score
-
-    def _capture(self, frame_shape):
-        """One hipGraph per step, as HomoTracker._capture (the warm-up also runs MIOpen's find at this batch size)."""
+    def _static_input(self, imgs):
         # (arena mode: the arena IS the static input - its slots hold the sequences' latest frames, their sizes are device data)
-        self._static_frames = self._arena if self._arena is not None else torch.empty(frame_shape, dtype=torch.uint8, device=self.dev)
-        got = capture_graph(lambda: self._body(self._static_frames), [self.H_total], "batched per-frame")
-        self.use_graph = got is not None
-        if got is not None:
-            self._graph, (self._g_out, self._g_score) = got
+        if self._arena is not None:
+            return self._arena
+        shape = tuple(imgs.shape) if isinstance(imgs, torch.Tensor) else (self.n,) + tuple(np.asarray(imgs[0]).shape)
+        return torch.empty(shape, dtype=torch.uint8, device=self.dev)
+
+    def _frames(self, imgs, into=None):
+        return self._arena if self._arena is not None else self._upload(imgs, self.dev, into=into)
+
+    _static_frames = property(lambda self: self._static_frame)      # (the static input of the captured graph, under this class's name for it)
 
     def track_new(self, fr_idx, imgs, sync: bool = True):
         """One frame of every sequence.  -> list of n result dictionaries with hdnTrackerHomo.track_new's keys (sync=True; one host read
         for all of them), or device views {'points' [n, P, 2], 'best_score' [n]} (sync=False)."""
         n, P = self.n, self.n_points
-        arena = self._arena is not None
-        if arena:
+        if self._arena is not None:
             imgs = [np.asarray(im) if not isinstance(im, torch.Tensor) else im for im in imgs] if not isinstance(imgs, torch.Tensor) else imgs
             upload_arena(self._arena, imgs, same_size=True)   # (before a first capture too: a refused step leaves nothing half done)
-        if self.use_graph and self._graph is None:
-            shape = None if arena else tuple(imgs.shape) if isinstance(imgs, torch.Tensor) else (n,) + tuple(np.asarray(imgs[0]).shape)
-            self._capture(shape)                              # (may switch use_graph off)
-        if self.use_graph:
-            if not arena:
-                self._upload(imgs, self.dev, into=self._static_frames)
-            self._graph.replay()
-            out, score = self._g_out, self._g_score
-            if not sync:
-                out, score = out.clone(), score.clone()
-        else:
-            out, score = self._body(self._arena if arena else self._upload(imgs, self.dev))
-            out = out.clone()
-        self.last_points, self.last_score = out[:, :2 * P].view(n, P, 2), score
+        out, self.last_score = self._step(imgs, sync)
+        self.last_points = out[:, :2 * P].view(n, P, 2)
         if not sync:
             return {"points": self.last_points, "polygon": self.last_points, "best_score": out[:, 2 * P]}
         host = out.cpu().numpy()
@@ -201,6 +170,9 @@ class BatchedHomoTracker:
 
     def track(self, imgs):
         return self.track_new(None, imgs)
+
+    def similarity_state(self):
+        raise NotImplementedError("similarity_state() decodes ONE sequence's record; the lock-step tracker's records are similarity.state [n, 48]")
 
 
 class BatchedDeviceTracker(BatchedHomoTracker):
@@ -211,27 +183,11 @@ class BatchedDeviceTracker(BatchedHomoTracker):
 
     def __init__(self, model, n: int, graph: bool = None, iterations: int = 1, cfg: TrackerConfig = None, fold_backbone: bool = None,
                  hip_trunk: bool = None, frame_capacity=None):
-        if cfg is None:
-            cfg, _ = reference_config()
-        if graph is None:
-            graph = env_flag("HDN_TRACKER_GRAPH")
         self.model = model
-        self.miopen_find, self.folded = prepare_model(model, fold_backbone)
+        cfg, _, graph, self.miopen_find, self.folded = device_setup(model, cfg, graph, fold_backbone)
         self.hip_trunk = attach_hip_trunk(model, hip_trunk)
         super().__init__(model.hm_net, n, iterations=iterations, similarity=DeviceSimilarity(model, cfg), graph=graph, cfg=cfg,
                          frame_capacity=frame_capacity)
-
-    def init(self, imgs, bboxes, polys, gt_points, first_points=None):
-        with find_mode(self.miopen_find):
-            return super().init(imgs, bboxes, polys, gt_points, first_points)
-
-    def track_new(self, fr_idx, imgs, sync: bool = True):
-        with find_mode(self.miopen_find):
-            return super().track_new(fr_idx, imgs, sync=sync)
-
-    def reinit(self, slot, img, bbox, poly, gt_points, first_point=None):
-        with find_mode(self.miopen_find):
-            return super().reinit(slot, img, bbox, poly, gt_points, first_point)
 
 
 @dataclasses.dataclass

@@ -33,8 +33,8 @@ import torch
 
 from . import _lib
 from . import frame as FR
-from ._loop import (FrameUploader, capture_graph, env_flag, find_mode, prepare_model, reference_config, similarity_result, track_state_row,
-                    upload_arena, validate_frame_capacity)
+from ._loop import (FrameUploader, capture_graph, device_setup, env_flag, find_mode, similarity_result, track_state_row, upload_arena,
+                    validate_frame_capacity)
 from .similarity import SEQ_DOUBLES, SimilarityDecoder, TrackerConfig
 
 TRACK_DOUBLES, OUT_DOUBLES = 48, 20     # HDN_SIMI_TRACK_DOUBLES / HDN_SIMI_OUT_DOUBLES
@@ -84,6 +84,7 @@ def sequence_records(poly, first_point, channel_average, cfg: TrackerConfig):
 
 
 class SimiTracker:
+    miopen_find = False        # (DeviceTrackerSimi: MIOpen find mode around the network work of init / reinit / track_new, capture included)
     _label = "per-frame"       # (how the warning of a failed capture names the body)
 
     def __init__(self, model, cfg: TrackerConfig = None, graph: bool = False, scale_score_thresh: float = 0.5, batch_template: bool = None):
@@ -184,7 +185,8 @@ class SimiTracker:
         self._out = torch.zeros((1, OUT_DOUBLES), dtype=torch.float64, device=self.dev)
         self._zf_static, self._graph = None, None
         z_crop = FR.get_subwindow(frame, None, c.exemplar_size, None, None, params=self.track[:, 40:46], islog=1)    # :140-143
-        self._template(z_crop, first=True)
+        with find_mode(self.miopen_find):
+            self._template(z_crop, first=True)
         return z_crop
 
     # -------------------------------------------------------------------------------------------------- one frame
@@ -242,20 +244,29 @@ class SimiTracker:
         if got is not None:
             self._graph, self._g_out = got
 
+    def _frames(self, img, into=None):
+        """This step's frame on the device, or copied into `into` (the static input of the captured graph)."""
+        if into is None:
+            return FR.upload(img)
+        return into.copy_(img if isinstance(img, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(img)), non_blocking=True)
+
+    def _step(self, imgs, frame_shape):
+        """Capture on first use; the frames into the static input and one replay, or the body eagerly.  -> out (a buffer the next step overwrites)."""
+        with find_mode(self.miopen_find):
+            if self.use_graph and self._graph is None:
+                self._capture(frame_shape)                        # (may switch use_graph off)
+            if self.use_graph:
+                self._frames(imgs, into=self._static_frame)
+                self._graph.replay()
+                return self._g_out
+            return self._body(self._frames(imgs))
+
     def track_new(self, fr_idx, img, gt_box=None, gt_poly=None, gt_points=None, sync: bool = True):
         """-> {'bbox', 'bbox_aligned', 'best_score', 'rot', 'polygon'} as hdnTracker.track_new (:295-301); sync=False: the float64 device record
         [20] (include/hdn_hip.h: hdn_simi_track_update_f64's `out`) without any host read."""
         if tuple(img.shape[:2]) != self.frame_hw:
             raise ValueError(f"frames of a sequence have one size: init saw {self.frame_hw}, this one is {tuple(img.shape[:2])}")
-        if self.use_graph and self._graph is None:
-            self._capture(tuple(img.shape))                   # (may switch use_graph off)
-        if self.use_graph:
-            t = img if isinstance(img, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(img))
-            self._static_frame.copy_(t, non_blocking=True)
-            self._graph.replay()
-            out = self._g_out
-        else:
-            out = self._body(FR.upload(img))
+        out = self._step(img, tuple(img.shape))
         if not sync:
             return {"record": out.clone().view(-1)}
         h = out.view(-1).cpu().numpy()
@@ -338,7 +349,8 @@ class BatchedSimiTracker(SimiTracker):
         self._out = torch.zeros((n, OUT_DOUBLES), dtype=torch.float64, device=self.dev)
         self._zf_static, self._graph = None, None
         z_crop = FR.get_subwindow(frames, None, c.exemplar_size, None, None, params=self.track[:, 40:46], islog=1)
-        self._template(z_crop, first=True)
+        with find_mode(self.miopen_find):
+            self._template(z_crop, first=True)
         return z_crop
 
     # -------------------------------------------------------------------------------------------------- arena mode: the parts of a step that see frame sizes
@@ -360,6 +372,9 @@ class BatchedSimiTracker(SimiTracker):
         # (arena mode: the arena IS the static input - its slots hold the sequences' latest frames, their sizes are device data; the first frames
         # are not copied over them)
         return self._arena if self._arena is not None else super()._static_input(frame_shape)
+
+    def _frames(self, imgs, into=None):
+        return self._arena if self._arena is not None else self._upload(imgs, self.dev, into=into)
 
     def reinit(self, slot: int, img, bbox, poly, gt_points, first_point=None):
         """What init does for ONE sequence, written in place into row `slot` of track / seq / state / the result buffer, of every level of the
@@ -390,19 +405,20 @@ class BatchedSimiTracker(SimiTracker):
         # the model's own template() reassigns zf / zf_lp and, behind install(), drops what the heads cached: a replayed graph reads both by address
         heads = [getattr(m, name) for name in ("head", "head_lp") if hasattr(m, name)]
         kept = [HD.template_cache_state(h) for h in heads]
-        try:
-            new = self._template_features(z_crop)
-            for dst, src in zip(self._zf_static, new):
-                for d, t in zip(*((dst, src) if isinstance(dst, list) else ([dst], [src]))):
-                    d[slot:slot + 1].copy_(t)
-        finally:
-            m.zf, m.zf_lp = self._zf_static
-            for h, k in zip(heads, kept):
-                HD.restore_template_cache_state(h, k)
-        if self._graph is not None and not self._kern_in_graph:
-            # (the capture found the heads' template-branch features cached, outside the graph: a replay reads those buffers, so bring the row up to date)
-            for h, z in zip(heads, self._zf_static):
-                HD.refresh_template_cache(h, z if isinstance(z, list) else [z], slot)
+        with find_mode(self.miopen_find):
+            try:
+                new = self._template_features(z_crop)
+                for dst, src in zip(self._zf_static, new):
+                    for d, t in zip(*((dst, src) if isinstance(dst, list) else ([dst], [src]))):
+                        d[slot:slot + 1].copy_(t)
+            finally:
+                m.zf, m.zf_lp = self._zf_static
+                for h, k in zip(heads, kept):
+                    HD.restore_template_cache_state(h, k)
+            if self._graph is not None and not self._kern_in_graph:
+                # (the capture found the heads' template-branch features cached, outside the graph: a replay reads those buffers, so bring the row up to date)
+                for h, z in zip(heads, self._zf_static):
+                    HD.refresh_template_cache(h, z if isinstance(z, list) else [z], slot)
         return z_crop
 
     def track_new(self, fr_idx, imgs, gt_box=None, gt_poly=None, gt_points=None, sync: bool = True):
@@ -419,15 +435,7 @@ class BatchedSimiTracker(SimiTracker):
             shape = tuple(imgs.shape) if isinstance(imgs, torch.Tensor) else (len(imgs),) + tuple(np.asarray(imgs[0]).shape)
             if shape[0] != self.n or tuple(shape[1:3]) != self.frame_hw:
                 raise ValueError(f"a step takes {self.n} frames of {self.frame_hw}, got {shape}")
-        if self.use_graph and self._graph is None:
-            self._capture(shape)                              # (may switch use_graph off)
-        if self.use_graph:
-            if shape is not None:
-                self._upload(imgs, self.dev, into=self._static_frame)
-            self._graph.replay()
-            out = self._g_out
-        else:
-            out = self._body(self._arena if shape is None else self._upload(imgs, self.dev))
+        out = self._step(imgs, shape)
         if not sync:
             return {"record": out.clone()}
         h = out.cpu().numpy()
@@ -445,19 +453,6 @@ class DeviceTrackerSimi(SimiTracker):
     backbone / necks and MIOpen find mode around this tracker's calls, exactly as hdn_amd.tracker.DeviceTrackerHomo."""
 
     def __init__(self, model, graph: bool = None, cfg: TrackerConfig = None, fold_backbone: bool = None, batch_template: bool = None):
-        thresh = 0.5
-        if cfg is None:
-            cfg, ref_cfg = reference_config()
-            thresh = float(getattr(getattr(ref_cfg, "TRACK", None), "SCALE_SCORE_THRESH", thresh))
-        if graph is None:
-            graph = env_flag("HDN_TRACKER_GRAPH")
-        self.miopen_find, self.folded = prepare_model(model, fold_backbone)
+        cfg, ref_cfg, graph, self.miopen_find, self.folded = device_setup(model, cfg, graph, fold_backbone)
+        thresh = float(getattr(getattr(ref_cfg, "TRACK", None), "SCALE_SCORE_THRESH", 0.5))      # (0.5 too when a cfg was handed in: no node is read then)
         super().__init__(model, cfg=cfg, graph=graph, scale_score_thresh=thresh, batch_template=batch_template)
-
-    def init(self, img, bbox, poly, *rest):
-        with find_mode(self.miopen_find):
-            return super().init(img, bbox, poly, *rest)
-
-    def track_new(self, fr_idx, img, gt_box=None, gt_poly=None, gt_points=None, sync: bool = True):
-        with find_mode(self.miopen_find):
-            return super().track_new(fr_idx, img, gt_box, gt_poly, gt_points, sync=sync)

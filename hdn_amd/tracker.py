@@ -21,6 +21,9 @@ head maps and six .cpu().numpy() syncs — is here ONE upload of the uint8 frame
 two one-lane kernels for the 3x3 float64 bookkeeping (hdn_track_prepare_f64 / hdn_track_accumulate_f64); the only host read is the 4 projected corners + best_score the caller asks for
 (`sync=True`).  Nothing in the body depends on host values, so it replays as one hipGraph (`graph=True`) with or without the
 similarity branch.  Sequences are independent: N GPUs run N sequences (replicas only, no collective).
+
+HomoTracker is written for n sequences per call with n = 1: its _body, _capture and _step take n from the object and never look at a buffer's
+shape, so hdn_amd.batched_tracker.BatchedHomoTracker inherits the three and overrides only init / reinit, the frame upload and track_new's results.
 """
 from __future__ import annotations
 
@@ -29,7 +32,7 @@ import torch
 
 from . import _lib
 from . import frame as FR
-from ._loop import capture_graph, env_flag, find_mode, homography_result, prepare_model, reference_config
+from ._loop import capture_graph, device_setup, env_flag, find_mode, homography_result
 from .refine import homo_refine
 from .similarity import DeviceSimilarity, TrackerConfig
 
@@ -57,13 +60,17 @@ def _const_row(zp, exemplar_size, score_gate):
 
 
 class HomoTracker:
+    miopen_find = False          # (the Device* classes: MIOpen find mode around the network work of init / reinit / track_new, capture included)
+    _label = "per-frame"         # (how the warning of a failed capture names the body)
+    _per_sample = False          # the score that gates: sample 0's (hdn_l1_score2_f32) / every sample's own (hdn_l1_score2_batch_f32)
+
     def __init__(self, hm_net, iterations: int = 1, similarity=None, score_gate: float = 2.5, graph: bool = False, cfg: TrackerConfig = None):
         """hm_net: hdn_amd.HomoModelBuilder (or the reference's, after install()) in eval mode on the GPU.
         iterations: trip count of the refinement loop (1 in the shipped tracker, :242; 2 in BASELINE config 5).
         similarity: None (identity) or a DeviceSimilarity: `.init(frame, init_pos, init_s_z, init_s_z_sm, avg)` once per
         sequence, `(stabilised_frame) -> views into its device state record` per frame (no host values).
         graph: replay the whole per-frame body as ONE hipGraph (several hundred launches at B = 1 are launch-latency bound)."""
-        self.net = hm_net
+        self.net, self.n = hm_net, 1       # n: sequences advanced per call
         self.cfg = cfg or (similarity.cfg if similarity is not None and hasattr(similarity, "cfg") else TrackerConfig())
         self.use_graph = bool(graph)
         self._graph = None
@@ -87,84 +94,102 @@ class HomoTracker:
         self.z_crop_points_sm = FR.crop_points(self.center_pos, self.init_s_z_sm, H, W)
         # get_template_info(get_subwindow_for_homo(...)[:, 0:3]) : the normalised gray template, constant for the sequence
         self.init_homo_tmp = FR.get_search_info(frame, self.center_pos, self.init_s_z_sm, self.channel_average, model_sz=c.exemplar_size)
-        with torch.no_grad():   # ShareFeature(template): constant for the sequence, so not part of the per-frame work
-            self.init_patch_1 = self.net.ShareFeature(self.init_homo_tmp).detach()
-        if self.similarity is not None:
-            self.similarity.init(frame, self.init_pos, self.init_s_z, self.init_s_z_sm, self.channel_average)   # model.template(z_crop), :99-107
+        with find_mode(self.miopen_find):
+            with torch.no_grad():   # ShareFeature(template): constant for the sequence, so not part of the per-frame work
+                self.init_patch_1 = self.net.ShareFeature(self.init_homo_tmp).detach()
+            if self.similarity is not None:
+                self.similarity.init(frame, self.init_pos, self.init_s_z, self.init_s_z_sm, self.channel_average)   # model.template(z_crop), :99-107
         self.init_points = torch.tensor(np.asarray(gt_points, np.float64).reshape(1, -1, 2), dtype=torch.float64, device=self.dev).contiguous()
+        self.n_points = self.init_points.shape[1]      # any number of initial points (cv2.perspectiveTransform takes any; POT gives 4)
         self.H_total = torch.eye(3, dtype=torch.float64, device=self.dev)
         self._Ht, self._Hinv = (torch.empty((3, 3), dtype=torch.float64, device=self.dev) for _ in range(2))
-        self._out = torch.empty((1, 2 * self.init_points.shape[1] + 1), dtype=torch.float32, device=self.dev)
+        self._out = torch.empty((1, 2 * self.n_points + 1), dtype=torch.float32, device=self.dev)
         self._const_params = FR._dev_f64([self.init_pos[0], self.init_pos[1], self.init_s_z_sm] + [float(a) for a in self.channel_average], self.dev)
         self._graph = None
         self._consts = torch.from_numpy(_const_row(self.z_crop_points_sm, c.exemplar_size, self.score_gate)).to(self.dev)
 
-    # -------------------------------------------------------------------------------------------------- one frame
-    def _body(self, frame):
-        """Everything of a frame that runs on the device, from the uploaded frame to the 4 projected corners; no host
-        reads, no allocations that depend on data: capturable in a hipGraph when the frame is a static buffer.
-        -> (H_total' [3,3] float64 (a buffer of this object), out float32 [9] = 4 corners (x, y) + best_score, homo_score)."""
-        lib, st = _lib.load(), _lib.stream_ptr(self.dev)
+    # -------------------------------------------------------------------------------------------------- one frame (of each of the n sequences)
+    def _body(self, frames):
+        """Everything of a frame that runs on the device, from the uploaded frame(s) - [H,W,3], [n,H,W,3] or an arena - to the projected corners; no
+        host reads, no allocations that depend on data: capturable in a hipGraph when the frames are a static buffer.  H_total ([3,3] / [n,3,3]
+        float64, a buffer of this object) advances in place.
+        -> (out float32 [n, 2 * points + 1] = corners (x, y) + best_score per sequence (a buffer of this object), the gating score)."""
+        lib, st, n = _lib.load(), _lib.stream_ptr(self.dev), self.n
         # :150-155  undo the accumulated motion (a singular H_total is reset to the identity, as the reference does).
-        # hdn_frame_warp_perspective_u8 inverts its matrix itself (cv2 semantics), so it is handed inv(H_total).
+        # hdn_frame_warp_perspective_u8 inverts its matrix itself (cv2 semantics), so it is handed inv(H_total), every sequence its own.
         with _lib.device_guard(self.dev):
-            _lib.check(lib.hdn_track_prepare_f64(_lib.ptr(self.H_total), _lib.ptr(self._Ht), _lib.ptr(self._Hinv), 1, st), "track prepare")
-        frame = FR.warp_perspective(frame, self._Hinv.view(-1))
+            _lib.check(lib.hdn_track_prepare_f64(_lib.ptr(self.H_total), _lib.ptr(self._Ht), _lib.ptr(self._Hinv), n, st), "track prepare")
+        frames = FR.warp_perspective(frames, self._Hinv.view(n, 9))
         sim_state = None
         if self.similarity is not None:
             # :157-214 on the STABILISED frame; :223 rotate back by -rot_delta about the new centre (bicubic; rot 0 = identity)
-            sim = self.similarity(frame)
+            sim = self.similarity(frames)
             sim_state, params = self.similarity.state, sim["params_homo"]
-            rot_img = FR.warp_affine_cubic(frame, sim["rot_matrix"])
+            rot_img = FR.warp_affine_cubic(frames, sim["rot_matrix"])
         else:
-            params, rot_img = self._const_params, frame
+            params, rot_img = self._const_params, frames
         # :224-239  cut the homography crop, normalise
         search = FR.get_search_info(rot_img, None, None, None, model_sz=self.cfg.exemplar_size, params=params)
         # :242-250  refinement loop around track_proj
-        H_comp, homo_score, _ = homo_refine(self.net, self.init_homo_tmp, search, iterations=self.iterations, patch_1=self.init_patch_1)
+        H_comp, homo_score, _ = homo_refine(self.net, self.init_homo_tmp, search, iterations=self.iterations, patch_1=self.init_patch_1,
+                                            per_sample=self._per_sample)
         # :251-272  un-scale, un-shift, gate, accumulate, project the initial corners
         score = homo_score.detach().reshape(-1).to(torch.float32).contiguous()
         with _lib.device_guard(self.dev):
             _lib.check(lib.hdn_track_accumulate_f64(_lib.ptr(self._Ht), _lib.ptr(sim_state) if sim_state is not None else None, _lib.ptr(H_comp),
-                                                    _lib.ptr(score), _lib.ptr(self._consts), _lib.ptr(self.init_points),
-                                                    self.init_points.shape[1], _lib.ptr(self.H_total), _lib.ptr(self._out), 1, st),
+                                                    _lib.ptr(score), _lib.ptr(self._consts), _lib.ptr(self.init_points), self.n_points,
+                                                    _lib.ptr(self.H_total), _lib.ptr(self._out), n, st),
                        "track accumulate")     # (in place: the kernel reads Ht, the copy hdn_track_prepare_f64 made)
-        return self.H_total, self._out.view(-1), homo_score
+        return self._out, (score if self._per_sample else homo_score)
 
-    def _capture(self, frame_shape):
-        """hipGraph of the whole per-frame body.  The frame lands in a static device buffer; H_total is carried in a static tensor updated
+    def _static_input(self, img):
+        return torch.empty(tuple(np.shape(img)), dtype=torch.uint8, device=self.dev)
+
+    def _frames(self, img, into=None):
+        """This step's frame on the device, or copied into `into` (the static input of the captured graph)."""
+        if into is None:
+            return FR.upload(img)
+        t = img if isinstance(img, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(img))
+        if tuple(t.shape) != tuple(into.shape) or t.dtype != torch.uint8:
+            raise ValueError(f"graph mode was captured for uint8 frames of shape {tuple(into.shape)}, got {t.dtype} {tuple(t.shape)}")
+        return into.copy_(t, non_blocking=True)
+
+    def _capture(self, imgs):
+        """hipGraph of the whole per-frame body.  The frames land in a static device buffer; H_total is carried in a static tensor updated
         in place by the graph itself (the recurrence lives inside the graph; the warm-up's advance of it is put back); the similarity state
         record is a static tensor of the DeviceSimilarity.  A body that cannot be captured: use_graph goes False, eager from here on."""
-        self._static_frame = torch.empty(frame_shape, dtype=torch.uint8, device=self.dev)
-        got = capture_graph(lambda: self._body(self._static_frame), [self.H_total], "per-frame")
+        self._static_frame = self._static_input(imgs)
+        got = capture_graph(lambda: self._body(self._static_frame), [self.H_total], self._label)
         self.use_graph = got is not None
         if got is not None:
-            self._graph, (_, self._g_out, self._g_score) = got
+            self._graph, (self._g_out, self._g_score) = got
+
+    def _step(self, imgs, sync):
+        """Capture on first use; the frames into the static input and one replay, or the body eagerly.  -> (out, score) that a later step leaves alone
+        (sync: the caller reads `out` to the host before that, so the graph's own buffer will do)."""
+        with find_mode(self.miopen_find):
+            if self.use_graph and self._graph is None:
+                self._capture(imgs)                    # (may switch use_graph off)
+            if self.use_graph:
+                self._frames(imgs, into=self._static_frame)
+                self._graph.replay()
+                out, score = self._g_out, self._g_score
+                if not sync:  # the graph's static outputs are overwritten by the next replay: hand out copies
+                    out, score = out.clone(), score.clone()
+            else:
+                out, score = self._body(self._frames(imgs))
+                out = out.clone()
+        return out, score
 
     def track_new(self, fr_idx, img, gt_box=None, gt_poly=None, gt_points=None, sync: bool = True):
-        if self.use_graph:
-            t = img if isinstance(img, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(img))
-            if self._graph is None:
-                self._capture(tuple(t.shape))          # (may switch use_graph off)
-        if self.use_graph:
-            if tuple(t.shape) != tuple(self._static_frame.shape) or t.dtype != torch.uint8:
-                raise ValueError(f"graph mode was captured for uint8 frames of shape {tuple(self._static_frame.shape)}, got {t.dtype} {tuple(t.shape)}")
-            self._static_frame.copy_(t, non_blocking=True)
-            self._graph.replay()
-            out, homo_score = self._g_out, self._g_score
-            if not sync:  # the graph's static outputs are overwritten by the next replay: hand out copies
-                out, homo_score = out.clone(), homo_score.clone()
-        else:
-            H, out, homo_score = self._body(FR.upload(img))
-            out = out.clone()
-        n = self.init_points.shape[1]          # any number of initial points (cv2.perspectiveTransform takes any; POT gives 4)
-        pts = out[:2 * n].view(n, 2)
-        self.last_points, self.last_score = pts, homo_score
+        out, self.last_score = self._step(img, sync)
+        P = self.n_points
+        pts = self.last_points = out[0, :2 * P].view(P, 2)
         if not sync:
-            return {"points": pts, "polygon": pts, "best_score": out[2 * n]}
+            return {"points": pts, "polygon": pts, "best_score": out[0, 2 * P]}
         host = out.cpu().numpy()
         self.host_syncs += 1
-        return homography_result(host, n)
+        return homography_result(host[0], P)
 
     def track(self, img):
         """BaseTracker.track (hdn/tracker/base_tracker.py:28-37, abstract there): the next frame, nothing else known."""
@@ -211,12 +236,8 @@ class DeviceTrackerHomo(HomoTracker):
     BatchNorm-folded HIP form attached (hdn_amd.homo_model.optimize_trunk(model.hm_net, channels_last=True); enable=False there undoes it)."""
 
     def __init__(self, model, graph: bool = None, iterations: int = 1, cfg: TrackerConfig = None, fold_backbone: bool = None, hip_trunk: bool = None):
-        if cfg is None:
-            cfg, _ = reference_config()
-        if graph is None:
-            graph = env_flag("HDN_TRACKER_GRAPH")
         self.model = model
-        self.miopen_find, self.folded = prepare_model(model, fold_backbone)
+        cfg, _, graph, self.miopen_find, self.folded = device_setup(model, cfg, graph, fold_backbone)
         self.hip_trunk = attach_hip_trunk(model, hip_trunk)
         super().__init__(model.hm_net, iterations=iterations, similarity=DeviceSimilarity(model, cfg), graph=graph, cfg=cfg)
         if (self.folded or self.miopen_find or self.hip_trunk) and not DeviceTrackerHomo._announced:
@@ -232,11 +253,3 @@ class DeviceTrackerHomo(HomoTracker):
                    "HDN_MIOPEN_FIND=0: torch's setting as it is)" if self.miopen_find else ""), file=sys.stderr)
 
     _announced = False
-
-    def init(self, img, bbox, poly, gt_points, first_point=None):
-        with find_mode(self.miopen_find):
-            return super().init(img, bbox, poly, gt_points, first_point)
-
-    def track_new(self, fr_idx, img, gt_box=None, gt_poly=None, gt_points=None, sync: bool = True):
-        with find_mode(self.miopen_find):
-            return super().track_new(fr_idx, img, gt_box, gt_poly, gt_points, sync=sync)

@@ -216,6 +216,37 @@ def test_batched_tracker_per_sequence_score_gate(dev):
         np.testing.assert_allclose(one.track_new(i, [fr[i]])[0]["points"], solo.track_new(i, fr[i])["points"], atol=1e-5)
 
 
+@pytest.mark.parametrize("graph", [False, True], ids=["eager", "graph"])
+def test_batched_tracker_at_one_sequence_is_the_single_tracker_bit_for_bit(dev, graph):
+    """BatchedHomoTracker(net, 1) inherits HomoTracker's frame body; the two differ in the score kernel only (per-sample hdn_l1_score2_batch_f32
+    against sample 0's hdn_l1_score2_f32), and the score only gates.  So H_total and the projected corners of four frames are EQUAL, eagerly and
+    as one hipGraph per frame - once the library convolutions of the stand-in estimator's trunk are asked for their deterministic solvers: the
+    default ones at B = 1 accumulate atomically and differ between two calls of the SAME class by an ulp (see the gate test above, and
+    test_gpu_trunk50.py), which is the only thing that separates the two classes without the flag (up to 2.8e-5 in H_total over these frames; two runs of one class differ alike)."""
+    from hdn_amd.batched_tracker import BatchedHomoTracker
+    from hdn_amd.tracker import HomoTracker
+    from test_gpu_parity import _seeded_net
+    fr, _, init = _sequences(1, 5)[0]
+    net = _seeded_net().to(dev)
+    prev = torch.backends.cudnn.deterministic
+    torch.backends.cudnn.deterministic = True
+    try:
+        one, solo = BatchedHomoTracker(net, 1, graph=graph), HomoTracker(net, graph=graph)
+        one.init([fr[0]], [init["bbox"]], [init["poly"]], [init["gt_points"]], [init["first_point"]])
+        solo.init(fr[0], init["bbox"], init["poly"], init["gt_points"], init["first_point"])
+        assert one.H_total.shape == (1, 3, 3) and solo.H_total.shape == (3, 3) and one._consts.shape == (1, 40) and solo._consts.shape == (40,)
+        for i in range(1, 5):
+            a, b = one.track_new(i, [fr[i]], sync=False), solo.track_new(i, fr[i], sync=False)
+            assert a["points"].shape == (1, 4, 2) and b["points"].shape == (4, 2)
+            assert torch.equal(one.H_total[0], solo.H_total), (i, float((one.H_total[0] - solo.H_total).abs().max()))
+            assert torch.equal(a["points"][0], b["points"]), i
+            assert abs(float(one.last_score[0]) - float(solo.last_score)) <= 1e-5 * abs(float(solo.last_score))     # (two kernels, one sum)
+        assert (one._graph is not None) == graph and (solo._graph is not None) == graph
+        assert not torch.equal(solo.H_total, torch.eye(3, dtype=torch.float64, device=dev))          # the sequence did move
+    finally:
+        torch.backends.cudnn.deterministic = prev
+
+
 def test_batched_device_tracker_production_shape(dev):
     """BatchedDeviceTracker(model, n) — n x the object install(tracker=True) registers — around the production-shaped stand-in
     (ResNet-50 backbone on PyTorch-ROCm, 256-channel heads: prod29 / circ13 correlations at batch n), one hipGraph per step,

@@ -1,6 +1,7 @@
 """CPU tests of hdn_amd._loop, the host-side code the four tracker modules share: the environment switches, MIOpen find mode, the look-up of the
 reference's configuration, frame_capacity, what the frame uploaders refuse before the first CUDA call, the result builders, and the geometry /
-const-row functions of hdn_amd.tracker against the arithmetic HomoTracker.init used to spell out.  No kernel is launched here."""
+const-row functions of hdn_amd.tracker against the arithmetic HomoTracker.init used to spell out, and the class structure of the trackers (one
+frame body per kind, find mode entered by the base classes).  No kernel is launched here."""
 import sys
 import types
 
@@ -159,3 +160,80 @@ def test_geometry_and_const_row_are_what_homotracker_init_spelled_out():
     got = _const_row(zp, E, gate)
     assert got.dtype == np.float64 and got.shape == want.shape and (got == want).all()
     assert np.linalg.inv(S).dtype == np.float32                                   # (numpy's dtype rule: the inverses are float32 too)
+
+
+def test_lockstep_trackers_inherit_the_frame_body_and_the_device_classes_are_constructors():
+    """The lock-step classes run the single trackers' own frame body (function identity, not a copy kept in step by hand); MIOpen find mode is
+    entered by the base classes, so the Device* classes define no init / track_new / reinit of their own; and the public constructors take what
+    they took before the classes were put under one base."""
+    import inspect
+    from hdn_amd.batched_tracker import BatchedDeviceTracker, BatchedHomoTracker
+    from hdn_amd.simi_tracker import BatchedSimiTracker, DeviceTrackerSimi, SimiTracker
+    from hdn_amd.tracker import DeviceTrackerHomo, HomoTracker
+    assert BatchedHomoTracker._body is HomoTracker._body and BatchedHomoTracker._capture is HomoTracker._capture
+    assert BatchedSimiTracker._body is SimiTracker._body
+    assert HomoTracker._per_sample is False and BatchedHomoTracker._per_sample is True        # sample 0's score / every sequence's own, at n = 1 too
+    with pytest.raises(NotImplementedError, match="ONE sequence"):                             # (inherited by name only: it decodes one record)
+        BatchedHomoTracker.similarity_state(None)
+    for cls in (DeviceTrackerHomo, BatchedDeviceTracker, DeviceTrackerSimi):
+        assert not {"init", "track_new", "reinit"} & set(vars(cls)), cls
+    assert HomoTracker.miopen_find is False and SimiTracker.miopen_find is False
+    want = {
+        HomoTracker: "(self, hm_net, iterations=1, similarity=None, score_gate=2.5, graph=False, cfg=None)",
+        BatchedHomoTracker: "(self, hm_net, n, iterations=1, similarity=None, score_gate=2.5, graph=False, cfg=None, frame_capacity=None)",
+        DeviceTrackerHomo: "(self, model, graph=None, iterations=1, cfg=None, fold_backbone=None, hip_trunk=None)",
+        BatchedDeviceTracker: "(self, model, n, graph=None, iterations=1, cfg=None, fold_backbone=None, hip_trunk=None, frame_capacity=None)",
+        SimiTracker: "(self, model, cfg=None, graph=False, scale_score_thresh=0.5, batch_template=None)",
+        BatchedSimiTracker: "(self, model, n, cfg=None, graph=False, scale_score_thresh=0.5, batch_template=None, frame_capacity=None)",
+        DeviceTrackerSimi: "(self, model, graph=None, cfg=None, fold_backbone=None, batch_template=None)",
+    }
+    for cls, sig in want.items():
+        params = inspect.signature(cls.__init__).parameters.values()
+        assert "(" + ", ".join(p.name if p.default is p.empty else f"{p.name}={p.default!r}" for p in params) + ")" == sig, cls
+
+
+def test_device_setup_fills_in_what_was_not_given(monkeypatch):
+    """The Device* constructors' preamble: a cfg handed in is kept and the reference's node is not looked up; None reads it; graph None reads
+    HDN_TRACKER_GRAPH; the model is put in eval mode."""
+    from hdn_amd.similarity import TrackerConfig
+    monkeypatch.setattr(LP, "reference_config", lambda: (TrackerConfig(instance_size=303), "node"))
+    monkeypatch.setenv("HDN_FOLD_BACKBONE", "0")
+    model = torch.nn.Conv2d(1, 1, 1).train()
+    mine = TrackerConfig(instance_size=271)
+    monkeypatch.setenv("HDN_TRACKER_GRAPH", "0")
+    assert LP.device_setup(model, mine, None, None) == (mine, None, False, False, []) and not model.training
+    assert LP.device_setup(model, mine, True, False)[:3] == (mine, None, True)
+    monkeypatch.delenv("HDN_TRACKER_GRAPH")
+    cfg, ref, graph, find, folded = LP.device_setup(model, None, None, False)
+    assert cfg.instance_size == 303 and ref == "node" and graph is True and find is False and folded == []
+
+
+def test_step_enters_find_mode_around_the_capture_and_the_body(monkeypatch):
+    """The shared step of either tracker kind raises cudnn.benchmark (when miopen_find is set, as the Device* constructors do) around the graph
+    capture AND the frame body, puts it back, and goes on eagerly after a refused capture; with the class default nothing is touched."""
+    from hdn_amd.simi_tracker import SimiTracker
+    from hdn_amd.tracker import HomoTracker
+    cudnn, seen = torch.backends.cudnn, []
+    monkeypatch.setattr(cudnn, "benchmark", False)
+    for base, rest, out in ((HomoTracker, (True,), (torch.zeros(1, 9), torch.zeros(()))), (SimiTracker, ((4, 6, 3),), torch.zeros(1, 20))):
+        class Fake(base):
+            def __init__(self):
+                self.use_graph, self._graph = True, None
+
+            def _capture(self, *_):
+                seen.append(("capture", cudnn.benchmark))
+                self.use_graph = False                       # (what a refused stream capture leaves behind)
+
+            def _frames(self, imgs, into=None):
+                return imgs
+
+            def _body(self, frames):
+                seen.append(("body", frames, cudnn.benchmark))
+                return out
+        for find in (True, False):
+            t = Fake()
+            if find:
+                t.miopen_find = True
+            t._step("frame", *rest)
+            assert seen == [("capture", find), ("body", "frame", find)] and cudnn.benchmark is False and t.use_graph is False, (base, find)
+            seen.clear()
