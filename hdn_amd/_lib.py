@@ -131,6 +131,11 @@ SIGNATURES = {
     "hdn_gather_peer_access": (_i, [_i, ctypes.c_char_p]),
     "hdn_device_pci_bus_id": (_i, [_i, ctypes.c_char_p, _i]),
     "hdn_logpolar_sample_f32": (_i, [_c_float_p] * 7 + [_i] * 5 + [ctypes.c_void_p]),
+    "hdn_logpolar_sample_bwd_workspace_bytes": (ctypes.c_longlong, [_i, _i]),
+    "hdn_logpolar_sample_bwd_f32": (_i, [_c_float_p] * 9 + [ctypes.c_longlong] + [_i] * 5 + [ctypes.c_void_p]),
+    "hdn_dlt_solve_bwd_f32": (_i, [_c_float_p] * 5 + [_i, ctypes.c_void_p]),
+    "hdn_warp_bwd_workspace_bytes": (ctypes.c_longlong, [_i, _i, _i]),
+    "hdn_warp_bwd_f32": (_i, [_c_float_p] * 6 + [ctypes.c_longlong] + [_i] * 4 + [ctypes.c_void_p]),
 }
 
 ERRORS = {

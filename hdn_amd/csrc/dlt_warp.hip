@@ -14,19 +14,13 @@
 // (both taps clamped to one index -> exact cancellation, |t| < 1e-7 nudge, float->int
 // conversion of out-of-range coordinates) come out as the reference's PyTorch-CPU path gives
 // them.  See DESIGN.md "warp semantics".
-#include "hdn_common.h"
+#include "geometry.h"   // dlt_point, grid_coord, f2i_x86, clampi, WARP_PX_PER_*: shared with the backward (geometry_bwd.hip)
 
 // The reference's CPU kernels round after every multiply and add here: rn_mul/rn_add/rn_sub/rn_div (hdn_common.h) are
 // compiled with contraction off; fusion is spelled out with __builtin_fmaf where the reference fuses.
 #pragma clang fp contract(off)
 
 namespace hdn {
-
-constexpr int WARP_PX_PER_THREAD = 4;
-constexpr int WARP_PX_PER_BLOCK = HDN_BLOCK * WARP_PX_PER_THREAD;
-
-// reference point order inside the solve: utils.py:18-26 gathers columns [0,1,2,3,6,7,4,5]
-__device__ __forceinline__ int dlt_point(int p) { return p == 2 ? 3 : (p == 3 ? 2 : p); }
 
 // All 64 lanes call this; each aligned group of 8 lanes solves the same system redundantly.
 // Returns h[r] for r = lane & 7 (the r-th of the 8 unknowns).
@@ -149,20 +143,6 @@ __device__ __forceinline__ void normalise_H(const float* Hm, float ax, float ay,
   mat3_mul(Minv, Hm, P);
   mat3_mul(P, M, theta);
 }
-
-// torch.linspace(-1, 1, n)[i] on the CPU: start + step*i below the midpoint, end - step*(n-1-i)
-// above, each with a single rounding (verified bit-for-bit in tests/test_host_logic.py).
-__device__ __forceinline__ float grid_coord(int i, int n) {
-  const float step = rn_div(2.0f, (float)(n - 1));
-  return i < n / 2 ? __builtin_fmaf(step, (float)i, -1.0f) : __builtin_fmaf(-step, (float)(n - 1 - i), 1.0f);
-}
-
-// float -> int32 as the reference's x86 path converts it: out-of-range and NaN give INT_MIN.
-__device__ __forceinline__ int f2i_x86(float f) {
-  return (f >= -2147483648.0f && f < 2147483648.0f) ? (int)f : (int)0x80000000;
-}
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // One output pixel (row i, column j) of image `img` (C planes of H x W, plane stride H*W) written to
 // out[(i*W + j)*C + c].

@@ -21,12 +21,11 @@ attribute the reference resolves at call time:
     ModelBuilder.template                                unchanged, then drops the heads' cached template-branch features
     hdn.tracker.tracker_builder.TRACKS['hdnTrackerHomoProje2e']   (install(tracker=True)) the device-resident tracker loop
 
-Training under install(): of the drop-ins only xcorr_depthwise and xcorr_depthwise_circular are differentiable (hdn_amd/xcorr.py).  The rebound head
-forwards defer to the classes' own forward in .train() mode, so code that trains the correlation heads alone (MultiBAN / MultiCircBAN and what feeds
-them) receives every gradient.  The reference's own training forward (tools/train.py -> ModelBuilder.forward, model_builder...:333-390) does NOT run
-under install(): it passes a polar that carries the graph of the first head through STN_Polar, and the STN_Polar drop-in has no backward - it raises
-there rather than detach.  DLT_solve / transform / transformer, the fused track_proj and xcorr_fast / xcorr_slow are inference-only as well (they
-detach).  uninstall() before tools/train.py and before training the homography estimator.
+Training under install(train=True): every statement of the reference's training forwards that resolves to a drop-in is differentiable on the device -
+xcorr_depthwise{,_circular} (hdn_amd/xcorr.py), DLT_solve / transform / transformer (hdn_amd/homography.py) and, with train=True, STN_Polar
+(STN_PolarTrain, hdn_amd/logpolar.py; without train=True the STN_Polar drop-in raises on a grad-carrying input rather than detach).  The rebound head
+forwards defer to the classes' own forward in .train() mode.  What still needs uninstall(): anything that calls the fused inference paths with
+autograd expected - the fused track_proj, dlt_warp, the fused heads in eval mode, xcorr_fast / xcorr_slow, xcorr_depthwise_multi (they detach).
 """
 from __future__ import annotations
 
@@ -134,11 +133,9 @@ def _rebind(owner, attr, value, item=False):
 
 
 def uninstall() -> int:
-    """Undo every rebinding install() made (most recent first): the reference runs on its own PyTorch ops again, e.g.
-    for the reference's tools/train.py or for training the homography estimator (of the drop-ins only the two depthwise correlations are
-    differentiable; STN_Polar raises on a grad-carrying input, DLT_solve / transform / transformer, the fused track_proj and xcorr_fast carry no
-    autograd graph).  Folded trunks that install(trunk=True) attached are
-    detached (optimize_trunk(net, enable=False)).  Returns the number of rebindings undone."""
+    """Undo every rebinding install() made (most recent first): the reference runs on its own PyTorch ops again, e.g. for code that expects autograd
+    through the fused inference paths (the fused track_proj, dlt_warp, the eval-mode heads and xcorr_fast carry no autograd graph).  Folded trunks
+    that install(trunk=True) attached are detached (optimize_trunk(net, enable=False)).  Returns the number of rebindings undone."""
     n = 0
     while _trunk_nets:
         net = _trunk_nets.pop()()
@@ -162,14 +159,15 @@ def uninstall() -> int:
     return n
 
 
-def install(strict: bool = False, modules: dict = None, tracker: bool = False, trunk: bool = False) -> list:
+def install(strict: bool = False, modules: dict = None, tracker: bool = False, trunk: bool = False, train: bool = False) -> list:
     """Apply the rebindings.  tracker=True also registers hdn_amd.tracker.DeviceTrackerHomo under
     TRACKS['hdnTrackerHomoProje2e'] (hdn/tracker/tracker_builder.py:12-19), so build_tracker(model) of tools/test.py:72 /
     tools/demo.py returns the device-resident loop (frames uploaded once, crops / warps / decodes as kernels, one host read per
     frame) instead of the host-side one.  `modules` (name -> module) lets tests supply stand-in modules; by default the
     real reference modules are imported.  trunk=True: the rebound ModelBuilder.track_proj attaches the BatchNorm-folded HIP trunk
     (hdn_amd.homo_model.optimize_trunk(self.hm_net, channels_last=True)) at its first eval-mode call with CUDA float32 weights, for users of the
-    rebindings without the device tracker; off by default.  Returns the list of (module, attribute) pairs that were rebound;
+    rebindings without the device tracker; off by default.  train=True: the two STN_Polar sites are bound to hdn_amd.logpolar.STN_PolarTrain (the same
+    module with differentiable=True), so that the reference's training forward runs on the drop-ins; everything else is unchanged.  Returns the list of (module, attribute) pairs that were rebound;
     with strict=True a site that cannot be imported raises instead of being skipped.  uninstall() reverses it."""
     done = []
 
@@ -189,7 +187,7 @@ def install(strict: bool = False, modules: dict = None, tracker: bool = False, t
             continue
         if not hasattr(m, attr) and strict:
             raise AttributeError(f"{mod_name}.{attr} not found: reference layout changed?")
-        _rebind(m, attr, fn)
+        _rebind(m, attr, logpolar.STN_PolarTrain if train and fn is logpolar.STN_Polar else fn)
         done.append((mod_name, attr))
 
     pre = get(_DLT + ".preprocess")

@@ -229,6 +229,69 @@ int hdn_logpolar_sample_f32(const float* img, const float* polar, const float* r
                             int S, void* stream);
 
 /*
+ * Backward of the three geometry operators (csrc/geometry_bwd.hip; training only).  Common rules:
+ *   - an output pointer that is NULL means that gradient is neither computed nor written; asking for no gradient at all is HDN_E_SHAPE;
+ *   - checked before any launch, in this order: an input NULL -> HDN_E_NULL; the forward's shape rules (and "no gradient") -> HDN_E_SHAPE; the
+ *     forward's limits -> HDN_E_LIMIT; the workspace, where one is needed (NULL -> HDN_E_NULL, not 16-byte aligned or too small -> HDN_E_LIMIT,
+ *     overlapping img or grad_out -> HDN_E_ALIAS); an output equal to an input, the workspace or the other output -> HDN_E_ALIAS;
+ *   - every kernel recomputes the forward's sample point with the forward's own statements, so it differentiates through the taps the forward read;
+ *   - grad_polar, grad_theta, grad_src and grad_off are DETERMINISTIC: no atomics, a fixed-order reduction in the block (wave shuffles, then LDS),
+ *     one partial per (sample, block) in `workspace`, and a second launch of the same call that adds the partials in a fixed order.  Two calls are
+ *     bit-equal, and sample b of a batch has the bits of that sample run alone;
+ *   - grad_img is a scatter by plain fp32 atomicAdd into the buffer the call zero-fills on `stream`: it is the one output that is NOT
+ *     bit-reproducible between calls on arbitrary data (the order in which colliding taps are added is not fixed).  Neither the reference's
+ *     `search` (model_builder_e2e_unconstrained_v2.py:379) nor its `org_imgs` (homo_model_builder.py:168) requires grad in training.
+ *
+ * hdn_logpolar_sample_bwd_f32: the sampler above.  With the forward's clamped pixel position (px, py), w = px - floor(px), e = 1 - w,
+ * n = py - floor(py), s = 1 - n, the four taps I_nw, I_ne, I_sw, I_se masked as in the forward (an east / south tap beyond the last index is 0):
+ *   d out / d px = s (I_ne - I_nw) + n (I_se - I_sw)
+ *   d out / d py = e (I_sw - I_nw) + w (I_se - I_ne)
+ *   d px / d polar_x = (W/2) / (H//2),  d py / d polar_y = (H/2) / (W//2)      (the forward's (sic) pairing of x with H//2 and y with W//2)
+ * both times PyTorch's border rule (clip_coordinates_set_grad, what F.grid_sample(padding_mode='border') differentiates with): a coordinate the
+ * clamp moved has derivative 0, i.e. p <= 0 or p >= size - 1 before clamping.
+ *   grad_polar[b] = sum over c, a, r of grad_out[b,c,a,r] (d out / d px d px / d polar_x, d out / d py d py / d polar_y)
+ *   grad_img[b,c] += grad_out[b,c,a,r] {s e, s w, n e, n w} at the four taps; masked taps receive nothing.
+ * img[B,C,H,W], polar[B,2], the three tables [S], grad_out[B,C,S,S] -> grad_polar[B,2] and/or grad_img[B,C,H,W].
+ * workspace: hdn_logpolar_sample_bwd_workspace_bytes(B, S) bytes, 16-byte aligned, needed for grad_polar only (else it may be NULL).
+ * Differentiates STN_Polar.forward, hdn/models/logpolar.py:100-124 (training forward: model_builder_e2e_unconstrained_v2.py:377-379).
+ */
+long long hdn_logpolar_sample_bwd_workspace_bytes(int B, int S);
+int hdn_logpolar_sample_bwd_f32(const float* img, const float* polar, const float* rho, const float* cos_theta, const float* sin_theta,
+                                const float* grad_out, float* grad_polar_or_null, float* grad_img_or_null, float* workspace,
+                                long long workspace_bytes, int B, int C, int H, int W, int S, void* stream);
+
+/*
+ * hdn_dlt_solve_bwd_f32: hdn_dlt_solve_f32.  [A|b] is rebuilt as the forward builds it (the reference's point order, dst = src + off as an fp32
+ * add), with rows (x, y, 1, 0, 0, 0, -u x, -u y | u) and (0, 0, 0, x, y, 1, -v x, -v y | v) per point.  In float64, by elimination with partial
+ * pivoting within an 8-lane group like the forward:
+ *   A h = b,   A^T lambda = grad_H[0:8]        (grad_H[8] meets the constant 1 and is ignored)
+ *   grad_b = lambda,   grad_A = -lambda h^T
+ * pushed through the rows to x, y, u, v; then grad_off = (grad_u, grad_v), grad_src = (grad_x + grad_u, grad_y + grad_v), in the caller's point
+ * order, each rounded to fp32 once.
+ * src[B,8], off[B,8], grad_H[B,9] -> grad_src[B,8] and/or grad_off[B,8].
+ * Differentiates DLT_solve, .../Oneline_DLTv1/utils.py:7-67 (training forward: homo_model_builder.py:166).
+ */
+int hdn_dlt_solve_bwd_f32(const float* src, const float* off, const float* grad_H, float* grad_src_or_null, float* grad_off_or_null, int B,
+                          void* stream);
+
+/*
+ * hdn_warp_bwd_f32: hdn_warp_f32.  x, y, the clamped taps x0, x1, y0, y1 and Ia = img[y0][x0], Ib = img[y1][x0], Ic = img[y0][x1],
+ * Id = img[y1][x1] are the forward's.  What the reference's autograd differentiates: the integer taps are constants, the nudge has derivative 1.
+ *   d out / d x = (Ic - Ia)(y1 - y) + (Id - Ib)(y - y0)
+ *   d out / d y = (Ib - Ia)(x1 - x) + (Id - Ic)(x - x0)
+ *   d x / d xs = W/2,  d y / d ys = H/2;   xs = T0 / t:  d xs / d T0 = 1 / t,  d xs / d t = -xs / t  (ys likewise)
+ *   T_r = theta[3r] gx + theta[3r+1] gy + theta[3r+2]
+ *   grad_theta[b] = the nine sums over the H W C terms of sample b
+ *   grad_img[b,c] += grad_out {wa, wb, wc, wd} at (y0,x0), (y1,x0), (y0,x1), (y1,x1); coinciding clamped taps simply add.
+ * img[B,C,H,W], theta[B,9], grad_out[B,H,W,C] (NHWC, the forward's output layout) -> grad_theta[B,9] and/or grad_img[B,C,H,W].
+ * workspace: hdn_warp_bwd_workspace_bytes(B, H, W) bytes, 16-byte aligned, needed for grad_theta only (else it may be NULL).
+ * Differentiates transformer, .../Oneline_DLTv1/utils.py:70-254 (training forward: homo_model_builder.py:168).
+ */
+long long hdn_warp_bwd_workspace_bytes(int B, int H, int W);
+int hdn_warp_bwd_f32(const float* img, const float* theta, const float* grad_out, float* grad_theta_or_null, float* grad_img_or_null,
+                     float* workspace, long long workspace_bytes, int B, int C, int H, int W, void* stream);
+
+/*
  * Device-resident frame handling: the uint8 frame [H,W,C] (HWC, BGR as cv2.imread delivers it) is
  * uploaded once; crops and warps are kernels.  `params` / `M` are DEVICE float64 arrays so that positions and homographies
  * produced on the device never visit the host.

@@ -1,0 +1,507 @@
+"""Shared by tests/test_gpu_geometry_bwd.py and tests/test_geometry_bwd_host.py: the restatements, the float64 closed-form backwards with the magnitudes of
+the bound, the fixtures and the device runners of the three geometry backwards (hdn_logpolar_sample_bwd_f32, hdn_dlt_solve_bwd_f32, hdn_warp_bwd_f32).
+Nothing here launches a kernel except the run_* functions.
+
+The restatements (any dtype): logpolar_rs = oracle.hdn_oracle.logpolar_sample with the caller's tables; dlt_rs = dlt_system + torch.linalg.solve with
+the fp32-rounded dst; transformer_rs = the oracle's transformer without its casts to fp32 (its fp32 forward is pinned to the oracle's bit for bit by the
+host test).  The truth of every test is float64: the closed forms below, which the host test pins to float64 autograd through the restatements.
+
+The closed forms return, per output element, the sum (the truth) and M: the same sum with |grad_out|, every image difference Ia - Ib replaced by
+|Ia| + |Ib| and absolute chain factors - the sum of the absolute terms that an fp32 evaluation rounds.  A bilinear sampler's derivative jumps where a
+sample coordinate crosses an integer, so float64 and fp32 must agree on the cell of every sample: logpolar_margin() / warp_margin() is the distance of the nearest
+unclamped coordinate to an integer, the bound fixtures (SEED) are chosen with a margin above 1e-4 (20 or more fp32 ulps at these sizes; the host test
+asserts it), and where a shape is too large for any data to keep that margin (127 x 127: 32,258 coordinates) the closed form takes the cells that the
+fp32 CPU restatement of the forward picks (cells=torch.float32) - the derivative on the cell the forward read.
+
+The bound on random data: |got - truth| <= K M with K = max(4 r_ref, 2e-6), r_ref = the worst |g32 - truth| / M of the reference formulation's own
+fp32 CPU autograd on the same fixture (the oracle restatement, F.grid_sample for the sampler).  4 x: the kernel performs the same roundings per term
+as the CPU path on coordinates computed by the forward's own statements, and differs only in reduction order and contraction.  2e-6: the relative
+term the project uses for the correlation backward.  DLT_solve: |got - truth| <= 2^-23 |truth| + 2^-23 max|truth| per sample and output: one fp32
+rounding of an fp64 solve whose own noise, cond(A) 2^-53, is three or more orders below."""
+import functools
+import os
+import sys
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+SEED = 20261019
+MARGIN = 1e-4                                            # no unclamped sample coordinate of a bound fixture is nearer to an integer
+K_FLOOR = 2e-6
+DLT_POINT_ORDER = (0, 1, 3, 2)                           # utils.py:18-26
+OFFSETS = [(0, 0, 0, 0, 0), (1, 2, 3, 1, 2)]             # float offsets of the image, parameter, grad_out and two output base pointers in a 16-byte line
+BYTE = 0xA5
+FILL = float(np.frombuffer(bytes([BYTE] * 4), dtype=np.float32)[0])
+PAD = 8                                                  # floats of 0xA5 around every output
+
+
+def k_bound(r_ref):
+    return max(4.0 * r_ref, K_FLOOR)
+
+
+def worst_ratio(got, truth, M):
+    """max |got - truth| / M; an element with M == 0 must be exact (inf otherwise)."""
+    err = (got.double() - truth.double()).abs()
+    M = M.double()
+    r = torch.where(M > 0, err / M.clamp_min(1e-300), torch.where(err > 0, torch.full_like(err, float("inf")), torch.zeros_like(err)))
+    return float(r.max())
+
+
+# ================================================================================================================= log-polar sampler
+def logpolar_rs(x, polar, tabs, dtype=torch.float64):
+    """oracle.hdn_oracle.logpolar_sample (hdn/models/logpolar.py:100-124) with the caller's tables, in `dtype`: x [B,C,H,W], polar [B,2] -> [B,C,S,S]."""
+    B, C, H, W = x.shape
+    rho, c, s = (t.to(dtype) for t in tabs)
+    ix = rho.unsqueeze(0) * c.unsqueeze(1)
+    iy = rho.unsqueeze(0) * s.unsqueeze(1)
+    gx = (ix.unsqueeze(0) + polar[:, 0].reshape(B, 1, 1)) / (H // 2)
+    gy = (iy.unsqueeze(0) + polar[:, 1].reshape(B, 1, 1)) / (W // 2)
+    return F.grid_sample(x, torch.stack([gx, gy], dim=3), mode="bilinear", padding_mode="border", align_corners=False)
+
+
+def logpolar_coords(polar, tabs, H, W, dtype):
+    """The unclamped pixel position (pxu, pyu) [B,S,S] of every sample by the statements of logpolar_kernel, each op rounded in `dtype`."""
+    rho, c, s = (t.to(dtype) for t in tabs)
+    p = polar.detach().to(dtype)
+    B = p.shape[0]
+    gx = (rho.unsqueeze(0) * c.unsqueeze(1)).unsqueeze(0) + p[:, 0].reshape(B, 1, 1)
+    gy = (rho.unsqueeze(0) * s.unsqueeze(1)).unsqueeze(0) + p[:, 1].reshape(B, 1, 1)
+    gx, gy = gx / float(H // 2), gy / float(W // 2)
+    return (gx + 1.0) * (W * 0.5) - 0.5, (gy + 1.0) * (H * 0.5) - 0.5
+
+
+def _margin(*coords):
+    return min(float((c.double() - c.double().round()).abs().min()) for c in coords)
+
+
+def logpolar_margin(polar, tabs, H, W):
+    return _margin(*logpolar_coords(polar, tabs, H, W, torch.float64))
+
+
+def logpolar_closed(x, polar, tabs, g, cells=torch.float64):
+    """Float64 closed-form backward of the sampler: (grad_polar [B,2], M_polar, grad_x [B,C,H,W], M_x).  cells: the dtype whose coordinates choose the
+    cell and the border rule of every sample."""
+    B, C, H, W = x.shape
+    S = tabs[0].numel()
+    xd, gd = x.detach().double(), g.detach().double()
+    pxu, pyu = logpolar_coords(polar, tabs, H, W, torch.float64)
+    cxu, cyu = logpolar_coords(polar, tabs, H, W, cells)
+    mx = ((cxu > 0) & (cxu < W - 1)).double()
+    my = ((cyu > 0) & (cyu < H - 1)).double()
+    px, py = pxu.clamp(0, W - 1), pyu.clamp(0, H - 1)
+    x0 = cxu.clamp(0, W - 1).floor().long()
+    y0 = cyu.clamp(0, H - 1).floor().long()
+    w, n = px - x0.double(), py - y0.double()
+    e, s = 1.0 - w, 1.0 - n
+    e_ok, s_ok = (x0 + 1 < W), (y0 + 1 < H)
+    x1, y1 = torch.where(e_ok, x0 + 1, x0), torch.where(s_ok, y0 + 1, y0)
+    flat = xd.reshape(B, C, H * W)
+
+    def take(yy, xx, ok):
+        idx = (yy * W + xx).reshape(B, 1, S * S).expand(B, C, S * S)
+        return flat.gather(2, idx).reshape(B, C, S, S) * ok.double().unsqueeze(1)
+
+    one = torch.ones_like(e_ok)
+    taps = ((y0, x0, one, s * e), (y0, x1, e_ok, s * w), (y1, x0, s_ok, n * e), (y1, x1, e_ok & s_ok, n * w))
+    v_nw, v_ne, v_sw, v_se = (take(yy, xx, ok) for yy, xx, ok, _ in taps)
+    u = lambda t: t.unsqueeze(1)
+    dpx = u(s) * (v_ne - v_nw) + u(n) * (v_se - v_sw)
+    dpy = u(e) * (v_sw - v_nw) + u(w) * (v_se - v_ne)
+    apx = u(s) * (v_ne.abs() + v_nw.abs()) + u(n) * (v_se.abs() + v_sw.abs())
+    apy = u(e) * (v_sw.abs() + v_nw.abs()) + u(w) * (v_se.abs() + v_ne.abs())
+    fx, fy = (W / 2) / (H // 2), (H / 2) / (W // 2)
+    gp = torch.stack([fx * (gd * dpx * u(mx)).sum(dim=(1, 2, 3)), fy * (gd * dpy * u(my)).sum(dim=(1, 2, 3))], dim=1)
+    Mp = torch.stack([fx * (gd.abs() * apx * u(mx)).sum(dim=(1, 2, 3)), fy * (gd.abs() * apy * u(my)).sum(dim=(1, 2, 3))], dim=1)
+    gxm, Mx = torch.zeros(B, C, H * W, dtype=torch.float64), torch.zeros(B, C, H * W, dtype=torch.float64)
+    for yy, xx, ok, wt in taps:
+        idx = (yy * W + xx).reshape(B, 1, S * S).expand(B, C, S * S)
+        term = (gd * u(wt * ok.double())).reshape(B, C, S * S)
+        gxm.scatter_add_(2, idx, term)
+        Mx.scatter_add_(2, idx, term.abs())
+    return gp, Mp, gxm.reshape(B, C, H, W), Mx.reshape(B, C, H, W)
+
+
+def logpolar_autograd(x, polar, tabs, g, dtype):
+    """(grad_polar, grad_x) of sum(logpolar_rs * g) by torch autograd in `dtype`."""
+    xr, pr = x.detach().to(dtype).requires_grad_(True), polar.detach().to(dtype).requires_grad_(True)
+    logpolar_rs(xr, pr, tabs, dtype).backward(g.to(dtype))
+    return pr.grad, xr.grad
+
+
+EXACT_TABS = (torch.tensor([0.0, 0.5, 1.5, 2.75]), torch.tensor([1.0, 0.0, -1.0, 0.5]), torch.tensor([0.0, 1.0, 0.5, -1.0]))
+# (H, W, C, polar): dyadic origins that push samples past both borders of both axes, one (-3.5 at W = 8) that puts the rho = 0 column on p == 0 exactly
+LOGPOLAR_EXACT = ((8, 8, 1, [[-3.5, 3.25]]), (8, 8, 3, [[-3.0, 3.25], [3.0, -2.5]]), (16, 16, 2, [[-7.0, 6.5], [7.25, -7.5], [0.25, 0.5]]),
+                  (8, 16, 2, [[-3.25, 6.0], [3.5, -7.0]]), (16, 8, 3, [[6.5, -3.0], [-7.5, 3.25], [1.0, 0.5]]))
+
+
+def _ints(rng, shape):
+    return torch.from_numpy(rng.integers(-3, 4, shape).astype(np.float32))
+
+
+@functools.lru_cache(maxsize=None)
+def logpolar_exact_problem(i):
+    """(x, polar, tabs, g, grad_polar, grad_x): integer image and grad_out in [-3, 3], dyadic tables and origins; float64 closed forms."""
+    H, W, C, polar = LOGPOLAR_EXACT[i]
+    polar = torch.tensor(polar)
+    B = polar.shape[0]
+    rng = np.random.default_rng(SEED + 31 * i)
+    x, g = _ints(rng, (B, C, H, W)), _ints(rng, (B, C, 4, 4))
+    gp, _, gx, _ = logpolar_closed(x, polar, EXACT_TABS, g)
+    return x, polar, EXACT_TABS, g, gp, gx
+
+
+def real_tables(S):
+    from hdn_amd import logpolar
+    return logpolar.tables(S)
+
+
+def _origins(rng, B, tabs, H, W, margin):
+    """[B,2] origins: sample b lies 0.42 of the crop from the centre towards a corner (b even: -x +y, b odd: +x -y, every third at the centre), so that
+    samples pass every border between them, plus a jitter uniform in +-1 that is redrawn until no coordinate of the sample is within `margin` of an
+    integer (margin None: drawn once)."""
+    rows = []
+    for b in range(B):
+        sign = 0.0 if b % 3 == 2 else (-1.0 if b % 2 == 0 else 1.0)
+        base = np.array([[sign * 0.42 * H, -sign * 0.42 * W]])          # (sic) x is scaled by H//2 and y by W//2 in the forward
+        for _ in range(20000):
+            p = torch.from_numpy((base + rng.uniform(-1, 1, (1, 2))).astype(np.float32))
+            if margin is None or logpolar_margin(p, tabs, H, W) > margin:
+                break
+        else:
+            raise AssertionError("no origin keeps the margin")
+        rows.append(p)
+    return torch.cat(rows)
+
+
+LOGPOLAR_BOUND = dict(B=2, C=3, H=31, W=29, S=15)
+
+
+@functools.lru_cache(maxsize=None)
+def logpolar_random_problem(B, C, H, W, S, cells32=False):
+    """N(0,1) image and grad_out, the module's own tables, origins (_origins) that push part of the samples past every border.
+    cells32=False: origins that keep MARGIN, float64 cells; True: any origin, the fp32 restatement's cells.
+    -> (x, polar, tabs, g, grad_polar, M_polar, grad_x, M_x)."""
+    rng = np.random.default_rng(SEED + 1009 * H + 101 * W + 11 * S + B + 7 * C)
+    tabs = real_tables(S)
+    x = torch.from_numpy(rng.standard_normal((B, C, H, W), dtype=np.float32))
+    g = torch.from_numpy(rng.standard_normal((B, C, S, S), dtype=np.float32))
+    polar = _origins(rng, B, tabs, H, W, None if cells32 else MARGIN)
+    return (x, polar, tabs, g) + logpolar_closed(x, polar, tabs, g, torch.float32 if cells32 else torch.float64)
+
+
+@functools.lru_cache(maxsize=None)
+def logpolar_r_ref(B=None, C=None, H=None, W=None, S=None, cells32=False):
+    """(r_ref of grad_polar, of grad_x): F.grid_sample's fp32 CPU autograd on the same fixture (default: the bound fixture).  r_ref belongs to a
+    shape: a bilinear weight is px - floor(px), so its error grows with the size of the coordinates."""
+    kw = LOGPOLAR_BOUND if B is None else dict(B=B, C=C, H=H, W=W, S=S, cells32=cells32)
+    x, polar, tabs, g, gp, Mp, gx, Mx = logpolar_random_problem(**kw)
+    p32, x32 = logpolar_autograd(x, polar, tabs, g, torch.float32)
+    return worst_ratio(p32, gp, Mp), worst_ratio(x32, gx, Mx)
+
+
+# ================================================================================================================= DLT solve
+def dlt_rs(src_p, off_set, dtype=torch.float64):
+    """oracle.hdn_oracle.dlt_system + torch.linalg.solve in `dtype`, dst = the fp32-rounded src + off (utils.py:36; derivative 1 to both): -> H [B,9]."""
+    B = src_p.shape[0]
+    round_off = ((src_p.detach().float() + off_set.detach().float()).double() - (src_p.detach().double() + off_set.detach().double())).to(dtype)
+    src = src_p.reshape(B, 4, 2)[:, DLT_POINT_ORDER, :]
+    dst = (src_p + off_set + round_off).reshape(B, 4, 2)[:, DLT_POINT_ORDER, :]
+    x, y = src[..., 0], src[..., 1]
+    u, v = dst[..., 0], dst[..., 1]
+    one, zero = torch.ones_like(x), torch.zeros_like(x)
+    row_u = torch.stack([x, y, one, zero, zero, zero, -(u * x), -(u * y)], dim=-1)
+    row_v = torch.stack([zero, zero, zero, x, y, one, -(v * x), -(v * y)], dim=-1)
+    A = torch.stack([row_u, row_v], dim=2).reshape(B, 8, 8)
+    b = torch.stack([u, v], dim=2).reshape(B, 8, 1)
+    h8 = torch.linalg.solve(A, b).reshape(B, 8)
+    return torch.cat([h8, torch.ones_like(h8[:, :1])], dim=1)
+
+
+def dlt_autograd(src_p, off_set, gH, dtype=torch.float64):
+    s, o = src_p.detach().to(dtype).requires_grad_(True), off_set.detach().to(dtype).requires_grad_(True)
+    dlt_rs(s, o, dtype).backward(gH.reshape(-1, 9).to(dtype))
+    return s.grad, o.grad
+
+
+def dlt_closed(src_p, off_set, gH):
+    """Float64 closed form of include/hdn_hip.h: A h = b, A^T lambda = grad_h, grad_A = -lambda h^T pushed through the rows: (grad_src, grad_off) [B,8]."""
+    B = src_p.shape[0]
+    s = src_p.detach().double().reshape(B, 4, 2)
+    d = (src_p.detach().float() + off_set.detach().float()).double().reshape(B, 4, 2)
+    gs, go = torch.zeros(B, 4, 2, dtype=torch.float64), torch.zeros(B, 4, 2, dtype=torch.float64)
+    for b in range(B):
+        A, rhs = torch.zeros(8, 8, dtype=torch.float64), torch.zeros(8, dtype=torch.float64)
+        for q, p in enumerate(DLT_POINT_ORDER):
+            x, y, u, v = s[b, p, 0], s[b, p, 1], d[b, p, 0], d[b, p, 1]
+            A[2 * q] = torch.stack([x, y, x * 0 + 1, x * 0, x * 0, x * 0, -u * x, -u * y])
+            A[2 * q + 1] = torch.stack([x * 0, x * 0, x * 0, x, y, x * 0 + 1, -v * x, -v * y])
+            rhs[2 * q], rhs[2 * q + 1] = u, v
+        h = torch.linalg.solve(A, rhs)
+        lam = torch.linalg.solve(A.t(), gH.reshape(B, 9)[b, :8].double())
+        gA = -torch.outer(lam, h)
+        for q, p in enumerate(DLT_POINT_ORDER):
+            x, y, u, v = s[b, p, 0], s[b, p, 1], d[b, p, 0], d[b, p, 1]
+            ru, rv = gA[2 * q], gA[2 * q + 1]
+            gx = ru[0] - u * ru[6] + rv[3] - v * rv[6]
+            gy = ru[1] - u * ru[7] + rv[4] - v * rv[7]
+            gu = -x * ru[6] - y * ru[7] + lam[2 * q]
+            gv = -x * rv[6] - y * rv[7] + lam[2 * q + 1]
+            go[b, p, 0], go[b, p, 1] = gu, gv
+            gs[b, p, 0], gs[b, p, 1] = gx + gu, gy + gv
+    return gs.reshape(B, 8), go.reshape(B, 8)
+
+
+DLT_CORNERS = {"production": [0.0, 0.0, 127.0, 0.0, 0.0, 127.0, 127.0, 127.0], "skewed": [3.0, -5.0, 120.0, 9.0, -8.0, 131.0, 140.0, 118.0]}
+DLT_BATCHES = (1, 7, 8, 9, 65)                           # either side of the 8-lane group and of the wave (8 samples)
+
+
+@functools.lru_cache(maxsize=None)
+def dlt_problem(kind, B):
+    """(src [B,8], off [B,8] uniform in +-32, grad_H [B,9] N(0,1), grad_src, grad_off float64)."""
+    rng = np.random.default_rng(SEED + 17 * B + (kind == "skewed"))
+    src = torch.tensor(DLT_CORNERS[kind]).repeat(B, 1)
+    off = torch.from_numpy(rng.uniform(-32, 32, (B, 8)).astype(np.float32))
+    gH = torch.from_numpy(rng.standard_normal((B, 9), dtype=np.float32))
+    return (src, off, gH) + dlt_closed(src, off, gH)
+
+
+def dlt_excess(got, truth):
+    """The largest |got - truth| - (2^-23 |truth| + 2^-23 max|truth| of the sample); <= 0 inside the bound."""
+    t = truth.double()
+    lim = 2.0 ** -23 * t.abs() + 2.0 ** -23 * t.abs().amax(dim=1, keepdim=True)
+    return float(((got.double() - t).abs() - lim).max()), float(((got.double() - t).abs() / lim).max())
+
+
+# ================================================================================================================= projective warp
+def transformer_rs(U, theta, dtype=torch.float64):
+    """oracle.hdn_oracle.transformer (utils.py:70-254) statement for statement in `dtype` instead of its casts to fp32; the grid is torch.linspace in
+    fp32 as there.  U [B,C,H,W], theta [B,9] -> [B,H,W,C]."""
+    B, C, H, W = U.shape
+    xs = torch.linspace(-1.0, 1.0, W)
+    ys = torch.linspace(-1.0, 1.0, H)
+    gx = xs.unsqueeze(0).expand(H, W).reshape(-1)
+    gy = ys.unsqueeze(1).expand(H, W).reshape(-1)
+    grid = torch.stack([gx, gy, torch.ones_like(gx)], dim=0).to(dtype)
+    T = torch.matmul(theta.reshape(-1, 3, 3).to(dtype), grid.unsqueeze(0).expand(B, 3, H * W))
+    t = T[:, 2, :].reshape(-1)
+    t = t + 1e-6 * (1.0 - (t.abs() >= 1e-7).to(dtype))
+    xs = T[:, 0, :].reshape(-1) / t
+    ys = T[:, 1, :].reshape(-1) / t
+    x = (xs + 1.0) * W / 2.0
+    y = (ys + 1.0) * H / 2.0
+    x0 = torch.floor(x).int()
+    y0 = torch.floor(y).int()
+    x1 = x0 + 1
+    y1 = y0 + 1
+    x0, x1 = x0.clamp(0, W - 1), x1.clamp(0, W - 1)
+    y0, y1 = y0.clamp(0, H - 1), y1.clamp(0, H - 1)
+    flat = U.permute(0, 2, 3, 1).reshape(-1, C).to(dtype)
+    base = (torch.arange(B) * (H * W)).repeat_interleave(H * W)
+    take = lambda yy, xx: flat[(base + yy.long() * W + xx.long())]
+    Ia, Ib, Ic, Id = take(y0, x0), take(y1, x0), take(y0, x1), take(y1, x1)
+    x0f, x1f, y0f, y1f = x0.to(dtype), x1.to(dtype), y0.to(dtype), y1.to(dtype)
+    wa = ((x1f - x) * (y1f - y)).unsqueeze(1)
+    wb = ((x1f - x) * (y - y0f)).unsqueeze(1)
+    wc = ((x - x0f) * (y1f - y)).unsqueeze(1)
+    wd = ((x - x0f) * (y - y0f)).unsqueeze(1)
+    return (wa * Ia + wb * Ib + wc * Ic + wd * Id).reshape(B, H, W, C)
+
+
+def warp_coords(theta, B, H, W, dtype):
+    """(gx, gy [HW]; t, xs, ys, x, y [B,HW]) by the statements of warp_pixel, each op rounded in `dtype`."""
+    gx = torch.linspace(-1.0, 1.0, W).unsqueeze(0).expand(H, W).reshape(-1)
+    gy = torch.linspace(-1.0, 1.0, H).unsqueeze(1).expand(H, W).reshape(-1)
+    grid = torch.stack([gx, gy, torch.ones_like(gx)], dim=0).to(dtype)
+    T = torch.matmul(theta.detach().reshape(B, 3, 3).to(dtype), grid.unsqueeze(0).expand(B, 3, H * W))
+    t = T[:, 2, :]
+    t = t + 1e-6 * (1.0 - (t.abs() >= 1e-7).to(dtype))
+    xs, ys = T[:, 0, :] / t, T[:, 1, :] / t
+    return gx.to(dtype), gy.to(dtype), t, xs, ys, (xs + 1.0) * W / 2.0, (ys + 1.0) * H / 2.0
+
+
+def warp_margin(theta, B, H, W):
+    c = warp_coords(theta, B, H, W, torch.float64)
+    return _margin(c[5], c[6])
+
+
+def warp_closed(U, theta, g, cells=torch.float64):
+    """Float64 closed-form backward of the warp: (grad_theta [B,9], M_theta, grad_U [B,C,H,W], M_U).  g: [B,H,W,C].  cells: the dtype whose
+    coordinates choose the integer taps of every pixel."""
+    B, C, H, W = U.shape
+    gx, gy, t, xs, ys, x, y = warp_coords(theta, B, H, W, torch.float64)
+    cx, cy = warp_coords(theta, B, H, W, cells)[5:]
+    xf, yf = cx.floor().double(), cy.floor().double()
+    x0, x1 = xf.clamp(0, W - 1).long(), (xf + 1).clamp(0, W - 1).long()
+    y0, y1 = yf.clamp(0, H - 1).long(), (yf + 1).clamp(0, H - 1).long()
+    ax, bx, ay, by = x1.double() - x, x - x0.double(), y1.double() - y, y - y0.double()
+    flat = U.detach().double().reshape(B, C, H * W)
+    gd = g.detach().double().reshape(B, H * W, C).permute(0, 2, 1)                     # [B,C,HW]
+    idx = lambda yy, xx: (yy * W + xx).unsqueeze(1).expand(B, C, H * W)
+    Ia, Ib, Ic, Id = (flat.gather(2, idx(yy, xx)) for yy, xx in ((y0, x0), (y1, x0), (y0, x1), (y1, x1)))
+    u = lambda v: v.unsqueeze(1)
+    sx = (gd * ((Ic - Ia) * u(ay) + (Id - Ib) * u(by))).sum(1)
+    sy = (gd * ((Ib - Ia) * u(ax) + (Id - Ic) * u(bx))).sum(1)
+    sxa = (gd.abs() * ((Ic.abs() + Ia.abs()) * u(ay.abs()) + (Id.abs() + Ib.abs()) * u(by.abs()))).sum(1)
+    sya = (gd.abs() * ((Ib.abs() + Ia.abs()) * u(ax.abs()) + (Id.abs() + Ic.abs()) * u(bx.abs()))).sum(1)
+    gxs, gys, gxsa, gysa = sx * (W / 2), sy * (H / 2), sxa * (W / 2), sya * (H / 2)
+    g0, g1, g2 = gxs / t, gys / t, -(gxs * xs + gys * ys) / t
+    a0, a1, a2 = gxsa / t.abs(), gysa / t.abs(), (gxsa * xs.abs() + gysa * ys.abs()) / t.abs()
+    nine = lambda p, q, r, kx, ky: torch.stack([(v * k).sum(1) for v in (p, q, r) for k in (kx, ky, torch.ones_like(kx))], dim=1)
+    gth, Mth = nine(g0, g1, g2, gx, gy), nine(a0, a1, a2, gx.abs(), gy.abs())
+    gU, MU = torch.zeros(B, C, H * W, dtype=torch.float64), torch.zeros(B, C, H * W, dtype=torch.float64)
+    for yy, xx, wt in ((y0, x0, ax * ay), (y1, x0, ax * by), (y0, x1, bx * ay), (y1, x1, bx * by)):
+        term = gd * u(wt)
+        gU.scatter_add_(2, idx(yy, xx), term)
+        MU.scatter_add_(2, idx(yy, xx), term.abs())
+    return gth, Mth, gU.reshape(B, C, H, W), MU.reshape(B, C, H, W)
+
+
+def warp_autograd(U, theta, g, dtype):
+    """(grad_theta [B,9], grad_U) of sum(transformer_rs * g) by torch autograd in `dtype`."""
+    Ur, tr = U.detach().to(dtype).requires_grad_(True), theta.detach().reshape(-1, 9).to(dtype).requires_grad_(True)
+    transformer_rs(Ur, tr, dtype).backward(g.to(dtype))
+    return tr.grad, Ur.grad
+
+
+WARP_THETAS = ([1, .25, .125, -.25, 1, .25, 0, 0, 1], [.5, 0, -.25, .5, .75, 0, 0, 0, 1], [1, 0, 0, 0, 1, 0, 0, 0, 1])
+# (H, W, C, B): W, H in {5, 9, 17} (a dyadic linspace step), H != W; sample b takes WARP_THETAS[b]
+WARP_EXACT = ((5, 9, 1, 1), (9, 5, 2, 2), (17, 9, 3, 3), (9, 17, 2, 3), (5, 17, 3, 2), (17, 5, 1, 3))
+
+
+@functools.lru_cache(maxsize=None)
+def warp_exact_problem(i):
+    """(U, theta [B,9], g [B,H,W,C], grad_theta, grad_U): integer image and grad_out in [-3, 3], dyadic affine theta; float64 closed forms."""
+    H, W, C, B = WARP_EXACT[i]
+    rng = np.random.default_rng(SEED + 53 * i)
+    U, g = _ints(rng, (B, C, H, W)), _ints(rng, (B, H, W, C))
+    theta = torch.tensor(WARP_THETAS[:B], dtype=torch.float32)
+    gth, _, gU, _ = warp_closed(U, theta, g)
+    return U, theta, g, gth, gU
+
+
+WARP_BOUND = dict(B=2, C=3, H=11, W=13)
+WARP_BOUND_SEED = 1                                      # of seeds 0-5 the first whose 11 x 13 fixture keeps MARGIN (asserted by the host test)
+
+
+def _warp_random(seed, B, C, H, W):
+    rng = np.random.default_rng(SEED + 100003 * seed + 1009 * H + 101 * W + B + 7 * C)
+    U = torch.from_numpy(rng.standard_normal((B, C, H, W), dtype=np.float32))
+    g = torch.from_numpy(rng.standard_normal((B, H, W, C), dtype=np.float32))
+    theta = torch.eye(3).reshape(1, 9).repeat(B, 1) + 0.08 * torch.from_numpy(rng.standard_normal((B, 9), dtype=np.float32))
+    return U, theta, g
+
+
+@functools.lru_cache(maxsize=None)
+def warp_random_problem(B, C, H, W, cells32=False, seed=WARP_BOUND_SEED):
+    """N(0,1) image and grad_out, theta = I + 0.08 N(0,1) -> (U, theta, g, grad_theta, M_theta, grad_U, M_U); cells32 as in logpolar_random_problem."""
+    U, theta, g = _warp_random(seed, B, C, H, W)
+    return (U, theta, g) + warp_closed(U, theta, g, torch.float32 if cells32 else torch.float64)
+
+
+@functools.lru_cache(maxsize=None)
+def warp_r_ref(B=None, C=None, H=None, W=None, cells32=False):
+    """(r_ref of grad_theta, of grad_U): the oracle restatement's fp32 CPU autograd on the same fixture (default: the bound fixture); per shape, as
+    logpolar_r_ref."""
+    kw = WARP_BOUND if B is None else dict(B=B, C=C, H=H, W=W, cells32=cells32)
+    U, theta, g, gth, Mth, gU, MU = warp_random_problem(**kw)
+    t32, U32 = warp_autograd(U, theta, g, torch.float32)
+    return worst_ratio(t32, gth, Mth), worst_ratio(U32, gU, MU)
+
+
+# ================================================================================================================= on the device
+def at_offset(t, off, dev, margin=0, fill=0.0):
+    """(view, whole buffer): the values of t (an int: that many floats of NaN) at float offset margin + off of a fresh allocation that ends `margin`
+    floats behind them; the rest holds `fill`."""
+    n = t if isinstance(t, int) else t.numel()
+    host = torch.full((margin + off + n + margin,), float(fill))
+    host[margin + off:margin + off + n] = float("nan") if isinstance(t, int) else t.reshape(-1)
+    buf = host.to(dev)
+    assert buf.data_ptr() % 16 == 0
+    return buf[margin + off:margin + off + n], buf
+
+
+def untouched(buf, lo, hi):
+    """Is every byte of the whole buffer (on the CPU) outside the floats [lo, hi) still 0xA5?"""
+    raw = buf.numpy().view(np.uint8).reshape(-1, 4)
+    return bool((raw[:lo] == BYTE).all()) and bool((raw[hi:] == BYTE).all())
+
+
+def _outputs(n1, n2, offsets, dev, need1, need2):
+    v1, b1 = at_offset(n1, offsets[3], dev, margin=PAD, fill=FILL)
+    v2, b2 = at_offset(n2, offsets[4], dev, margin=PAD, fill=FILL)
+    if not need1:
+        b1.fill_(FILL)
+    if not need2:
+        b2.fill_(FILL)
+    return v1, b1, v2, b2
+
+
+def _finish(dev, v1, b1, n1, o1, need1, v2, b2, n2, o2, need2):
+    torch.cuda.synchronize(dev)
+    b1c, b2c = b1.cpu(), b2.cpu()
+    clean = untouched(b1c, PAD + o1, PAD + o1 + n1) if need1 else untouched(b1c, 0, 0)
+    clean = clean and (untouched(b2c, PAD + o2, PAD + o2 + n2) if need2 else untouched(b2c, 0, 0))
+    return (v1.cpu() if need1 else None), (v2.cpu() if need2 else None), clean
+
+
+def run_logpolar(x, polar, tabs, g, dev, offsets=(0, 0, 0, 0, 0), need_polar=True, need_x=True):
+    """One raw call of hdn_logpolar_sample_bwd_f32: outputs from NaN inside 0xA5 margins, an output that is not asked for NULL and its buffer 0xA5
+    everywhere.  -> (grad_polar | None [B,2], grad_x | None [B,C,H,W] on the CPU, were all bytes outside the results left alone?)."""
+    from hdn_amd import _lib
+    lib = _lib.load()
+    B, C, H, W = x.shape
+    S = tabs[0].numel()
+    xd, pd, gd = at_offset(x, offsets[0], dev)[0], at_offset(polar, offsets[1], dev)[0], at_offset(g, offsets[2], dev)[0]
+    td = [t.to(dev) for t in tabs]
+    gpv, gpb, gxv, gxb = _outputs(B * 2, x.numel(), offsets, dev, need_polar, need_x)
+    nbytes = lib.hdn_logpolar_sample_bwd_workspace_bytes(B, S)
+    ws = torch.full((nbytes // 4,), float("nan"), device=dev)
+    rc = lib.hdn_logpolar_sample_bwd_f32(_lib.ptr(xd), _lib.ptr(pd), _lib.ptr(td[0]), _lib.ptr(td[1]), _lib.ptr(td[2]), _lib.ptr(gd),
+                                         _lib.ptr(gpv) if need_polar else None, _lib.ptr(gxv) if need_x else None,
+                                         _lib.ptr(ws) if need_polar else None, nbytes, B, C, H, W, S, _lib.stream_ptr(dev))
+    _lib.check(rc, "hdn_logpolar_sample_bwd_f32")
+    gp, gx, clean = _finish(dev, gpv, gpb, B * 2, offsets[3], need_polar, gxv, gxb, x.numel(), offsets[4], need_x)
+    return (gp.view(B, 2) if need_polar else None), (gx.view(B, C, H, W) if need_x else None), clean
+
+
+def run_warp(U, theta, g, dev, offsets=(0, 0, 0, 0, 0), need_theta=True, need_U=True):
+    """One raw call of hdn_warp_bwd_f32, as run_logpolar.  -> (grad_theta | None [B,9], grad_U | None, clean)."""
+    from hdn_amd import _lib
+    lib = _lib.load()
+    B, C, H, W = U.shape
+    Ud, td, gd = at_offset(U, offsets[0], dev)[0], at_offset(theta, offsets[1], dev)[0], at_offset(g, offsets[2], dev)[0]
+    gtv, gtb, gUv, gUb = _outputs(B * 9, U.numel(), offsets, dev, need_theta, need_U)
+    nbytes = lib.hdn_warp_bwd_workspace_bytes(B, H, W)
+    ws = torch.full((nbytes // 4,), float("nan"), device=dev)
+    rc = lib.hdn_warp_bwd_f32(_lib.ptr(Ud), _lib.ptr(td), _lib.ptr(gd), _lib.ptr(gtv) if need_theta else None, _lib.ptr(gUv) if need_U else None,
+                              _lib.ptr(ws) if need_theta else None, nbytes, B, C, H, W, _lib.stream_ptr(dev))
+    _lib.check(rc, "hdn_warp_bwd_f32")
+    gt, gU, clean = _finish(dev, gtv, gtb, B * 9, offsets[3], need_theta, gUv, gUb, U.numel(), offsets[4], need_U)
+    return (gt.view(B, 9) if need_theta else None), (gU.view(B, C, H, W) if need_U else None), clean
+
+
+def run_dlt(src, off, gH, dev, offsets=(0, 0, 0, 0, 0), need_src=True, need_off=True):
+    """One raw call of hdn_dlt_solve_bwd_f32, as run_logpolar.  -> (grad_src | None [B,8], grad_off | None [B,8], clean)."""
+    from hdn_amd import _lib
+    B = src.shape[0]
+    sd, od, gd = at_offset(src, offsets[0], dev)[0], at_offset(off, offsets[1], dev)[0], at_offset(gH, offsets[2], dev)[0]
+    gsv, gsb, gov, gob = _outputs(B * 8, B * 8, offsets, dev, need_src, need_off)
+    rc = _lib.load().hdn_dlt_solve_bwd_f32(_lib.ptr(sd), _lib.ptr(od), _lib.ptr(gd), _lib.ptr(gsv) if need_src else None,
+                                           _lib.ptr(gov) if need_off else None, B, _lib.stream_ptr(dev))
+    _lib.check(rc, "hdn_dlt_solve_bwd_f32")
+    gs, go, clean = _finish(dev, gsv, gsb, B * 8, offsets[3], need_src, gov, gob, B * 8, offsets[4], need_off)
+    return (gs.view(B, 8) if need_src else None), (go.view(B, 8) if need_off else None), clean
+
+
+def first_difference(got, truth):
+    """None, or where got (fp32) first differs from truth (float64 holding fp32-exact values)."""
+    bad = ~(got.double() == truth.double())
+    if not bool(bad.any()):
+        return None
+    at = tuple(bad.nonzero()[0].tolist())
+    return f"{int(bad.sum())} of {bad.numel()} differ; first at {at}: got {float(got[at])!r}, want {float(truth[at])!r}"
