@@ -26,7 +26,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .ops import _c_pack, _host_f32, bias_relu_
+from .ops import _pack_conv_search, _pack_w1, bias_relu_, head_conv_batch, head_conv_search, head_tail, head_tail_batch
 from .xcorr import out_shape, xcorr_depthwise, xcorr_depthwise_circular, xcorr_depthwise_multi
 
 
@@ -166,42 +166,22 @@ def refresh_template_cache(head, z_fs, rows=None):
     sel = slice(None) if rows is None else slice(rows, rows + 1) if isinstance(rows, int) else rows
     boxes = [getattr(head, "box" + str(i + 2)) for i in range(n)]
     branches = [br for box in boxes for br in (box.cls, box.loc)]
+    tp = getattr(head, "_hdn_template_pack", None) if _hip_heads_on(head) else None
+    if tp is not None and not (tp.ok and tp.key[0] == _param_versions(branches)):
+        tp = None                                            # (never built here: only the pack the forward took, for these weights)
     with torch.no_grad():
-        zs = [z[sel] for z in z_fs]
-        tp = getattr(head, "_hdn_template_pack", None) if _hip_heads_on(head) else None
-        if tp is not None and tp.ok and tp.key[0] == _param_versions(branches):
-            y = head_conv_batch(zs, tp.wsp, tp.bsp)           # the pack holds weights only: it serves any batch
-            new = [y[l, g] for l in range(n) for g in range(2)]
-        else:
-            new = [br.conv_kernel(z) for box, z in zip(boxes, zs) for br in (box.cls, box.loc)]
-        for dst, src in zip(cache.kern, new):
+        for dst, src in zip(cache.kern, _template_features(boxes, [z[sel] for z in z_fs], tp)):   # (the pack holds weights only: it serves any batch)
             dst[sel].copy_(src)
     cache.z_versions = tuple(z._version for z in z_fs)
     return True
-
-
-_HIP_HEADS = None
-
-
-def hip_heads() -> bool:
-    """HDN_HIP_HEADS (default off), read once: the template branch at any batch and conv_search at B > 1 on hdn_head_conv3x3_batch_f32."""
-    global _HIP_HEADS
-    if _HIP_HEADS is None:
-        _HIP_HEADS = os.environ.get("HDN_HIP_HEADS", "0") not in ("", "0")
-    return _HIP_HEADS
-
-
-def _hip_heads_on(head) -> bool:
-    v = getattr(head, "_hdn_hip_heads", None)                # the per-head attribute overrides the environment
-    return hip_heads() if v is None else bool(v)
 
 
 _HIP_HEADS_LEVEL = None
 
 
 def hip_heads_level() -> int:
-    """HDN_HIP_HEADS as a level, read once: 0 off (default), 1 what hip_heads() switches on, 2 also the 1x1 tail at B > 1 on hdn_head_tail_batch_f32.
-    Any other non-empty value is level 1, as hip_heads() reads it."""
+    """HDN_HIP_HEADS as a level, read once: 0 off (unset, empty or "0" after strip(): the default), 1 the template branch at any batch and conv_search at
+    B > 1 on hdn_head_conv3x3_batch_f32, 2 also the 1x1 tail at B > 1 on hdn_head_tail_batch_f32.  Any other value is level 1."""
     global _HIP_HEADS_LEVEL
     if _HIP_HEADS_LEVEL is None:
         v = os.environ.get("HDN_HIP_HEADS", "0").strip()
@@ -209,19 +189,31 @@ def hip_heads_level() -> int:
     return _HIP_HEADS_LEVEL
 
 
+def hip_heads() -> bool:
+    """Is HDN_HIP_HEADS on at any level?"""
+    return hip_heads_level() >= 1
+
+
 def _hip_heads_level_of(head) -> int:
-    v = getattr(head, "_hdn_hip_heads", None)                # True and 1: level 1; 2: level 2
+    v = getattr(head, "_hdn_hip_heads", None)                # the per-head attribute overrides the environment.  True and 1: level 1; 2: level 2
     if v is None:
         return hip_heads_level()
     return 2 if (v is not True and v == 2) else 1 if v else 0
 
 
+def _hip_heads_on(head) -> bool:
+    return _hip_heads_level_of(head) >= 1
+
+
 class _ConvPack:
     """The 3x3 convolutions of one side (conv_search or conv_kernel) of all levels, BatchNorm folded, cls || loc along CO: ws / bs the fp32 weights
     and biases per level, wsp / bsp the stream and the [n, CO] bias hdn_head_conv3x3(_batch)_f32 take (None where the kernel does not fit).
-    `key`: the version counters it was built from; `ok`: what the predicate of its path said for that key."""
+    `key`: the version counters it was built from; `ok`: its path's predicate said yes for that key and the kernel fits."""
 
     __slots__ = ("key", "ok", "ws", "bs", "wsp", "bsp")
+
+    def __init__(self):
+        self.wsp = self.bsp = None
 
 
 class _PackedHead:
@@ -246,6 +238,21 @@ def _head_key(self, boxes):
     return _versions(refs)
 
 
+def _bn_folds(bn):
+    """_fold_bn folds the running statistics and the affine weights: eval-mode BatchNorm only."""
+    return not (bn.training or not bn.track_running_stats or not bn.affine or bn.running_mean is None)
+
+
+def _conv_bn_relu_eval(seq):
+    """Is `seq` the 3x3 stage of the reference's DepthwiseXCorr in eval mode: Sequential(Conv2d without bias / stride 1 / no padding / no dilation /
+    groups 1, a BatchNorm2d _fold_bn can fold, ReLU)?  (The kernel size is the caller's business: it shows in the weight's shape.)"""
+    if not (isinstance(seq, nn.Sequential) and len(seq) == 3 and isinstance(seq[0], nn.Conv2d) and isinstance(seq[1], nn.BatchNorm2d)
+            and isinstance(seq[2], nn.ReLU)):
+        return False
+    c = seq[0]
+    return _bn_folds(seq[1]) and c.bias is None and c.stride == (1, 1) and c.padding == (0, 0) and c.dilation == (1, 1) and c.groups == 1
+
+
 def _packable(self, boxes, x_fs):
     """The packed path covers the reference's configuration: B = 1 on a GPU, every level with the same channel counts and the
     module layout of DepthwiseXCorr (conv3x3 no bias + BN + ReLU; conv1x1 no bias + BN + ReLU + conv1x1)."""
@@ -260,20 +267,12 @@ def _packable_any_batch(self, boxes, x_fs):
     ref = None
     for box in boxes:
         for br in (box.cls, box.loc):
-            cs, hd = br.conv_search, br.head
-            if not (isinstance(cs, nn.Sequential) and len(cs) == 3 and isinstance(cs[0], nn.Conv2d) and isinstance(cs[1], nn.BatchNorm2d)
-                    and isinstance(hd, nn.Sequential) and len(hd) == 4 and isinstance(hd[0], nn.Conv2d) and isinstance(hd[1], nn.BatchNorm2d)
-                    and isinstance(hd[3], nn.Conv2d)):
+            hd = br.head
+            if not (_conv_bn_relu_eval(br.conv_search) and isinstance(hd, nn.Sequential) and len(hd) == 4 and isinstance(hd[0], nn.Conv2d)
+                    and isinstance(hd[1], nn.BatchNorm2d) and isinstance(hd[2], nn.ReLU) and isinstance(hd[3], nn.Conv2d) and _bn_folds(hd[1])
+                    and hd[0].bias is None and hd[0].kernel_size == (1, 1) and hd[3].kernel_size == (1, 1) and hd[3].bias is not None):
                 return False
-            if not (isinstance(cs[2], nn.ReLU) and isinstance(hd[2], nn.ReLU)):
-                return False
-            if any(bn.training or not bn.track_running_stats or not bn.affine or bn.running_mean is None for bn in (cs[1], hd[1])):
-                return False          # _fold_bn folds the running statistics and the affine weights: eval-mode BatchNorm only
-            c0, h0, h3 = cs[0], hd[0], hd[3]
-            if (c0.bias is not None or c0.stride != (1, 1) or c0.padding != (0, 0) or c0.dilation != (1, 1) or c0.groups != 1
-                    or h0.bias is not None or h0.kernel_size != (1, 1) or h3.kernel_size != (1, 1) or h3.bias is None):
-                return False
-            sig = (tuple(c0.weight.shape), tuple(h0.weight.shape))
+            sig = (tuple(br.conv_search[0].weight.shape), tuple(hd[0].weight.shape))
             if ref is None:
                 ref = sig
             elif sig != ref:
@@ -289,29 +288,9 @@ def _fold_bn(conv, bn):
     return conv.weight * s.reshape(-1, 1, 1, 1), bn.bias - bn.running_mean * s
 
 
-def _pack_w1(w1):
-    """[G, H, H] fp32 (row = output channel) -> the stream hdn_head_tail_f32 takes (hdn_pack_head_tail_f32, csrc/pack.hip), on w1's device."""
-    from . import _lib
-
-    G, H, _ = w1.shape
-    lib, w = _lib.load(), _host_f32(w1)
-    return _c_pack("pack_head_tail", lib.hdn_pack_head_tail_bytes(G, H), lambda o, n: lib.hdn_pack_head_tail_f32(w.data_ptr(), G, H, o, n)).to(w1.device)
-
-
-def _pack_conv_search(ws):
-    """n folded conv_search weights [CO, 256, 3, 3] fp32 -> the stream hdn_head_conv3x3_f32 takes (hdn_pack_head_conv3x3_f32), on their device."""
-    import ctypes
-
-    from . import _lib
-
-    host = [_host_f32(t) for t in ws]
-    n, CO = len(host), host[0].shape[0]
-    if any(tuple(t.shape) != (CO, 256, 3, 3) for t in host):
-        raise ValueError("conv_search weights must be [CO, 256, 3, 3]")
-    lib = _lib.load()
-    ptrs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in host])
-    return _c_pack("pack_head_conv3x3", lib.hdn_pack_head_conv3x3_bytes(n, CO),
-                   lambda o, nb: lib.hdn_pack_head_conv3x3_f32(ptrs, n, CO, o, nb)).to(ws[0].device)
+def _in_fp16(ws):
+    """Folded |w| < 65504 everywhere (the kernels split a weight into two fp16 pieces; NaN is out).  `meta` weights have no values to look at: in."""
+    return ws[0].device.type == "meta" or all(float(w.detach().abs().max()) < 65504.0 for w in ws)
 
 
 def _patch_fits(Hi, Wi):
@@ -330,18 +309,17 @@ def _pack_convs(boxes, name):
         pk.bs.append(torch.cat([bc, bl], 0).contiguous())
     # all levels as one launch on the matrix cores (hdn_head_conv3x3_f32 / _batch_f32): 3x3 / stride 1 / no padding, 256 input channels
     w0 = pk.ws[0]
-    fits_conv = (w0.is_cuda and len(boxes) <= 4 and tuple(w0.shape[1:]) == (256, 3, 3) and w0.shape[0] % 32 == 0 and all(w.shape == w0.shape for w in pk.ws)
-                 and max(float(w.abs().max()) for w in pk.ws) < 65504.0)
-    pk.wsp = _pack_conv_search(pk.ws) if fits_conv else None
-    pk.bsp = torch.stack(pk.bs).contiguous() if fits_conv else None
+    if (w0.is_cuda and len(boxes) <= 4 and tuple(w0.shape[1:]) == (256, 3, 3) and w0.shape[0] % 32 == 0 and all(w.shape == w0.shape for w in pk.ws)
+            and _in_fp16(pk.ws)):
+        pk.wsp, pk.bsp = _pack_conv_search(pk.ws), torch.stack(pk.bs).contiguous()
     return pk
 
 
-def _template_packable(boxes, z_fs, need_gpu=True):
+def _template_packable(boxes, z_fs, need_gpu=True, in_range=True):
     """The template branch as one launch of hdn_head_conv3x3_batch_f32, at any B: fp32 on a GPU (need_gpu=False: anywhere, for host tests), every
     level the same shape with 256 channels inside the kernel's patch limit, n <= 4, and conv_kernel of every (level, branch) the reference's
-    Sequential(Conv2d 3x3 no bias / stride 1 / no padding, eval-mode BatchNorm2d, ReLU) with one hidden width (a multiple of 32: the cls and loc
-    halves are tile-aligned groups) and folded |w| < 65504 (two fp16 pieces)."""
+    3x3 stage (_conv_bn_relu_eval) with one hidden width (a multiple of 32: the cls and loc halves are tile-aligned groups) and folded |w| < 65504
+    (in_range=False: not looked at, for a caller that goes on to _pack_convs, which folds the weights anyway and looks then)."""
     z0 = z_fs[0]
     n = len(boxes)
     if (need_gpu and not z0.is_cuda) or z0.dtype != torch.float32 or z0.dim() != 4 or any(z.shape != z0.shape for z in z_fs):
@@ -349,155 +327,47 @@ def _template_packable(boxes, z_fs, need_gpu=True):
     B, C, Hi, Wi = z0.shape
     if n != len(z_fs) or not 1 <= n <= 4 or C != 256 or B < 1 or n * B > 65535 or not _patch_fits(Hi, Wi):
         return False
-    ref = None
-    for box in boxes:
-        for br in (box.cls, box.loc):
-            ck = br.conv_kernel
-            if not (isinstance(ck, nn.Sequential) and len(ck) == 3 and isinstance(ck[0], nn.Conv2d) and isinstance(ck[1], nn.BatchNorm2d)
-                    and isinstance(ck[2], nn.ReLU)):
-                return False
-            c0, bn = ck[0], ck[1]
-            if bn.training or not bn.track_running_stats or not bn.affine or bn.running_mean is None:
-                return False          # _fold_bn folds the running statistics and the affine weights: eval-mode BatchNorm only
-            if c0.bias is not None or c0.stride != (1, 1) or c0.padding != (0, 0) or c0.dilation != (1, 1) or c0.groups != 1:
-                return False
-            shape = tuple(c0.weight.shape)
-            if ref is None:
-                ref = shape
-            if shape != ref or shape[1:] != (256, 3, 3) or shape[0] % 32 != 0:
-                return False
-            if c0.weight.device.type != "meta" and not float(_fold_bn(c0, bn)[0].detach().abs().max()) < 65504.0:
-                return False
-    return True
+    stages = [br.conv_kernel for box in boxes for br in (box.cls, box.loc)]
+    if not all(_conv_bn_relu_eval(ck) for ck in stages):
+        return False
+    shape = tuple(stages[0][0].weight.shape)
+    if shape[1:] != (256, 3, 3) or shape[0] % 32 != 0 or any(tuple(ck[0].weight.shape) != shape for ck in stages):
+        return False
+    return not in_range or _in_fp16([_fold_bn(ck[0], ck[1])[0] for ck in stages])
+
+
+def _conv_pack(self, attr, key, applies, boxes, name):
+    """The _ConvPack of side `name` kept in attribute `attr` of the head, or None where `applies()` refuses or the kernel does not fit: rebuilt when
+    `key` changes (version counters and the input's shape), dropped by invalidate_template_cache."""
+    pk = getattr(self, attr, None)
+    if pk is None or pk.key != key:
+        pk = _pack_convs(boxes, name) if applies() else _ConvPack()
+        pk.key, pk.ok = key, pk.wsp is not None
+        object.__setattr__(self, attr, pk)
+    return pk if pk.ok else None
 
 
 def _template_pack(self, boxes, branches, z_fs):
-    """The _ConvPack of conv_kernel for this head, or None where _template_packable refuses: rebuilt when a conv_kernel parameter / buffer or the
-    template's shape changes (the version counters _TemplateCache is keyed on), dropped by invalidate_template_cache."""
+    """The _ConvPack of conv_kernel for this head, or None where _template_packable refuses; keyed on what _TemplateCache is and the template's shape."""
     key = (_param_versions(branches), tuple(z_fs[0].shape), z_fs[0].device, z_fs[0].dtype)
-    tp = getattr(self, "_hdn_template_pack", None)
-    if tp is None or tp.key != key:
-        if _template_packable(boxes, z_fs):
-            tp = _pack_convs(boxes, "conv_kernel")
-            tp.ok = tp.wsp is not None
-        else:
-            tp = _ConvPack()
-            tp.ok = False
-        tp.key = key
-        object.__setattr__(self, "_hdn_template_pack", tp)
-    return tp if tp.ok else None
+    return _conv_pack(self, "_hdn_template_pack", key, lambda: _template_packable(boxes, z_fs, in_range=False), boxes, "conv_kernel")
 
 
 def _search_pack(self, boxes, x_fs):
     """The _ConvPack of conv_search for the batched form (B > 1), or None where it does not apply; keyed as _PackedHead is."""
+    B, C, Hi, Wi = x_fs[0].shape
     key = (_head_key(self, boxes), tuple(x_fs[0].shape), x_fs[0].device, x_fs[0].dtype)
-    sp = getattr(self, "_hdn_search_pack", None)
-    if sp is None or sp.key != key:
-        _, C, Hi, Wi = x_fs[0].shape
-        if len(boxes) <= 4 and C == 256 and _patch_fits(Hi, Wi) and len(boxes) * x_fs[0].shape[0] <= 65535 and _packable_any_batch(self, boxes, x_fs):
-            sp = _pack_convs(boxes, "conv_search")
-            sp.ok = sp.wsp is not None
-        else:
-            sp = _ConvPack()
-            sp.ok = False
-        sp.key = key
-        object.__setattr__(self, "_hdn_search_pack", sp)
-    return sp if sp.ok else None
+    return _conv_pack(self, "_hdn_search_pack", key, lambda: (len(boxes) <= 4 and C == 256 and _patch_fits(Hi, Wi) and len(boxes) * B <= 65535
+                                                              and _packable_any_batch(self, boxes, x_fs)), boxes, "conv_search")
 
 
-def head_conv_batch(x_fs, wsp, bsp, groups=2):
-    """n levels [B, 256, Hi, Wi] through one launch of hdn_head_conv3x3_batch_f32 (3x3 / no padding + bias + ReLU with the stream `wsp` of
-    _pack_conv_search and the bias `bsp` [n, CO]) -> [n, groups, B, CO / groups, Ho, Wo] contiguous: out[l, g] is a contiguous [B, CO / groups, Ho, Wo].
-    An image that is dense NCHW or dense channels-last is read where it is, whatever the batch stride (a batch slice needs no copy)."""
-    import ctypes
-
-    from . import _lib
-
-    x0 = x_fs[0]
-    dev = _lib.require_device(*x_fs)
-    n, (B, C, Hi, Wi) = len(x_fs), x0.shape
-    if C != 256 or any(x.shape != x0.shape for x in x_fs):
-        raise ValueError("head_conv_batch: every level must be [B, 256, Hi, Wi] of one shape")
-    image = C * Hi * Wi
-    forms = ((Hi * Wi, Wi, 1), (1, Wi * C, C))                                    # (channel, row, pixel) strides: NCHW, channels-last
-    nhwc = 1 if tuple(x0.stride()[1:]) == forms[1] else 0
-
-    def dense(x):
-        return tuple(x.stride()[1:]) == forms[nhwc] and (B == 1 or x.stride(0) >= image)
-
-    xs = [x.detach() for x in x_fs]
-    xs = [x if dense(x) else x.contiguous(memory_format=torch.channels_last if nhwc else torch.contiguous_format) for x in xs]
-    if B > 1 and len({x.stride(0) for x in xs}) > 1:                                # one batch stride per launch
-        xs = [x if x.stride(0) == image else x.contiguous(memory_format=torch.channels_last if nhwc else torch.contiguous_format) for x in xs]
-    xbs = image if B == 1 else xs[0].stride(0)
-    CO = bsp.shape[1]
-    out = torch.empty((n, groups, B, CO // groups, Hi - 2, Wi - 2), dtype=torch.float32, device=dev)
-    with _lib.device_guard(dev):
-        rc = _lib.load().hdn_head_conv3x3_batch_f32((ctypes.c_void_p * n)(*[t.data_ptr() for t in xs]), _lib.ptr(wsp), _lib.ptr(bsp), _lib.ptr(out),
-                                                    n, B, groups, CO, Hi, Wi, nhwc, xbs, _lib.stream_ptr(dev))
-    _lib.check(rc, "head_conv_batch")
-    return out
-
-
-def head_conv_search(x_fs, pk):
-    """The n levels' conv_search (both branches) + bias + ReLU in one launch -> [n, 2 hidden, Ho, Wo] contiguous (hdn_head_conv3x3_f32)."""
-    import ctypes
-
-    from . import _lib
-
-    x0 = x_fs[0]
-    dev = _lib.require_device(*x_fs)
-    n, (_, C, Hi, Wi) = len(x_fs), x0.shape
-    nhwc = 0 if x0.is_contiguous() else 1
-    xs = []
-    for x in x_fs:
-        x = x.detach()
-        if not (x.is_contiguous() if nhwc == 0 else x.is_contiguous(memory_format=torch.channels_last)):
-            x = x.contiguous() if nhwc == 0 else x.contiguous(memory_format=torch.channels_last)
-        xs.append(x)
-    CO = pk.bsp.shape[1]
-    out = torch.empty((n, CO, Hi - 2, Wi - 2), dtype=torch.float32, device=dev)
-    arr = ctypes.c_void_p * n
-    with _lib.device_guard(dev):
-        rc = _lib.load().hdn_head_conv3x3_f32(arr(*[t.data_ptr() for t in xs]), _lib.ptr(pk.wsp), _lib.ptr(pk.bsp),
-                                              arr(*[out[i].data_ptr() for i in range(n)]), n, CO, Hi, Wi, nhwc, _lib.stream_ptr(dev))
-    _lib.check(rc, "head_conv_search")
-    return out
-
-
-def head_tail(feats, pk, n):
-    """feats [2n, H, Ho, Wo] -> out [2, om, Ho * Wo] through hdn_head_tail_f32 (pk: a _PackedHead with w1p)."""
-    from . import _lib
-
-    dev = _lib.require_device(feats)
-    G, H = feats.shape[0], feats.shape[1]
-    P = feats.shape[2] * feats.shape[3]
-    om = pk.wf.shape[1]
-    out = torch.empty((2, om, P), dtype=torch.float32, device=dev)
-    with _lib.device_guard(dev):
-        rc = _lib.load().hdn_head_tail_f32(_lib.ptr(feats), _lib.ptr(pk.w1p), _lib.ptr(pk.b1), _lib.ptr(pk.wf), _lib.ptr(pk.bf), _lib.ptr(out),
-                                           n, H, P, om, _lib.stream_ptr(dev))
-    _lib.check(rc, "head_tail")
-    return out
-
-
-def head_tail_batch(feats, pk, n, B):
-    """feats [2n, B, H, Ho, Wo] -> (cls [B, oc, Ho, Wo], loc [B, ol, Ho, Wo]), contiguous views of ONE output buffer, through hdn_head_tail_batch_f32
-    (pk: a _PackedHead with w1p)."""
-    from . import _lib
-
-    dev = _lib.require_device(feats)
-    if feats.dim() != 5 or feats.shape[0] != 2 * n or feats.shape[1] != B or feats.dtype != torch.float32 or not feats.is_contiguous():
-        raise ValueError(f"head_tail_batch: feats must be a contiguous float32 [{2 * n}, {B}, H, Ho, Wo], got {tuple(feats.shape)}")
-    H, Ho, Wo = feats.shape[2:]
-    P = Ho * Wo
-    out = torch.empty(B * (pk.oc + pk.ol) * P, dtype=torch.float32, device=dev)
-    with _lib.device_guard(dev):
-        rc = _lib.load().hdn_head_tail_batch_f32(_lib.ptr(feats), _lib.ptr(pk.w1p), _lib.ptr(pk.b1), _lib.ptr(pk.wf), _lib.ptr(pk.bf), _lib.ptr(out),
-                                                 n, B, H, P, pk.oc, pk.ol, _lib.stream_ptr(dev))
-    _lib.check(rc, "head_tail_batch")
-    split = B * pk.oc * P
-    return out[:split].view(B, pk.oc, Ho, Wo), out[split:].view(B, pk.ol, Ho, Wo)
+def _template_features(boxes, zs, tp):
+    """conv_kernel(z) of every (level, branch), (cls, loc) per level: with the template pack `tp` one launch, each a contiguous [B, hidden, h, w] view
+    of its output; without one (None) through the modules, in whatever layout they answer."""
+    if tp is None:
+        return [br.conv_kernel(z) for box, z in zip(boxes, zs) for br in (box.cls, box.loc)]
+    y = head_conv_batch(zs, tp.wsp, tp.bsp)
+    return [y[l, g] for l in range(len(zs)) for g in range(2)]
 
 
 def _tail_lds_bytes(n, hidden, om):
@@ -510,7 +380,15 @@ def _tail_fits(n, hidden, om, w1):
     """The shapes and range hdn_head_tail_f32 / hdn_head_tail_batch_f32 take: hidden 128 or 256, at most 8 output rows and 4 levels, the staged operands
     inside the 160 KB of LDS, and the folded first 1x1 weights `w1` inside fp16 (two pieces).  Asks nothing of the device."""
     return (hidden in (128, 256) and 1 <= om <= 8 and 1 <= n <= 4 and _tail_lds_bytes(n, hidden, om) <= 160 * 1024
-            and bool(float(w1.detach().abs().max()) < 65504.0))
+            and _in_fp16([w1]))
+
+
+def _level_weights(self, n, like):
+    """(cw, lw): what level i counts in the cls / loc sum (loc_scale apart) - the softmax of cls_weight / loc_weight of a weighted head, 1 / n otherwise."""
+    if self.weighted:
+        return F.softmax(self.cls_weight, 0), F.softmax(self.loc_weight, 0)
+    even = torch.full((n,), 1.0 / n, device=like.device, dtype=like.dtype)
+    return even, even
 
 
 def _pack_head(self, boxes, cs=None):
@@ -526,10 +404,7 @@ def _pack_head(self, boxes, cs=None):
     pk.w1 = torch.stack([w.reshape(hidden, -1) for w in w1]).contiguous()      # [2n, hidden, hidden]
     pk.b1 = torch.stack(b1).reshape(2 * n, hidden, 1).contiguous()
     dev, dt = pk.w1.device, pk.w1.dtype
-    if self.weighted:
-        cw, lw = F.softmax(self.cls_weight, 0), F.softmax(self.loc_weight, 0)
-    else:
-        cw = lw = torch.full((n,), 1.0 / n, device=dev, dtype=dt)
+    cw, lw = _level_weights(self, n, pk.w1)
     lw = lw * self.loc_scale
     pk.oc, pk.ol = boxes[0].cls.head[3].weight.shape[0], boxes[0].loc.head[3].weight.shape[0]
     om = max(pk.oc, pk.ol)
@@ -545,15 +420,20 @@ def _pack_head(self, boxes, cs=None):
     return pk
 
 
+def _packed_head(self, boxes, cs=None):
+    """The head's _PackedHead, rebuilt (around the _ConvPack `cs` of conv_search where the caller has one) when a tensor it was built from changed."""
+    pk = getattr(self, "_hdn_packed_head", None)
+    if pk is None or pk.key != _head_key(self, boxes):
+        pk = _pack_head(self, boxes, cs)
+        object.__setattr__(self, "_hdn_packed_head", pk)
+    return pk
+
+
 def _batched_forward(self, boxes, kern, x_fs, sp, circular):
     """Level 2 at B > 1: conv_search, the correlations and the tail as one launch each (head_conv_batch, xcorr_depthwise_multi into one feats buffer,
     head_tail_batch).  None where the tail does not fit (the caller goes on with the level-1 path)."""
     n, B = len(boxes), x_fs[0].shape[0]
-    pk = getattr(self, "_hdn_packed_head", None)
-    key = _head_key(self, boxes)
-    if pk is None or pk.key != key:
-        pk = _pack_head(self, boxes, sp)
-        object.__setattr__(self, "_hdn_packed_head", pk)
+    pk = _packed_head(self, boxes, sp)
     if pk.w1p is None or tuple(pk.w1.shape[1:]) != (sp.bsp.shape[1] // 2,) * 2:      # (the head's 1x1 is hidden x hidden on conv_search's channels)
         return None
     y = head_conv_batch(x_fs, sp.wsp, sp.bsp)                 # [n, 2, B, hidden, Ho, Wo]
@@ -567,16 +447,10 @@ def _batched_forward(self, boxes, kern, x_fs, sp, circular):
 
 def _packed_forward(self, boxes, kern, x_fs, circular):
     n = len(boxes)
-    pk = getattr(self, "_hdn_packed_head", None)
-    key = _head_key(self, boxes)
-    if pk is None or pk.key != key:
-        pk = _pack_head(self, boxes)
-        object.__setattr__(self, "_hdn_packed_head", pk)
+    pk = _packed_head(self, boxes)
     h = pk.hidden
     s_cls, s_loc = [], []
-    Hi, Wi = x_fs[0].shape[2], x_fs[0].shape[3]
-    rows = min((63 + Wi - 3) // (Wi - 2) + 3, Hi) if Wi > 2 else 0          # patch rows of 64 consecutive output pixels (head_conv.hip)
-    use_conv = (pk.wsp is not None and x_fs[0].shape[1] == 256 and Hi >= 3 and Wi >= 3 and rows * Wi <= 224
+    use_conv = (pk.wsp is not None and x_fs[0].shape[1] == 256 and _patch_fits(x_fs[0].shape[2], x_fs[0].shape[3])
                 and not getattr(self, "_hdn_no_head_conv", False))
     if use_conv:
         y = head_conv_search(x_fs, pk)
@@ -605,6 +479,28 @@ def _packed_forward(self, boxes, kern, x_fs, circular):
     return (out[0, :pk.oc].reshape(1, pk.oc, shape[2], shape[3]), out[1, :pk.ol].reshape(1, pk.ol, shape[2], shape[3]))
 
 
+def _module_forward(self, boxes, kern, x_fs, sp, circular, one_launch):
+    """Module by module around the correlations; with the _ConvPack `sp` of conv_search (level 1 at B > 1) that side as one launch.  `one_launch`: the
+    template features are of one shape and at most 8, what hdn_xcorr_depthwise_multi_f32 asks besides search features of one shape."""
+    n = len(boxes)
+    if sp is not None:
+        y = head_conv_batch(x_fs, sp.wsp, sp.bsp)             # conv_search of every level and both branches at B > 1: one launch
+        srch = [y[l, g] for l in range(n) for g in range(2)]
+    else:
+        srch = [br.conv_search(x) for box, x in zip(boxes, x_fs) for br in (box.cls, box.loc)]
+    if one_launch and all(s.shape == srch[0].shape for s in srch):
+        feats = xcorr_depthwise_multi(srch, kern, circular=circular)
+    else:
+        one = xcorr_depthwise_circular if circular else xcorr_depthwise
+        feats = [one(s, k) for s, k in zip(srch, kern)]
+    cls = [boxes[i].cls.head(feats[2 * i]) for i in range(n)]
+    loc = [boxes[i].loc.head(feats[2 * i + 1]) * self.loc_scale[i] for i in range(n)]
+    if not self.weighted:
+        return sum(cls) / n, sum(loc) / n                     # (one division of the sum, as the reference has it: not _level_weights' 1 / n per level)
+    cw, lw = _level_weights(self, n, cls[0])
+    return sum(cls[i] * cw[i] for i in range(n)), sum(loc[i] * lw[i] for i in range(n))
+
+
 def fused_forward(self, z_fs, x_fs, circular=None):
     """MultiBAN.forward / MultiCircBAN.forward (ban.py:102-127, ban_lp.py:66-92) with one correlation launch and
     cached template-branch features.  `self` needs box2.., (cls|loc)_weight, loc_scale, weighted.
@@ -627,51 +523,33 @@ def fused_forward(self, z_fs, x_fs, circular=None):
     if circular is None:
         circular = bool(getattr(boxes[0].cls, "_circular", False)) or type(boxes[0].cls).__name__.endswith("Circ")
     with torch.no_grad():
+        level = _hip_heads_level_of(self)
         cache = getattr(self, "_hdn_template_cache", None)
-        hip_heads_on = _hip_heads_on(self)
         if cache is None or not cache.matches(z_fs, branches, False):
-            tp = _template_pack(self, boxes, branches, z_fs) if hip_heads_on else None
-            if tp is not None:
-                y = head_conv_batch(z_fs, tp.wsp, tp.bsp)     # one launch; (cls, loc) per level, each a contiguous [B, hidden, h, w] view
-                kern = [y[l, g] for l in range(n) for g in range(2)]
-            else:
-                kern = [br.conv_kernel(z).contiguous() for box, z in zip(boxes, z_fs) for br in (box.cls, box.loc)]   # (NCHW once, not per frame)
+            tp = _template_pack(self, boxes, branches, z_fs) if level >= 1 else None
+            kern = [k.contiguous() for k in _template_features(boxes, z_fs, tp)]     # (NCHW once, not per frame; the pack's views are as they are)
             cache = _TemplateCache(z_fs, branches, False, kern)
             object.__setattr__(self, "_hdn_template_cache", cache)
         kern = cache.kern
+        # the shape facts the four forms ask about
+        B = x_fs[0].shape[0]
+        one_x = all(x.shape == x_fs[0].shape for x in x_fs)
+        one_k = all(k.shape == kern[0].shape for k in kern)
+        few = 2 * n <= 8                                      # what one launch of hdn_xcorr_depthwise_multi_f32 takes
         pv = getattr(self, "_hdn_packable", None)
         sig = (tuple(x_fs[0].shape), x_fs[0].device, x_fs[0].dtype)
         if pv is None or pv[0] != sig:
-            pv = (sig, 2 * n <= 8 and _packable(self, boxes, x_fs))
+            pv = (sig, few and _packable(self, boxes, x_fs))
             object.__setattr__(self, "_hdn_packable", pv)
-        if (pv[1] and all(x.shape == x_fs[0].shape for x in x_fs) and all(k.shape == kern[0].shape for k in kern)
-                and not getattr(self, "_hdn_no_packed_head", False)):
-            return _packed_forward(self, boxes, kern, x_fs, circular)
-        sp = _search_pack(self, boxes, x_fs) if hip_heads_on and x_fs[0].shape[0] > 1 else None
-        if (sp is not None and 2 * n <= 8 and _hip_heads_level_of(self) == 2 and all(k.shape == kern[0].shape for k in kern)
-                and kern[0].shape[:2] == (x_fs[0].shape[0], sp.bsp.shape[1] // 2) and not getattr(self, "_hdn_no_head_tail", False)):
-            out = _batched_forward(self, boxes, kern, x_fs, sp, circular)     # level 2: the 1x1 tail too, three launches in all
+        if pv[1] and one_x and one_k and not getattr(self, "_hdn_no_packed_head", False):
+            return _packed_forward(self, boxes, kern, x_fs, circular)                # B = 1, packed
+        sp = _search_pack(self, boxes, x_fs) if level >= 1 and B > 1 else None
+        if (sp is not None and few and level == 2 and one_k and kern[0].shape[:2] == (B, sp.bsp.shape[1] // 2)
+                and not getattr(self, "_hdn_no_head_tail", False)):
+            out = _batched_forward(self, boxes, kern, x_fs, sp, circular)            # level 2: the 1x1 tail too, three launches in all
             if out is not None:
                 return out
-        if sp is not None:
-            y = head_conv_batch(x_fs, sp.wsp, sp.bsp)         # conv_search of every level and both branches at B > 1: one launch
-            srch = [y[l, g] for l in range(n) for g in range(2)]
-        else:
-            srch = [br.conv_search(x) for box, x in zip(boxes, x_fs) for br in (box.cls, box.loc)]
-        same = all(k.shape == kern[0].shape for k in kern) and all(s.shape == srch[0].shape for s in srch)
-        if same and len(kern) <= 8:
-            feats = xcorr_depthwise_multi(srch, kern, circular=circular)
-        else:
-            one = xcorr_depthwise_circular if circular else xcorr_depthwise
-            feats = [one(s, k) for s, k in zip(srch, kern)]
-        cls = [boxes[i].cls.head(feats[2 * i]) for i in range(n)]
-        loc = [boxes[i].loc.head(feats[2 * i + 1]) * self.loc_scale[i] for i in range(n)]
-        if self.weighted:
-            cw, lw = F.softmax(self.cls_weight, 0), F.softmax(self.loc_weight, 0)
-            c = sum(cls[i] * cw[i] for i in range(n))
-            l = sum(loc[i] * lw[i] for i in range(n))
-            return c, l
-        return sum(cls) / n, sum(loc) / n
+        return _module_forward(self, boxes, kern, x_fs, sp, circular, one_k and few)
 
 
 class MultiBAN(nn.Module):

@@ -6,6 +6,8 @@ torch's caching allocator and launches on torch's current stream.  There is no f
 """
 from __future__ import annotations
 
+import ctypes
+
 import torch
 import torch.nn as nn
 
@@ -133,6 +135,23 @@ def pack_simi_stem(weight):
     return _pack("pack_simi_stem", "[64, 3, 7, 7]", [weight], [(64, 3, 7, 7)])
 
 
+def _pack_w1(w1):
+    """[G, H, H] fp32 (row = output channel) -> the stream hdn_head_tail_f32 takes (hdn_pack_head_tail_f32, csrc/pack.hip), on w1's device."""
+    G, H = w1.shape[0], w1.shape[1]
+    return _pack("pack_head_tail", "[G, H, H]", [w1], [(G, H, H)], G, H).to(w1.device)
+
+
+def _pack_conv_search(ws):
+    """n folded conv_search weights [CO, 256, 3, 3] fp32 -> the stream hdn_head_conv3x3_f32 takes (hdn_pack_head_conv3x3_f32), on their device."""
+    host = [_host_f32(t) for t in ws]
+    n, CO = len(host), host[0].shape[0]
+    if any(tuple(t.shape) != (CO, 256, 3, 3) for t in host):
+        raise ValueError("conv_search weights must be [CO, 256, 3, 3]")
+    lib, ptrs = _lib.load(), _ptr_array(host)
+    return _c_pack("pack_head_conv3x3", lib.hdn_pack_head_conv3x3_bytes(n, CO),
+                   lambda o, nb: lib.hdn_pack_head_conv3x3_f32(ptrs, n, CO, o, nb)).to(ws[0].device)
+
+
 # ------------------------------------------------------------------------------------------------------------------------- launch helpers
 _CL = torch.channels_last
 
@@ -140,6 +159,11 @@ _CL = torch.channels_last
 def _opt(t):
     """The device pointer of an optional tensor (NULL for None)."""
     return _lib.ptr(t) if t is not None else None
+
+
+def _ptr_array(tensors):
+    """The data pointers of `tensors` as the `const float* const*` of the C side (the caller keeps the tensors alive until the call is made)."""
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
 
 
 def _square_cl(x):
@@ -387,3 +411,77 @@ def simi_stem(x, wpacked, bias):
     out = _empty_cl((B, 64, Sp, Sp), dev)
     _launch("simi_stem", dev, lib.hdn_simi_stem_f32, _lib.ptr(x), _lib.ptr(wpacked), _lib.ptr(bias), _lib.ptr(out), B, S, 0)
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------------- the heads' entry points
+def _head_levels(x_fs, nhwc):
+    """The levels [B, C, Hi, Wi] of a head convolution as its kernel reads them -> (tensors, batch stride in elements).  An image that is dense NCHW
+    (nhwc = 0) / dense channels-last (nhwc = 1) is read where it is, whatever the batch stride (a batch slice needs no copy); anything else is copied
+    to that layout, and so is a level whose batch stride differs from the others' (one batch stride per launch)."""
+    B, C, Hi, Wi = x_fs[0].shape
+    image = C * Hi * Wi
+    form = (1, Wi * C, C) if nhwc else (Hi * Wi, Wi, 1)                             # (channel, row, pixel) strides
+    fmt = _CL if nhwc else torch.contiguous_format
+    xs = [x.detach() for x in x_fs]
+    xs = [x if tuple(x.stride()[1:]) == form and (B == 1 or x.stride(0) >= image) else x.contiguous(memory_format=fmt) for x in xs]
+    if B > 1 and len({x.stride(0) for x in xs}) > 1:
+        xs = [x if x.stride(0) == image else x.contiguous(memory_format=fmt) for x in xs]
+    return xs, (image if B == 1 else xs[0].stride(0))
+
+
+def head_conv_batch(x_fs, wsp, bsp, groups=2):
+    """n levels [B, 256, Hi, Wi] through one launch of hdn_head_conv3x3_batch_f32 (3x3 / no padding + bias + ReLU with the stream `wsp` of
+    _pack_conv_search and the bias `bsp` [n, CO]) -> [n, groups, B, CO / groups, Ho, Wo] contiguous: out[l, g] is a contiguous [B, CO / groups, Ho, Wo].
+    Channels-last where level 0 is dense channels-last, NCHW otherwise (_head_levels)."""
+    x0 = x_fs[0]
+    dev = _lib.require_device(*x_fs)
+    n, (B, C, Hi, Wi) = len(x_fs), x0.shape
+    if C != 256 or any(x.shape != x0.shape for x in x_fs):
+        raise ValueError("head_conv_batch: every level must be [B, 256, Hi, Wi] of one shape")
+    nhwc = int(tuple(x0.stride()[1:]) == (1, Wi * C, C))
+    xs, xbs = _head_levels(x_fs, nhwc)
+    CO = bsp.shape[1]
+    out = torch.empty((n, groups, B, CO // groups, Hi - 2, Wi - 2), dtype=torch.float32, device=dev)
+    _launch("head_conv_batch", dev, _lib.load().hdn_head_conv3x3_batch_f32, _ptr_array(xs), _lib.ptr(wsp), _lib.ptr(bsp), _lib.ptr(out),
+            n, B, groups, CO, Hi, Wi, nhwc, xbs)
+    return out
+
+
+def head_conv_search(x_fs, pk):
+    """The n levels' conv_search (both branches) + bias + ReLU in one launch -> [n, 2 hidden, Ho, Wo] contiguous (hdn_head_conv3x3_f32; pk: wsp / bsp of
+    a _PackedHead).  NCHW where level 0 is NCHW-contiguous, channels-last otherwise (_head_levels)."""
+    x0 = x_fs[0]
+    dev = _lib.require_device(*x_fs)
+    n, (_, C, Hi, Wi) = len(x_fs), x0.shape
+    nhwc = 0 if x0.is_contiguous() else 1
+    xs, _ = _head_levels(x_fs, nhwc)
+    CO = pk.bsp.shape[1]
+    out = torch.empty((n, CO, Hi - 2, Wi - 2), dtype=torch.float32, device=dev)
+    _launch("head_conv_search", dev, _lib.load().hdn_head_conv3x3_f32, _ptr_array(xs), _lib.ptr(pk.wsp), _lib.ptr(pk.bsp), _ptr_array(list(out)),
+            n, CO, Hi, Wi, nhwc)
+    return out
+
+
+def head_tail(feats, pk, n):
+    """feats [2n, H, Ho, Wo] -> out [2, om, Ho * Wo] through hdn_head_tail_f32 (pk: a _PackedHead with w1p)."""
+    dev = _lib.require_device(feats)
+    H, P, om = feats.shape[1], feats.shape[2] * feats.shape[3], pk.wf.shape[1]
+    out = torch.empty((2, om, P), dtype=torch.float32, device=dev)
+    _launch("head_tail", dev, _lib.load().hdn_head_tail_f32, _lib.ptr(feats), _lib.ptr(pk.w1p), _lib.ptr(pk.b1), _lib.ptr(pk.wf), _lib.ptr(pk.bf),
+            _lib.ptr(out), n, H, P, om)
+    return out
+
+
+def head_tail_batch(feats, pk, n, B):
+    """feats [2n, B, H, Ho, Wo] -> (cls [B, oc, Ho, Wo], loc [B, ol, Ho, Wo]), contiguous views of ONE output buffer, through hdn_head_tail_batch_f32
+    (pk: a _PackedHead with w1p)."""
+    dev = _lib.require_device(feats)
+    if feats.dim() != 5 or feats.shape[0] != 2 * n or feats.shape[1] != B or feats.dtype != torch.float32 or not feats.is_contiguous():
+        raise ValueError(f"head_tail_batch: feats must be a contiguous float32 [{2 * n}, {B}, H, Ho, Wo], got {tuple(feats.shape)}")
+    H, Ho, Wo = feats.shape[2:]
+    P = Ho * Wo
+    out = torch.empty(B * (pk.oc + pk.ol) * P, dtype=torch.float32, device=dev)
+    _launch("head_tail_batch", dev, _lib.load().hdn_head_tail_batch_f32, _lib.ptr(feats), _lib.ptr(pk.w1p), _lib.ptr(pk.b1), _lib.ptr(pk.wf), _lib.ptr(pk.bf),
+            _lib.ptr(out), n, B, H, P, pk.oc, pk.ol)
+    split = B * pk.oc * P
+    return out[:split].view(B, pk.oc, Ho, Wo), out[split:].view(B, pk.ol, Ho, Wo)

@@ -129,3 +129,60 @@ def head_inputs(circular, B, seed):
     g = torch.Generator().manual_seed(seed)
     zs, xs = (9, 9) if circular else (7, 15)
     return ([torch.randn(B, 256, zs, zs, generator=g) for _ in range(3)], [torch.randn(B, 256, xs, xs, generator=g) for _ in range(3)])
+
+
+# ------------------------------------------------------------------------------------------------- the module-layout predicates' cases
+def small_head(levels=1, hidden=32, cin=256):
+    """A MultiBAN of `levels` levels with cin -> hidden branches (the constructor's own are cin -> cin), eval mode: the smallest the predicates accept."""
+    from hdn_amd import heads
+    torch.manual_seed(9)
+    m = heads.MultiBAN([cin] * levels, 2, weighted=True)
+    for i in range(levels):
+        setattr(m, "box" + str(i + 2), heads.DepthwiseBAN(cin, hidden, 2))
+    return m.eval()
+
+
+def _reconv(stage, **kw):
+    c = stage[0]
+    stage[0] = torch.nn.Conv2d(c.in_channels, c.out_channels, 3, **{"bias": False, **kw})
+
+
+def _weight(stage, v):
+    stage[0].weight.data[3, 5, 1, 1] = v
+
+
+# one mutation of box2.cls's 3x3 stage each (a Sequential(Conv2d, BatchNorm2d, ReLU))
+STAGE_MUTATIONS = {
+    "bias": lambda st: _reconv(st, bias=True),
+    "stride2": lambda st: _reconv(st, stride=2),
+    "padding1": lambda st: _reconv(st, padding=1),
+    "dilation2": lambda st: _reconv(st, dilation=2),
+    "groups2": lambda st: _reconv(st, groups=2),
+    "bn_training": lambda st: st[1].train(),
+    "bn_not_affine": lambda st: st.__setitem__(1, torch.nn.BatchNorm2d(st[1].num_features, affine=False).eval()),
+    "bn_no_running_stats": lambda st: st.__setitem__(1, torch.nn.BatchNorm2d(st[1].num_features, track_running_stats=False).eval()),
+    "identity": lambda st: st.__setitem__(2, torch.nn.Identity()),
+    "length4": lambda st: st.append(torch.nn.Identity()),
+    "weight7e4": lambda st: _weight(st, 7e4),
+}
+# ... and whole heads: (levels, hidden, input channels, input side per level; None: the caller's)
+HEAD_VARIANTS = {
+    "reference": (1, 32, 256, [None]),
+    "hidden48": (1, 48, 256, [None]),
+    "cin128": (1, 32, 128, [None]),
+    "two_shapes": (2, 32, 256, [None, 9]),
+    "five_levels": (5, 32, 256, [None] * 5),
+    "side17": (1, 32, 256, [17]),
+    "side50": (1, 32, 256, [50]),
+}
+STAGE_CASES = list(HEAD_VARIANTS) + list(STAGE_MUTATIONS)
+
+
+def stage_case(name, side, B=1, S=5, dev="cpu"):
+    """Case `name` applied to `side` (conv_kernel / conv_search) -> (head, its boxes, the levels' inputs [B, C, S, S] of zeros), on `dev`."""
+    levels, hidden, cin, sides = HEAD_VARIANTS.get(name, HEAD_VARIANTS["reference"])
+    m = small_head(levels, hidden, cin)
+    if name in STAGE_MUTATIONS:
+        STAGE_MUTATIONS[name](getattr(m.box2.cls, side))
+    m = m.to(dev)
+    return m, [getattr(m, "box" + str(i + 2)) for i in range(levels)], [torch.zeros(B, cin, s or S, s or S, device=dev) for s in sides]

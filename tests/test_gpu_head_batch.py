@@ -220,6 +220,88 @@ def test_through_the_heads(dev, cls_name, B, packed, monkeypatch):
         assert err <= 4 * e_ref + 1e-5 * scale, (name, err, e_ref, scale)
 
 
+# ----------------------------------------------------------------------------------------------------------------- 5b. predicates and packs
+# What the parent of the heads' untangling answered (head_batch_cases.stage_case, hidden 32, [B, 256, 5, 5]); the only launches are the packers' uploads.
+# _packable_any_batch asks for the module layout and one shape, nothing of channel counts, levels or the patch: those are _search_pack's.  (hidden48: the
+# pack is built, 2 x 48 = 96 channels being a multiple of 32, although the kernel wants each half tile-aligned: characterised here, not endorsed.)
+LAYOUT_REFUSED = {"bias", "stride2", "padding1", "dilation2", "groups2", "bn_training", "bn_not_affine", "bn_no_running_stats", "identity", "length4"}
+SEARCH_PACKABLE = {name: name not in LAYOUT_REFUSED | {"two_shapes"} for name in HB.STAGE_CASES}
+SEARCH_PACK = {name: name in ("reference", "hidden48", "side17") for name in HB.STAGE_CASES}
+TEMPLATE_PACK = {name: name in ("reference", "side17") for name in HB.STAGE_CASES}
+
+
+def _rehead(hd, i, **kw):
+    c = hd[i]
+    hd[i] = torch.nn.Conv2d(c.in_channels, c.out_channels, **{"kernel_size": 1, "bias": c.bias is not None, **kw})
+
+
+# one mutation of box2.loc's 1x1 head each (a Sequential(Conv2d, BatchNorm2d, ReLU, Conv2d with bias))
+HEAD_MUTATIONS = {
+    "bias0": lambda hd: _rehead(hd, 0, bias=True),
+    "kernel0": lambda hd: _rehead(hd, 0, kernel_size=3, padding=1),
+    "bn_training": lambda hd: hd[1].train(),
+    "bn_not_affine": lambda hd: hd.__setitem__(1, torch.nn.BatchNorm2d(hd[1].num_features, affine=False).eval()),
+    "bn_no_running_stats": lambda hd: hd.__setitem__(1, torch.nn.BatchNorm2d(hd[1].num_features, track_running_stats=False).eval()),
+    "identity": lambda hd: hd.__setitem__(2, torch.nn.Identity()),
+    "length5": lambda hd: hd.append(torch.nn.Identity()),
+    "no_bias3": lambda hd: _rehead(hd, 3, bias=False),
+    "kernel3": lambda hd: _rehead(hd, 3, kernel_size=3, padding=1),
+}
+
+
+@pytest.mark.parametrize("B", [1, 2])
+def test_search_predicates_and_pack_truth_table(dev, B):
+    from hdn_amd import heads as HD
+    assert list(SEARCH_PACKABLE) == HB.STAGE_CASES
+    any_batch, b1, pack = {}, {}, {}
+    with torch.no_grad():
+        for name in HB.STAGE_CASES:
+            m, boxes, x = HB.stage_case(name, "conv_search", B=B, dev=dev)
+            any_batch[name], b1[name] = HD._packable_any_batch(m, boxes, x), HD._packable(m, boxes, x)
+            pack[name] = HD._search_pack(m, boxes, x) is not None
+            assert (getattr(m._hdn_search_pack, "wsp", None) is not None) == m._hdn_search_pack.ok == pack[name], name
+        for name, mutate in HEAD_MUTATIONS.items():
+            m, boxes, x = HB.stage_case("reference", "conv_search", B=B, dev="cpu")
+            mutate(m.box2.loc.head)
+            m, x = m.to(dev), [t.to(dev) for t in x]
+            got = HD._packable_any_batch(m, boxes, x), HD._packable(m, boxes, x), HD._search_pack(m, boxes, x)
+            assert got == (False, False, None), (name, got)
+    assert any_batch == SEARCH_PACKABLE
+    assert b1 == {name: ok and B == 1 for name, ok in SEARCH_PACKABLE.items()}
+    assert pack == SEARCH_PACK
+
+
+def test_template_pack_truth_table(dev):
+    from hdn_amd import heads as HD
+    got = {}
+    with torch.no_grad():
+        for name in HB.STAGE_CASES:
+            m, boxes, z = HB.stage_case(name, "conv_kernel", B=2, dev=dev)
+            got[name] = HD._template_pack(m, boxes, [br for box in boxes for br in (box.cls, box.loc)], z) is not None
+            assert (getattr(m._hdn_template_pack, "wsp", None) is not None) == m._hdn_template_pack.ok == got[name], name
+    assert got == TEMPLATE_PACK
+
+
+def test_pack_keys_follow_in_place_weight_updates(dev):
+    """Each pack is kept while its own side's tensors stand and rebuilt, under another key, after an in-place update of one of them."""
+    from hdn_amd import heads as HD
+    m, boxes, x = HB.stage_case("reference", "conv_search", B=2, dev=dev)
+    branches = [br for box in boxes for br in (box.cls, box.loc)]
+    with torch.no_grad():
+        sp, tp = HD._search_pack(m, boxes, x), HD._template_pack(m, boxes, branches, x)
+        assert HD._search_pack(m, boxes, x) is sp and HD._template_pack(m, boxes, branches, x) is tp
+        m.box2.loc.conv_kernel[0].weight.mul_(0.5)                                       # the template side only
+        tp2 = HD._template_pack(m, boxes, branches, x)
+        assert tp2 is not tp and tp2.key != tp.key and tp2.ok and not torch.equal(tp2.ws[0], tp.ws[0])
+        assert HD._search_pack(m, boxes, x) is sp
+        m.box2.cls.conv_search[1].running_var.add_(0.25)                                 # the search side only: a BatchNorm buffer counts
+        sp2 = HD._search_pack(m, boxes, x)
+        assert sp2 is not sp and sp2.key != sp.key and sp2.ok and not torch.equal(sp2.ws[0], sp.ws[0])
+        assert HD._template_pack(m, boxes, branches, x) is tp2
+        m.loc_scale.mul_(2.0)                                                            # the head's own parameters are in the search pack's key
+        assert HD._search_pack(m, boxes, x) is not sp2 and HD._template_pack(m, boxes, branches, x) is tp2
+
+
 # ----------------------------------------------------------------------------------------------------------------- 6. cache semantics
 def test_template_cache_semantics_with_the_switch_on(dev, monkeypatch):
     from hdn_amd import heads as HD

@@ -172,6 +172,23 @@ def test_template_packable_refuses():
     assert ok(m)
 
 
+# What the parent of the heads' untangling answered, case by case (head_batch_cases.stage_case on conv_kernel, a [1, 256, 5, 5] template): the layout
+# predicate is shared with conv_search since, and its truth table did not move.  (A 17 x 17 map is inside the patch limit: 8 rows of 17 <= 224 pixels.)
+TEMPLATE_PACKABLE = {"reference": True, "hidden48": False, "cin128": False, "two_shapes": False, "five_levels": False, "side17": True, "side50": False,
+                     "bias": False, "stride2": False, "padding1": False, "dilation2": False, "groups2": False, "bn_training": False, "bn_not_affine": False,
+                     "bn_no_running_stats": False, "identity": False, "length4": False, "weight7e4": False}
+
+
+def test_template_packable_truth_table():
+    from hdn_amd import heads
+    assert list(TEMPLATE_PACKABLE) == HB.STAGE_CASES
+    got = {}
+    for name in HB.STAGE_CASES:
+        m, boxes, z = HB.stage_case(name, "conv_kernel")
+        got[name] = heads._template_packable(boxes, z, need_gpu=False)
+    assert got == TEMPLATE_PACKABLE
+
+
 # ----------------------------------------------------------------------------------------------------------------- the switch
 def _cpu_forward(monkeypatch, m, B=1):
     """fused_forward on CPU tensors with the correlation launch replaced by the oracle's (the only step of the module path without a CPU form)."""
@@ -190,7 +207,7 @@ def test_switch_is_off_by_default_and_the_wrapper_is_never_reached(monkeypatch):
     def boom(*a, **k):
         raise AssertionError("head_conv_batch reached with the switch off")
     monkeypatch.delenv("HDN_HIP_HEADS", raising=False)
-    monkeypatch.setattr(heads, "_HIP_HEADS", None)
+    monkeypatch.setattr(heads, "_HIP_HEADS_LEVEL", None)
     monkeypatch.setattr(heads, "head_conv_batch", boom)
     monkeypatch.setattr(heads, "_template_packable", lambda *a, **k: True)       # even where the predicate would say yes
     assert heads.hip_heads() is False
@@ -201,14 +218,14 @@ def test_switch_is_off_by_default_and_the_wrapper_is_never_reached(monkeypatch):
         assert getattr(m, "_hdn_template_pack", None) is None and getattr(m, "_hdn_search_pack", None) is None
     m = _head()
     m._hdn_hip_heads = False                                                     # the attribute overrides the environment, both ways
-    monkeypatch.setattr(heads, "_HIP_HEADS", True)
+    monkeypatch.setattr(heads, "_HIP_HEADS_LEVEL", True)
     _cpu_forward(monkeypatch, m)
 
 
 def test_switch_on_reaches_the_wrapper_and_refuses_cpu_tensors(monkeypatch):
     """The same forward with the switch on: the template branch goes to head_conv_batch, which has no CPU fallback."""
     from hdn_amd import heads, _lib
-    monkeypatch.setattr(heads, "_HIP_HEADS", False)
+    monkeypatch.setattr(heads, "_HIP_HEADS_LEVEL", False)
     monkeypatch.setattr(heads, "_template_packable", lambda *a, **k: True)
     monkeypatch.setattr(heads, "_pack_conv_search", lambda ws: torch.zeros(1))   # (the packer itself is host code; its stream is not looked at here)
     orig = heads._pack_convs
@@ -223,7 +240,7 @@ def test_switch_on_reaches_the_wrapper_and_refuses_cpu_tensors(monkeypatch):
     with pytest.raises(_lib.HdnHipError, match="no CPU fallback"):
         _cpu_forward(monkeypatch, m)
     monkeypatch.setenv("HDN_HIP_HEADS", "1")
-    monkeypatch.setattr(heads, "_HIP_HEADS", None)
+    monkeypatch.setattr(heads, "_HIP_HEADS_LEVEL", None)
     assert heads.hip_heads() is True
     monkeypatch.setenv("HDN_HIP_HEADS", "0")
     assert heads.hip_heads() is True                                             # read once

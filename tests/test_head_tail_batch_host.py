@@ -164,10 +164,35 @@ def test_attribute_overrides_the_level_and_hip_heads_is_unchanged(monkeypatch):
     # hip_heads(): a bool, true for every level above 0, read once, independent of the level's cache
     for text, on in (("", False), ("0", False), ("1", True), ("2", True)):
         monkeypatch.setenv("HDN_HIP_HEADS", text)
-        monkeypatch.setattr(heads, "_HIP_HEADS", None)
+        monkeypatch.setattr(heads, "_HIP_HEADS_LEVEL", None)
         assert heads.hip_heads() is on, text
     monkeypatch.setenv("HDN_HIP_HEADS", "0")
     assert heads.hip_heads() is True
+
+
+def test_one_switch_two_readings(monkeypatch):
+    """HDN_HIP_HEADS and head._hdn_hip_heads, each as (on, level), written out; on is level >= 1 everywhere."""
+    from hdn_amd import heads
+
+    def env(text):
+        monkeypatch.setenv("HDN_HIP_HEADS", text)
+        monkeypatch.setattr(heads, "_HIP_HEADS_LEVEL", None)
+        monkeypatch.setattr(heads, "_HIP_HEADS", None, raising=False)          # (a second cache, where a version of the module has one)
+        return heads.hip_heads(), heads.hip_heads_level()
+    for text, want in (("", (False, 0)), ("0", (False, 0)), ("1", (True, 1)), ("2", (True, 2)), (" 2 ", (True, 2)), ("yes", (True, 1)), ("3", (True, 1)),
+                       (" 0", (False, 0))):                                     # " 0": "0" after strip(), off in both readings
+        got = env(text)
+        assert got == want and got[0] is (got[1] >= 1), (text, got)
+
+    class Head:
+        pass
+    h = Head()
+    for text, unset in (("0", (False, 0)), ("2", (True, 2))):
+        env(text)
+        for v, want in ((None, unset), (False, (False, 0)), (0, (False, 0)), (True, (True, 1)), (1, (True, 1)), (2, (True, 2)), (3, (True, 1))):
+            h._hdn_hip_heads = v
+            got = heads._hip_heads_on(h), heads._hip_heads_level_of(h)
+            assert got == want and got[0] is (got[1] >= 1), (text, v, got)
 
 
 # ----------------------------------------------------------------------------------------------------------------- the predicate
