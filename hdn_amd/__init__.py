@@ -5,7 +5,7 @@ the reference's own Python signatures.  See DESIGN.md and INTEGRATION.md.
 """
 from .xcorr import xcorr_depthwise, xcorr_depthwise_backward, xcorr_depthwise_circular, xcorr_depthwise_multi, xcorr_fast, xcorr_slow  # noqa: F401
 from .homography import DLT_solve, transform, transformer, Homo_STN, dlt_warp, dlt_solve_backward, transformer_backward  # noqa: F401
-from .share_feature import PreShareFeature, fold_params  # noqa: F401
+from .share_feature import PreShareFeature, PreShareFeatureTrain, fold_params  # noqa: F401
 from .homo_model import HomoModelBuilder, track_proj  # noqa: F401
 from .logpolar import STN_Polar, STN_PolarTrain, logpolar_sample_backward  # noqa: F401
 from .heads import MultiBAN, MultiCircBAN  # noqa: F401

@@ -34,6 +34,10 @@ SIGNATURES = {
     "hdn_xcorr_bwd_form": (_i, [_i] * 5),
     "hdn_xcorr_fast_f32": (_i, [_c_float_p] * 3 + [_i] * 7 + [ctypes.c_void_p]),
     "hdn_share_feature_f32": (_i, [_c_float_p] * 3 + [_i] * 3 + [ctypes.c_void_p]),
+    "hdn_share_feature_train_workspace_bytes": (ctypes.c_longlong, [_i] * 3),
+    "hdn_share_feature_train_saved_bytes": (ctypes.c_longlong, [_i] * 3),
+    "hdn_share_feature_train_fwd_f32": (_i, [_c_float_p] * 7 + [ctypes.c_float] * 3 + [_i] + [_c_float_p] * 4 + [ctypes.c_longlong] + [_i] * 3 + [ctypes.c_void_p]),
+    "hdn_share_feature_bwd_f32": (_i, [_c_float_p] * 12 + [ctypes.c_longlong] + [_i] * 4 + [ctypes.c_void_p]),
     "hdn_dlt_solve_f32": (_i, [_c_float_p] * 3 + [_i, ctypes.c_void_p]),
     "hdn_warp_f32": (_i, [_c_float_p] * 3 + [_i] * 4 + [ctypes.c_void_p]),
     "hdn_warp_count_f32": (_i, [_c_float_p] * 4 + [_i] * 4 + [ctypes.c_void_p]),

@@ -23,7 +23,8 @@ attribute the reference resolves at call time:
 
 Training under install(train=True): every statement of the reference's training forwards that resolves to a drop-in is differentiable on the device -
 xcorr_depthwise{,_circular} (hdn_amd/xcorr.py), DLT_solve / transform / transformer (hdn_amd/homography.py) and, with train=True, STN_Polar
-(STN_PolarTrain, hdn_amd/logpolar.py; without train=True the STN_Polar drop-in raises on a grad-carrying input rather than detach).  The rebound head
+(STN_PolarTrain, hdn_amd/logpolar.py; without train=True the STN_Polar drop-in raises on a grad-carrying input rather than detach) and
+PreShareFeature (PreShareFeatureTrain, hdn_amd/share_feature.py: batch statistics and the backward on HIP, and an eval mode that carries the graph).  The rebound head
 forwards defer to the classes' own forward in .train() mode.  What still needs uninstall(): anything that calls the fused inference paths with
 autograd expected - the fused track_proj, dlt_warp, the fused heads in eval mode, xcorr_fast / xcorr_slow, xcorr_depthwise_multi (they detach).
 """
@@ -119,6 +120,10 @@ def _make_template_method(orig):
     return template
 
 
+# Does install(train=True) bind PreShareFeatureTrain at preprocess.head['PreShareFeature']?  Set by the outcome of tools/share_feature_train_bench.py
+# (profiles/share_feature_train.json): True only while the HIP path is faster than the stock nn.Sequential on the step's six calls at B = 32.
+SHARE_FEATURE_TRAIN_BOUND = True
+
 _MISSING = object()
 _saved = []  # (owner, attribute or dict key, original value, is_dict_item) in application order; undone by uninstall()
 
@@ -167,7 +172,8 @@ def install(strict: bool = False, modules: dict = None, tracker: bool = False, t
     real reference modules are imported.  trunk=True: the rebound ModelBuilder.track_proj attaches the BatchNorm-folded HIP trunk
     (hdn_amd.homo_model.optimize_trunk(self.hm_net, channels_last=True)) at its first eval-mode call with CUDA float32 weights, for users of the
     rebindings without the device tracker; off by default.  train=True: the two STN_Polar sites are bound to hdn_amd.logpolar.STN_PolarTrain (the same
-    module with differentiable=True), so that the reference's training forward runs on the drop-ins; everything else is unchanged.  Returns the list of (module, attribute) pairs that were rebound;
+    module with differentiable=True) and, while SHARE_FEATURE_TRAIN_BOUND, preprocess.head['PreShareFeature'] to hdn_amd.share_feature.PreShareFeatureTrain
+    (hip_train=True), so that the reference's training forward runs on the drop-ins; everything else is unchanged.  Returns the list of (module, attribute) pairs that were rebound;
     with strict=True a site that cannot be imported raises instead of being skipped.  uninstall() reverses it."""
     done = []
 
@@ -192,7 +198,8 @@ def install(strict: bool = False, modules: dict = None, tracker: bool = False, t
 
     pre = get(_DLT + ".preprocess")
     if pre is not None and isinstance(getattr(pre, "head", None), dict):
-        _rebind(pre.head, "PreShareFeature", share_feature.PreShareFeature, item=True)
+        sf = share_feature.PreShareFeatureTrain if train and SHARE_FEATURE_TRAIN_BOUND else share_feature.PreShareFeature
+        _rebind(pre.head, "PreShareFeature", sf, item=True)
         done.append((_DLT + ".preprocess", "head['PreShareFeature']"))
 
     # heads: keep the reference's classes (and their weights), swap the schedule of forward()

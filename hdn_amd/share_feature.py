@@ -3,6 +3,9 @@
 Reference: homo_estimator/Deep_homography/Oneline_DLTv1/preprocess/input_feature_extractor.py:3-29.
 The module keeps the reference's parameter names (ShareFeature.{0,1,3,4,6,7}.*) so snapshots load
 unchanged (hdn/utils/model_load.py:78, strict=False).
+
+Training (hip_train / PreShareFeatureTrain): the layered kernels of csrc/share_feature_train.hip - BatchNorm on the batch's statistics, forward and
+backward - behind one torch.autograd.Function; tools/share_feature_train_bench.py measures the step's six calls against the stock layers.
 """
 from __future__ import annotations
 
@@ -63,15 +66,118 @@ def share_feature(x: torch.Tensor, folded: torch.Tensor) -> torch.Tensor:
     return out
 
 
-class PreShareFeature(nn.Module):
-    """Same structure and parameter names as the reference module; eval-mode forward runs the HIP kernel.
+def _check_train_shapes(x, w1, w2, w3):
+    if x.dim() != 4 or x.shape[1] != 1:
+        raise ValueError(f"PreShareFeature expects [B,1,H,W], got {tuple(x.shape)}")
+    if tuple(w1.shape) != (4, 1, 3, 3) or tuple(w2.shape) != (8, 4, 3, 3) or tuple(w3.shape) != (1, 8, 3, 3):
+        raise ValueError("unexpected PreShareFeature conv shapes: %s %s %s" % (tuple(w1.shape), tuple(w2.shape), tuple(w3.shape)))
 
-    In training mode (batch statistics, autograd) the stock nn.Sequential runs on the device through
-    PyTorch-ROCm; training is outside this build's scope and is kept only so the module stays usable there.
+
+def share_feature_train_forward(x, w1, w2, w3, gamma, bias, eps=(BN_EPS,) * 3, mean_var=None):
+    """One call of hdn_share_feature_train_fwd_f32 (include/hdn_hip.h): x [B,1,H,W], the three conv weights in PyTorch's order, gamma / bias [13]
+    (the three BatchNorms' concatenated) -> (y, saved, stats).  mean_var None: batch statistics (stats_mode 0); else the [26] tensor
+    (mean[13], var[13]) to normalise with (stats_mode 1).  `saved` (13 pre-normalisation planes) and `stats` (mean, invstd, unbiased variance, 39
+    floats) are what share_feature_train_backward needs.  No autograd graph is recorded here."""
+    _check_train_shapes(x, w1, w2, w3)
+    tensors = (x, w1, w2, w3, gamma, bias) + (() if mean_var is None else (mean_var,))
+    dev = _lib.require_device(*tensors)
+    if gamma.numel() != 13 or bias.numel() != 13 or (mean_var is not None and mean_var.numel() != 26):
+        raise ValueError("gamma and bias hold 13 floats, mean_var 26")
+    xc, w1, w2, w3, gamma, bias = (t.detach().contiguous() for t in (x, w1, w2, w3, gamma, bias))
+    mv = None if mean_var is None else mean_var.detach().contiguous()
+    B, _, H, W = xc.shape
+    lib = _lib.load()
+    ws_bytes = lib.hdn_share_feature_train_workspace_bytes(B, H, W)
+    _lib.check(min(ws_bytes, 0), "PreShareFeature (train)")
+    out = torch.empty_like(xc)
+    saved = torch.empty((13 * xc.numel(),), dtype=torch.float32, device=dev)
+    stats = torch.empty((39,), dtype=torch.float32, device=dev)
+    ws = torch.empty((ws_bytes // 4,), dtype=torch.float32, device=dev)
+    with _lib.device_guard(dev):
+        rc = lib.hdn_share_feature_train_fwd_f32(_lib.ptr(xc), _lib.ptr(w1), _lib.ptr(w2), _lib.ptr(w3), _lib.ptr(gamma), _lib.ptr(bias),
+                                                 None if mv is None else _lib.ptr(mv), float(eps[0]), float(eps[1]), float(eps[2]),
+                                                 0 if mv is None else 1, _lib.ptr(out), _lib.ptr(saved), _lib.ptr(stats), _lib.ptr(ws), ws_bytes,
+                                                 B, H, W, _lib.stream_ptr(dev))
+    _lib.check(rc, "PreShareFeature (train)")
+    return out, saved, stats
+
+
+def share_feature_train_backward(x, w1, w2, w3, gamma, bias, saved, stats, grad_out, frozen: bool = False, need_x: bool = True, need_params: bool = True):
+    """(grad_x | None, grad_params | None) from one call of hdn_share_feature_bwd_f32; grad_params = [grad_w1 36, grad_w2 288, grad_w3 72,
+    grad_gamma 13, grad_bias 13].  A gradient that is not needed is neither computed nor allocated.  frozen: the forward ran with mean_var."""
+    if not (need_x or need_params):
+        raise ValueError("share_feature_train_backward: neither gradient is asked for")
+    _check_train_shapes(x, w1, w2, w3)
+    if grad_out.shape != x.shape:
+        raise ValueError(f"grad_out {tuple(grad_out.shape)} does not have the input's shape {tuple(x.shape)}")
+    dev = _lib.require_device(x, w1, w2, w3, gamma, bias, saved, stats, grad_out)
+    xc, w1, w2, w3, gamma, bias, gc = (t.detach().contiguous() for t in (x, w1, w2, w3, gamma, bias, grad_out))
+    B, _, H, W = xc.shape
+    if saved.numel() != 13 * xc.numel() or stats.numel() != 39:
+        raise ValueError("saved / stats are not this input's")
+    lib = _lib.load()
+    ws_bytes = lib.hdn_share_feature_train_workspace_bytes(B, H, W)
+    _lib.check(min(ws_bytes, 0), "PreShareFeature backward")
+    gx = torch.empty_like(xc) if need_x else None
+    gp = torch.empty((N_PARAMS,), dtype=torch.float32, device=dev) if need_params else None
+    ws = torch.empty((ws_bytes // 4,), dtype=torch.float32, device=dev)
+    with _lib.device_guard(dev):
+        rc = lib.hdn_share_feature_bwd_f32(_lib.ptr(xc), _lib.ptr(w1), _lib.ptr(w2), _lib.ptr(w3), _lib.ptr(gamma), _lib.ptr(bias), _lib.ptr(saved),
+                                           _lib.ptr(stats), _lib.ptr(gc), _lib.ptr(gx) if need_x else None, _lib.ptr(gp) if need_params else None,
+                                           _lib.ptr(ws), ws_bytes, 1 if frozen else 0, B, H, W, _lib.stream_ptr(dev))
+    _lib.check(rc, "PreShareFeature backward")
+    return gx, gp
+
+
+class _ShareFeatureTrain(torch.autograd.Function):
+    """The layered HIP forward with its backward: (x, w1, g1, b1, w2, g2, b2, w3, g3, b3) are the differentiable inputs; gamma / bias are the same
+    BatchNorm parameters concatenated for the kernel, mean_var None (batch statistics) or the running buffers concatenated (frozen statistics).
+    Returns (y, stats); stats (mean, invstd, unbiased variance) is non-differentiable."""
+
+    @staticmethod
+    def forward(ctx, x, w1, g1, b1, w2, g2, b2, w3, g3, b3, gamma, bias, mean_var, eps):
+        out, saved, stats = share_feature_train_forward(x, w1, w2, w3, gamma, bias, eps, mean_var)
+        ctx.save_for_backward(x, w1, w2, w3, gamma, bias, saved, stats)
+        ctx.frozen = mean_var is not None
+        ctx.mark_non_differentiable(stats)
+        return out, stats
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out, _grad_stats):
+        need = ctx.needs_input_grad
+        need_x, need_params = need[0], any(need[1:10])
+        if not (need_x or need_params):
+            return (None,) * 14
+        x, w1, w2, w3, gamma, bias, saved, stats = ctx.saved_tensors
+        gx, gp = share_feature_train_backward(x, w1, w2, w3, gamma, bias, saved, stats, grad_out, ctx.frozen, need_x, need_params)
+        grads = [gx] + [None] * 13
+        if need_params:
+            gw = (gp[0:36].view(4, 1, 3, 3), gp[36:324].view(8, 4, 3, 3), gp[324:396].view(1, 8, 3, 3))
+            for l, (lo, hi) in enumerate(((0, 4), (4, 12), (12, 13))):
+                per_layer = (gw[l], gp[396 + lo:396 + hi], gp[409 + lo:409 + hi])
+                for j in range(3):
+                    if need[1 + 3 * l + j]:
+                        grads[1 + 3 * l + j] = per_layer[j]
+        return tuple(grads)
+
+
+class PreShareFeature(nn.Module):
+    """Same structure and parameter names as the reference module; eval-mode forward runs the fused HIP kernel.
+
+    hip_train (a plain attribute, default False; PreShareFeatureTrain is the same module with it set): with it, a fp32 CUDA input runs the layered HIP
+    kernels of csrc/share_feature_train.hip wherever autograd or batch statistics are involved:
+      - train() mode with running buffers: batch statistics, the running buffers and num_batches_tracked updated as nn.BatchNorm2d updates them
+        (unbiased variance, each module's own momentum - None = cumulative average - and eps), differentiable to x and to all nine parameters;
+      - eval() mode while autograd is recording and x or a parameter requires grad: the running statistics, differentiable likewise (without
+        hip_train that call is the fused kernel, which detaches x).
+    Every other case - hip_train False, CPU tensors, other dtypes, eval without grad, fewer than two values per channel in train() mode - is the code
+    path of the default module: the stock nn.Sequential in train() mode, the fused hdn_share_feature_f32 launch in eval() mode.
     """
 
-    def __init__(self):
+    def __init__(self, hip_train: bool = False):
         super().__init__()
+        self.hip_train = bool(hip_train)
         self.ShareFeature = nn.Sequential(
             nn.Conv2d(1, 4, kernel_size=3, padding=1, bias=False), nn.BatchNorm2d(4), nn.ReLU(inplace=True),
             nn.Conv2d(4, 8, kernel_size=3, padding=1, bias=False), nn.BatchNorm2d(8), nn.ReLU(inplace=True),
@@ -115,7 +221,84 @@ class PreShareFeature(nn.Module):
         self.refresh()
         return super().train(mode)
 
+    def _packed(self, name, tensors):
+        """torch.cat of `tensors` (detached), rebuilt when one of them changed: gamma / bias / running statistics as the train kernels take them.
+        Six calls of a training step share one concatenation."""
+        key = tuple((id(t), t.data_ptr(), t._version) for t in tensors)
+        cache = self.__dict__.setdefault("_pack_cache", {})
+        hit = cache.get(name)
+        if hit is None or hit[0] != key:
+            with torch.no_grad():
+                hit = (key, torch.cat([t.detach().reshape(-1) for t in tensors]))
+            cache[name] = hit
+        return hit[1]
+
+    def _hip_train_mode(self, x):
+        """0: today's code path; 1: the layered kernels with batch statistics; 2: with the running statistics."""
+        if not getattr(self, "hip_train", False) or not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32:
+            return 0
+        if x.dim() != 4 or x.shape[1] != 1:
+            return 0
+        seq = self.ShareFeature
+        for c, b in _SLOTS:
+            bn, w = seq[b], seq[c].weight
+            if not bn.track_running_stats or bn.running_mean is None or bn.running_var is None or bn.weight is None or bn.bias is None:
+                return 0
+            if w.device != x.device or w.dtype != torch.float32 or bn.weight.dtype != torch.float32 or bn.running_mean.dtype != torch.float32:
+                return 0
+        if self.training:
+            return 1 if x.numel() >= 2 else 0
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in seq.parameters())):
+            return 2
+        return 0
+
+    def _forward_hip(self, x, frozen: bool):
+        seq = self.ShareFeature
+        convs, bns = [seq[c] for c, _ in _SLOTS], [seq[b] for _, b in _SLOTS]
+        gamma = self._packed("gamma", [bn.weight for bn in bns])
+        bias = self._packed("bias", [bn.bias for bn in bns])
+        mean_var = self._packed("mean_var", [bn.running_mean for bn in bns] + [bn.running_var for bn in bns]) if frozen else None
+        args = []
+        for conv, bn in zip(convs, bns):
+            args += [conv.weight, bn.weight, bn.bias]
+        y, stats = _ShareFeatureTrain.apply(x, *args, gamma, bias, mean_var, tuple(bn.eps for bn in bns))
+        if not frozen:
+            self._update_running(bns, stats)
+        return y
+
+    @staticmethod
+    @torch.no_grad()
+    def _update_running(bns, stats):
+        """nn.BatchNorm2d's bookkeeping: num_batches_tracked += 1, then running = (1 - m) running + m stat with the unbiased variance;
+        momentum None = the cumulative average 1 / num_batches_tracked."""
+        means, uvars = (stats[0:4], stats[4:12], stats[12:13]), (stats[26:30], stats[30:38], stats[38:39])
+        counters = [bn.num_batches_tracked for bn in bns if bn.num_batches_tracked is not None]
+        if counters:
+            torch._foreach_add_(counters, 1)
+        momenta = [bn.momentum for bn in bns]
+        if None not in momenta and momenta[0] == momenta[1] == momenta[2]:
+            m = float(momenta[0])
+            bufs = [bn.running_mean for bn in bns] + [bn.running_var for bn in bns]
+            torch._foreach_mul_(bufs, 1.0 - m)
+            torch._foreach_add_(bufs, list(means) + list(uvars), alpha=m)
+            return
+        for bn, mean, uvar in zip(bns, means, uvars):
+            m = 1.0 / float(bn.num_batches_tracked) if bn.momentum is None else float(bn.momentum)
+            bn.running_mean.mul_(1.0 - m).add_(mean, alpha=m)
+            bn.running_var.mul_(1.0 - m).add_(uvar, alpha=m)
+
     def forward(self, x):
+        mode = self._hip_train_mode(x)
+        if mode:
+            return self._forward_hip(x, frozen=mode == 2)
         if self.training:
             return self.ShareFeature(x)
         return share_feature(x, self.folded(x.device))
+
+
+class PreShareFeatureTrain(PreShareFeature):
+    """PreShareFeature(hip_train=True): what install(train=True) binds at preprocess.head['PreShareFeature'] when SHARE_FEATURE_TRAIN_BOUND
+    (hdn_amd/install.py) says the measurement favours it."""
+
+    def __init__(self):
+        super().__init__(hip_train=True)

@@ -147,6 +147,49 @@ int hdn_xcorr_fast_f32(const float* x, const float* k, float* out, int B, int C,
 int hdn_share_feature_f32(const float* img, const float* folded, float* out, int B, int H, int W, void* stream);
 
 /*
+ * PreShareFeature for training (csrc/share_feature_train.hip): the same chain with BatchNorm on this call's batch statistics, and its backward.
+ *   c1 = conv1(x), a1 = relu(bn1(c1)), c2 = conv2(a1), a2 = relu(bn2(c2)), c3 = conv3(a2), y = relu(bn3(c3))
+ * Per channel over the N = B H W values of a pre-normalisation plane c: mean, var (biased), invstd = 1 / sqrt(var + eps), then
+ *   alpha = gamma invstd,  beta = bias - mean alpha,  z = c alpha + beta,  a = relu(z),  x^ = (c - mean) invstd.
+ * Layout: img / out / grad_out / grad_img [B,1,H,W]; w1[4][1][3][3], w2[8][4][3][3], w3[1][8][3][3] in PyTorch's own order; gamma[13], bias[13]
+ * the three BatchNorms' weight / bias concatenated (4 + 8 + 1 channels); `saved` = c1 [B,4,H,W], c2 [B,8,H,W], c3 [B,1,H,W] one after the other
+ * (13 N floats, hdn_share_feature_train_saved_bytes); `stats` = mean[13], invstd[13], unbiased variance[13] (39 floats).  The activations are never
+ * stored: every consumer recomputes relu(c alpha + beta) on load, so forward and backward read the same ReLU masks.
+ *
+ * hdn_share_feature_train_fwd_f32.  stats_mode 0: batch statistics (N >= 2, else HDN_E_SHAPE); per layer one convolution launch that also writes
+ * per-workgroup partial sums of c and c^2, and a one-workgroup launch that adds them in a fixed order and writes the layer's stats; the sums are
+ * float64 from the first add on, var = sum c^2 / N - mean^2 in float64, unbiased = var N / (N - 1); mean, invstd, unbiased are rounded to fp32 once
+ * and alpha / beta are built from the rounded values.  stats_mode 1 (eval): mean_var_or_null = the caller's mean[13], var[13]; stats_out receives
+ * (mean, 1 / sqrt(var + eps), var) and nothing is reduced.  eps1 .. eps3: each BatchNorm's own eps.  mean_var_or_null is not read in mode 0.
+ *
+ * hdn_share_feature_bwd_f32: for grad_out = d loss / d y, with dz = g [z > 0] per layer from layer 3 down to layer 1 (g = grad_out, then grad_a):
+ *   S1 = sum dz = grad_bias,   S2 = sum dz x^ = grad_gamma                     (float64 partials, fixed order)
+ *   dc = alpha (dz - S1 / N - x^ S2 / N)   (stats_mode 0),   dc = alpha dz     (stats_mode 1: the statistics are constants)
+ *   grad_a[ci](p) = sum over co, k of w[co][ci][k] dc[co](p - k)               (a gather over 9 CO taps)
+ *   grad_w[co][ci][k] = sum over p of dc[co](p) a[ci](p + k)                   (fp32 in a workgroup, float64 across workgroups, fixed order)
+ * `stats` is the forward's stats_out, stats_mode the forward's.  grad_params_or_null = grad_w1[36], grad_w2[288], grad_w3[72], grad_gamma[13],
+ * grad_bias[13] (422 floats); grad_img_or_null = d loss / d img.  A NULL output is neither computed nor written (NULL grad_img skips layer 1's data
+ * adjoint, NULL grad_params every weight adjoint and, in mode 1, every S1 / S2 reduction); both NULL: HDN_E_SHAPE.
+ *
+ * No atomics anywhere: every output of both calls, grad_img included, is bit-reproducible between calls.  One launch form (a workgroup owns 1024
+ * consecutive pixels of one image), so there is no form query.  workspace: hdn_share_feature_train_workspace_bytes(B, H, W) bytes for either call,
+ * 16-byte aligned; the other pointers need only float alignment.  The two queries are host only; negative = HDN_E_*.
+ * Checked before the first HIP call: a NULL pointer (mean_var in mode 1 included) -> HDN_E_NULL; B, H or W <= 0, a stats_mode other than 0 / 1,
+ * N < 2 in mode 0, no gradient asked for -> HDN_E_SHAPE; 13 N > 2^31 - 1, a workspace that is unaligned or too small -> HDN_E_LIMIT; the byte
+ * range of an output (the workspace included) overlapping an input's or another output's -> HDN_E_ALIAS.  Asynchronous on `stream`, allocates nothing.
+ * Differentiates PreShareFeature.forward in train() mode, .../Oneline_DLTv1/preprocess/input_feature_extractor.py:27-29 (six calls per training
+ * step: model_builder_e2e_unconstrained_v2.py:420-427, homo_model_builder.py:154-171).
+ */
+long long hdn_share_feature_train_workspace_bytes(int B, int H, int W);
+long long hdn_share_feature_train_saved_bytes(int B, int H, int W);
+int hdn_share_feature_train_fwd_f32(const float* img, const float* w1, const float* w2, const float* w3, const float* gamma, const float* bias,
+                                    const float* mean_var_or_null, float eps1, float eps2, float eps3, int stats_mode, float* out, float* saved,
+                                    float* stats_out, float* workspace, long long workspace_bytes, int B, int H, int W, void* stream);
+int hdn_share_feature_bwd_f32(const float* img, const float* w1, const float* w2, const float* w3, const float* gamma, const float* bias,
+                              const float* saved, const float* stats, const float* grad_out, float* grad_img_or_null, float* grad_params_or_null,
+                              float* workspace, long long workspace_bytes, int stats_mode, int B, int H, int W, void* stream);
+
+/*
  * 4-point DLT: H (3x3, H[2][2] = 1) with H * src_i ~ src_i + off_i.
  *   src[B,8], off[B,8] = (x,y) of 4 points in the caller's order (the reference's internal
  *   reordering, utils.py:18-26, does not change the solution); H_out[B,9] row-major.
