@@ -250,3 +250,27 @@ def device_guard(device: torch.device):
 
 def ptr(t: torch.Tensor) -> ctypes.c_void_p:
     return ctypes.c_void_p(t.data_ptr())
+
+
+def opt(t):
+    """The device pointer of an optional tensor (NULL for None)."""
+    return ptr(t) if t is not None else None
+
+
+def ptr_array(tensors):
+    """The data pointers of `tensors` as the `const float* const*` of the C side (the caller keeps the tensors alive until the call is made)."""
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def workspace(what, nbytes, dev):
+    """(workspace or None, its size in bytes) for what a hdn_*_workspace_bytes query answered (a negative answer is its error code)."""
+    if nbytes < 0:
+        check(int(nbytes), what)
+    return (torch.empty(nbytes // 4, dtype=torch.float32, device=dev) if nbytes else None), nbytes   # (from torch's caching allocator: no sync, graph-safe)
+
+
+def launch(what, dev, fn, *args):
+    """fn(*args, stream) on `dev`'s current stream; a non-zero return code raises (check)."""
+    with device_guard(dev):
+        rc = fn(*args, stream_ptr(dev))
+    check(rc, what)

@@ -550,7 +550,7 @@ template <class Cf>
 static int k_slices(int B) {
   const long long M = (long long)B * Cf::S * Cf::S;
   const long long tiles = ((M + Cf::BM - 1) / Cf::BM) * Cf::NB;
-  static const int target = [] { const char* e = getenv("HDN_CV_SLICE_TARGET"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 200; }();  // A/B switch
+  static const int target = env_positive("HDN_CV_SLICE_TARGET", 200);  // A/B switch
   int z = 1;
   while (tiles * z < target && z * 2 <= Cf::NCHUNK && Cf::NCHUNK % (z * 2) == 0) z *= 2;
   return z;
@@ -579,15 +579,7 @@ static int launch(const float* x, const void* wp, const float* bias, const float
     if (ws_bytes < workspace_bytes<Cf>(B) || !aligned16(ws)) return HDN_E_LIMIT;
   }
   static PerDeviceOnce attr;
-  const int dev_ = PerDeviceOnce::device();
-  if (!attr.done(dev_)) {
-    for (const void* fn : {reinterpret_cast<const void*>(&conv3x3_kernel<Cf, 0, false, SD>), reinterpret_cast<const void*>(&conv3x3_kernel<Cf, 1, false, SD>),
-                           reinterpret_cast<const void*>(&conv3x3_kernel<Cf, 2, false, SD>)}) {
-      hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, Cf::LDS_BYTES);
-      if (e != hipSuccess) return -(1000 + (int)e);
-    }
-    attr.set(dev_);
-  }
+  if (const int rc = lds_opt_in(attr, Cf::LDS_BYTES, &conv3x3_kernel<Cf, 0, false, SD>, &conv3x3_kernel<Cf, 1, false, SD>, &conv3x3_kernel<Cf, 2, false, SD>)) return rc;
   const dim3 grid((unsigned)((M + Cf::BM - 1) / Cf::BM), Cf::NB, z), blk(2 * HDN_BLOCK);
   const u32x4* w4 = (const u32x4*)wp;
   if (z == 1) {
@@ -615,14 +607,7 @@ static int launch_chain(const float* x, const LazyIn& lz, const void* wp, float*
   const int z = k_slices_chain<Cf>(B);
   if (lz.zx > 0 && Cf::NCHUNK / z > 2) return HDN_E_LIMIT;   // (cannot happen: k_slices_chain; the LAZY staging fills two A images)
   static PerDeviceOnce attr;
-  const int dev_ = PerDeviceOnce::device();
-  if (!attr.done(dev_)) {
-    for (const void* fn : {reinterpret_cast<const void*>(&conv3x3_kernel<Cf, 2, false, SD>), reinterpret_cast<const void*>(&conv3x3_kernel<Cf, 2, true, SD>)}) {
-      hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, Cf::LDS_BYTES);
-      if (e != hipSuccess) return -(1000 + (int)e);
-    }
-    attr.set(dev_);
-  }
+  if (const int rc = lds_opt_in(attr, Cf::LDS_BYTES, &conv3x3_kernel<Cf, 2, false, SD>, &conv3x3_kernel<Cf, 2, true, SD>)) return rc;
   const dim3 grid((unsigned)((M + Cf::BM - 1) / Cf::BM), Cf::NB, z), blk(2 * HDN_BLOCK);
   const u32x4* w4 = (const u32x4*)wp;
   if (lz.zx > 0) hipLaunchKernelGGL((conv3x3_kernel<Cf, 2, true, SD>), grid, blk, Cf::LDS_BYTES, stream, x, w4, nullptr, nullptr, out, out2, B, Cf::NCHUNK / z, lz);
@@ -946,7 +931,7 @@ static int k_slices_v2(int B) {
   const long long M = (long long)B * Cf::S * Cf::S;
   if (Cf::TPW > 1) return 1;       // (several tiles per workgroup: the launch is long enough as it is)
   const long long tiles = ((M + Cf::BM - 1) / Cf::BM) * Cf::NB;
-  static const int target = [] { const char* e = getenv("HDN_CV2_SLICE_TARGET"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 200; }();  // A/B switch
+  static const int target = env_positive("HDN_CV2_SLICE_TARGET", 200);  // A/B switch
   int z = 1;
   while (tiles * z < target && (Cf::NCHUNK / (z * 2)) % Cf::PER == 0 && Cf::NCHUNK % (z * 2) == 0 && z * 2 <= Cf::NCHUNK) z *= 2;
   return z;
@@ -962,15 +947,7 @@ static int launch_v2(const float* x, const void* wp, const float* bias, const fl
     if (ws_bytes < (size_t)z * M * Cf::C * sizeof(float) || !aligned16(ws)) return HDN_E_LIMIT;
   }
   static PerDeviceOnce attr;
-  const int dev_ = PerDeviceOnce::device();
-  if (!attr.done(dev_)) {
-    for (const void* fn : {reinterpret_cast<const void*>(&conv3x3_v2_kernel<Cf, 0, SD>), reinterpret_cast<const void*>(&conv3x3_v2_kernel<Cf, 1, SD>),
-                           reinterpret_cast<const void*>(&conv3x3_v2_kernel<Cf, 2, SD>)}) {
-      hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, Cf::LDS_BYTES);
-      if (e != hipSuccess) return -(1000 + (int)e);
-    }
-    attr.set(dev_);
-  }
+  if (const int rc = lds_opt_in(attr, Cf::LDS_BYTES, &conv3x3_v2_kernel<Cf, 0, SD>, &conv3x3_v2_kernel<Cf, 1, SD>, &conv3x3_v2_kernel<Cf, 2, SD>)) return rc;
   const long long wgs_m = ((M + Cf::BM - 1) / Cf::BM + Cf::TPW - 1) / Cf::TPW;
   if (wgs_m > 65535) return HDN_E_LIMIT;
   const dim3 grid(Cf::NB, (unsigned)wgs_m, z), blk(2 * HDN_BLOCK);

@@ -299,12 +299,7 @@ template <class Cf, bool SD = false>
 static int launch(const float* x, const void* wp, const float* bias, float* out, float* out_ds, int B, hipStream_t stream) {
   const long long M = (long long)B * Cf::SO * Cf::SO;
   static PerDeviceOnce attr;
-  const int dev_ = PerDeviceOnce::device();
-  if (!attr.done(dev_)) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3s2_v2_kernel<Cf, SD>), hipFuncAttributeMaxDynamicSharedMemorySize, Cf::LDS_BYTES);
-    if (e != hipSuccess) return -(1000 + (int)e);
-    attr.set(dev_);
-  }
+  if (const int rc = lds_opt_in(attr, Cf::LDS_BYTES, &conv3x3s2_v2_kernel<Cf, SD>)) return rc;
   if ((M + Cf::BM - 1) / Cf::BM > 65535) return HDN_E_LIMIT;      // grid.y (as launch_v2 of conv3x3.hip)
   const dim3 grid(Cf::NB, (unsigned)((M + Cf::BM - 1) / Cf::BM)), blk(2 * HDN_BLOCK);
   hipLaunchKernelGGL((conv3x3s2_v2_kernel<Cf, SD>), grid, blk, Cf::LDS_BYTES, stream, x, static_cast<const u32x4*>(wp), bias, out, out_ds, B);

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include <atomic>
 
@@ -41,9 +42,26 @@ int check_fp16_range(const float* x, long long n, hipStream_t stream, int act_do
 // bias may be NULL; n and C multiples of 4, everything 16-byte aligned.  The finish pass of the K-split forms of conv3x3s2.hip and conv3x3d.hip.
 int finish_slices(const float* ws, int Z, const float* bias, int relu, float* out, long long n, int C, hipStream_t stream);
 
-inline int launch_status() {
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? HDN_OK : -(1000 + (int)e);
+inline int hip_status(hipError_t e) { return e == hipSuccess ? HDN_OK : -(1000 + (int)e); }
+inline int launch_status() { return hip_status(hipGetLastError()); }
+
+// Dynamic LDS above 64 KiB needs an opt-in once per kernel and device: raises the limit of every kernel named to `bytes`, in argument order,
+// unless `once` (a function-local static of the caller: one per template instantiation) says this device has been through it.
+template <class... Kernels>
+inline int lds_opt_in(PerDeviceOnce& once, int bytes, Kernels... kernels) {
+  const int d = PerDeviceOnce::device();
+  if (once.done(d)) return HDN_OK;
+  for (const void* fn : {reinterpret_cast<const void*>(kernels)...})
+    if (const int rc = hip_status(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))) return rc;
+  once.set(d);
+  return HDN_OK;
+}
+
+// An integer switch of the environment: its value when it is set and positive, `fallback` otherwise.
+inline int env_positive(const char* name, int fallback) {
+  const char* e = getenv(name);
+  const int v = e ? atoi(e) : 0;
+  return v > 0 ? v : fallback;
 }
 
 // Copy n floats global -> LDS, linear image.  16-byte path when the source is aligned

@@ -246,12 +246,7 @@ extern "C" int hdn_head_conv3x3_f32(const float* const* xs, const void* w_packed
     if (const int rr = hdn::check_fp16_range(xs[i], (long long)hdn::hc::CI * Hi * Wi, static_cast<hipStream_t>(stream))) return rr;
   }
   static hdn::PerDeviceOnce attr;
-  const int dev_ = hdn::PerDeviceOnce::device();
-  if (!attr.done(dev_)) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hdn::hc::head_conv_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, hdn::hc::LDS_BYTES);
-    if (e != hipSuccess) return -(1000 + (int)e);
-    attr.set(dev_);
-  }
+  if (const int rc = hdn::lds_opt_in(attr, hdn::hc::LDS_BYTES, &hdn::hc::head_conv_kernel<false>)) return rc;
   const long long sc = nhwc ? 1 : (long long)Hi * Wi, sy = nhwc ? (long long)Wi * hdn::hc::CI : Wi, sx = nhwc ? hdn::hc::CI : 1;
   const dim3 grid((Ho * Wo + hdn::hc::TILE_N - 1) / hdn::hc::TILE_N, CO / hdn::hc::TILE_M, n);
   hipLaunchKernelGGL(hdn::hc::head_conv_kernel<false>, grid, dim3(512), hdn::hc::LDS_BYTES, static_cast<hipStream_t>(stream), P,
@@ -294,12 +289,7 @@ extern "C" int hdn_head_conv3x3_batch_f32(const float* const* xs, const void* w_
     }
   }
   static hdn::PerDeviceOnce attr;
-  const int dev_ = hdn::PerDeviceOnce::device();
-  if (!attr.done(dev_)) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hdn::hc::head_conv_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, hdn::hc::LDS_BYTES);
-    if (e != hipSuccess) return -(1000 + (int)e);
-    attr.set(dev_);
-  }
+  if (const int rc = hdn::lds_opt_in(attr, hdn::hc::LDS_BYTES, &hdn::hc::head_conv_kernel<true>)) return rc;
   const long long sc = nhwc ? 1 : (long long)Hi * Wi, sy = nhwc ? (long long)Wi * hdn::hc::CI : Wi, sx = nhwc ? hdn::hc::CI : 1;
   const dim3 grid((Ho * Wo + hdn::hc::TILE_N - 1) / hdn::hc::TILE_N, CO / hdn::hc::TILE_M, n * B);
   hipLaunchKernelGGL(hdn::hc::head_conv_kernel<true>, grid, dim3(512), hdn::hc::LDS_BYTES, s, P, static_cast<const hdn::hc::u32x4*>(w_packed), bias, CO, Hi,

@@ -225,12 +225,7 @@ static int launch(const float* feats, const void* w1p, const float* b1, const fl
   const size_t lds = lds_bytes<H>(N, om);
   if (lds > LDS_LIMIT) return HDN_E_LIMIT;
   static PerDeviceOnce attr;
-  const int dev_ = PerDeviceOnce::device();
-  if (!attr.done(dev_)) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&head_tail_kernel<H, N, BATCH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT);
-    if (e != hipSuccess) return -(1000 + (int)e);
-    attr.set(dev_);
-  }
+  if (const int rc = lds_opt_in(attr, (int)LDS_LIMIT, &head_tail_kernel<H, N, BATCH>)) return rc;
   hipLaunchKernelGGL((head_tail_kernel<H, N, BATCH>), dim3((P + TILE - 1) / TILE, 2, B), dim3(2 * H), lds, s, feats, static_cast<const u32x4*>(w1p), b1, wf, bf,
                      out, P, om, B, oc, ol);
   return launch_status();

@@ -180,12 +180,7 @@ extern "C" int hdn_simi_stem_f32(const float* x, const void* wpacked, const floa
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (const int rc = hdn::check_fp16_range(x, nx, st)) return rc;
   static hdn::PerDeviceOnce attr;
-  const int dev_ = hdn::PerDeviceOnce::device();
-  if (!attr.done(dev_)) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&simi_stem_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    if (e != hipSuccess) return -(1000 + (int)e);
-    attr.set(dev_);
-  }
+  if (const int rc = hdn::lds_opt_in(attr, LDS_BYTES, &simi_stem_kernel)) return rc;
   hipLaunchKernelGGL(simi_stem_kernel, dim3((unsigned)(2 * B * Sp)), dim3(THREADS), LDS_BYTES, st, x, static_cast<const u32x4*>(wpacked), bias, out, S, Sc,
                      Sp);
   return hdn::launch_status();

@@ -190,13 +190,7 @@ template <int ROWS, int STREAMS, bool OUT_SD = false>
 int launch(const float* x, const void* wfrag, const float* bias, float* out, int B, hipStream_t stream) {
   using G = Geo<ROWS, STREAMS>;
   static PerDeviceOnce attr;
-  const int dev_ = PerDeviceOnce::device();
-  if (!attr.done(dev_)) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&trunk_stem_mfma_kernel<ROWS, STREAMS, OUT_SD>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       G::LDS_BYTES);
-    if (e != hipSuccess) return -(1000 + (int)e);
-    attr.set(dev_);
-  }
+  if (const int rc = lds_opt_in(attr, G::LDS_BYTES, &trunk_stem_mfma_kernel<ROWS, STREAMS, OUT_SD>)) return rc;
   hipLaunchKernelGGL((trunk_stem_mfma_kernel<ROWS, STREAMS, OUT_SD>), dim3((unsigned)B * G::NBLK), dim3(G::THREADS), G::LDS_BYTES, stream, x,
                      static_cast<const u32x4*>(wfrag), bias, out);
   return launch_status();

@@ -890,16 +890,10 @@ static int north_variant() {
 static int launch_north(const XcorrPtrs& P, int n, int planes, hipStream_t stream) {
   void (*kern)(XcorrPtrs, int) = &xcorr_north_kernel<1>;   // exact-zero taps skipped
   static PerDeviceOnce attr;  // dynamic LDS above 64 KiB needs the opt-in once per kernel and device
-  const int dev_ = PerDeviceOnce::device();
-  if (!attr.done(dev_)) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)north::LDS_BYTES);
-    if (e != hipSuccess) return -(1000 + (int)e);
-    attr.set(dev_);
-  }
+  if (const int rc = lds_opt_in(attr, (int)north::LDS_BYTES, kern)) return rc;
   // persistent: 2 workgroups per CU x 256 CUs (fewer if there are fewer planes); n problems share the grid.
   // HDN_NORTH_BLOCKS caps the grid (e.g. 256 = one workgroup per CU, leaving LDS for kernels on other streams).
-  static const int cap = [] { const char* e = getenv("HDN_NORTH_BLOCKS"); int v = e ? atoi(e) : 0; return v > 0 ? v : 512; }();
+  static const int cap = env_positive("HDN_NORTH_BLOCKS", 512);
   const int per_problem = max(1, min(cdiv(planes, 4), cap / n));
   hipLaunchKernelGGL(kern, dim3(per_problem, n), dim3(HDN_BLOCK), north::LDS_BYTES, stream, P, planes);
   g_last_variant = "north_61x61_31x31";
@@ -961,7 +955,7 @@ static int xcorr_dispatch_(const XcorrPtrs& P, int n, int circular, int B, int C
       // (hdn_xcorr_north_variant / HDN_NORTH=direct) the packed-FMA direct sum with zero-tap skipping (~250 us on post-ReLU data).
       const int v = north_variant();
       if (v == HDN_NORTH_FFT_COL) {  // column-first FFT kernel: no alignment requirement
-        static const int cap = [] { const char* e = getenv("HDN_NORTH_BLOCKS"); int c = e ? atoi(e) : 0; return c > 0 ? c : 1024; }();
+        static const int cap = env_positive("HDN_NORTH_BLOCKS", 1024);
         for (int i = 0; i < n; ++i) {
           const int rc = launch_north_fft4(P.x[i], P.k[i], P.out[i], planes, cap, stream);
           if (rc != HDN_OK) return rc;

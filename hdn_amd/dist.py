@@ -71,9 +71,7 @@ class RcclComm:
             raise _lib.HdnHipError("communicator destroyed")
         loc = local.detach().contiguous()
         out = torch.empty((self.world * loc.shape[0], 8), dtype=torch.float32, device=dev)
-        with _lib.device_guard(dev):
-            rc = _lib.load().hdn_allgather_offsets(_lib.ptr(loc), _lib.ptr(out), loc.shape[0], self._h, _lib.stream_ptr(dev))
-        _lib.check(rc, "hdn_allgather_offsets")
+        _lib.launch("hdn_allgather_offsets", dev, _lib.load().hdn_allgather_offsets, _lib.ptr(loc), _lib.ptr(out), loc.shape[0], self._h)
         return out
 
     def comm_count(self) -> int:
@@ -228,9 +226,7 @@ class OneShotGather:
         self.check_status()            # (of the calls before this one: a host read of pinned memory, no synchronisation)
         loc = local.detach().to(torch.float32).contiguous()
         out = torch.empty((self.world * loc.shape[0], 8), dtype=torch.float32, device=dev)
-        with _lib.device_guard(dev):
-            rc = _lib.load().hdn_gather_offsets_oneshot(self._h, _lib.ptr(loc), _lib.ptr(out), loc.shape[0], _lib.stream_ptr(dev))
-        _lib.check(rc, "hdn_gather_offsets_oneshot")
+        _lib.launch("hdn_gather_offsets_oneshot", dev, _lib.load().hdn_gather_offsets_oneshot, self._h, _lib.ptr(loc), _lib.ptr(out), loc.shape[0])
         return out
 
     def status(self) -> int:

@@ -227,10 +227,8 @@ def _subwindow(frame, pos, model_sz, original_sz, avg_chans, mode, params=None):
         B, C, dev, m = frame.n, frame.C, frame.device, int(model_sz)
         keep, pp, stride = _records(params, B, 3 + C, "params")
         out = torch.empty((B, 1 if mode else C, m, m), dtype=torch.float32, device=dev)
-        with _lib.device_guard(dev):
-            rc = _lib.load().hdn_subwindow_ragged_f32(_lib.ptr(frame.data), frame.slot_stride, _lib.ptr(frame.dims), pp, stride, _lib.ptr(out), B,
-                                                      frame.Hmax, frame.Wmax, C, m, mode, _lib.stream_ptr(dev))
-        _lib.check(rc, "get_subwindow")
+        _lib.launch("get_subwindow", dev, _lib.load().hdn_subwindow_ragged_f32, _lib.ptr(frame.data), frame.slot_stride, _lib.ptr(frame.dims), pp, stride,
+                    _lib.ptr(out), B, frame.Hmax, frame.Wmax, C, m, mode)
         return out
     H, W, C = _check_frame(frame)
     dev = frame.device
@@ -244,9 +242,7 @@ def _subwindow(frame, pos, model_sz, original_sz, avg_chans, mode, params=None):
     keep, pp, stride = _records(params, B, 3 + C, "params")
     m = int(model_sz)
     out = torch.empty((B, 1 if mode else C, m, m), dtype=torch.float32, device=dev)
-    with _lib.device_guard(dev):
-        rc = _lib.load().hdn_subwindow_batch_f32(_lib.ptr(frame), pp, stride, _lib.ptr(out), B, H, W, C, m, mode, _lib.stream_ptr(dev))
-    _lib.check(rc, "get_subwindow")
+    _lib.launch("get_subwindow", dev, _lib.load().hdn_subwindow_batch_f32, _lib.ptr(frame), pp, stride, _lib.ptr(out), B, H, W, C, m, mode)
     return out
 
 
@@ -296,9 +292,7 @@ def get_polar_img(patch: torch.Tensor, original=None) -> torch.Tensor:
     mx, my = _polar_maps[key]
     src = patch.detach().contiguous()
     out = torch.empty_like(src)
-    with _lib.device_guard(dev):
-        rc = _lib.load().hdn_remap_linear_f32(_lib.ptr(src), _lib.ptr(mx), _lib.ptr(my), _lib.ptr(out), C, H, W, H, W, _lib.stream_ptr(dev))
-    _lib.check(rc, "get_polar_img")
+    _lib.launch("get_polar_img", dev, _lib.load().hdn_remap_linear_f32, _lib.ptr(src), _lib.ptr(mx), _lib.ptr(my), _lib.ptr(out), C, H, W, H, W)
     return out
 
 
@@ -336,10 +330,8 @@ def _warp_ragged(frame, M, width, what, entry, name, out):
     _arena_on_gpu(frame)
     B, keep, mp, stride = _matrices(frame, M, width, what)
     out = _arena_out(frame, out)
-    with _lib.device_guard(frame.device):
-        rc = getattr(_lib.load(), entry)(_lib.ptr(frame.data), frame.slot_stride, _lib.ptr(frame.dims), mp, stride, _lib.ptr(out.data), B,
-                                         frame.Hmax, frame.Wmax, frame.C, _lib.stream_ptr(frame.device))
-    _lib.check(rc, name)
+    _lib.launch(name, frame.device, getattr(_lib.load(), entry), _lib.ptr(frame.data), frame.slot_stride, _lib.ptr(frame.dims), mp, stride, _lib.ptr(out.data),
+                B, frame.Hmax, frame.Wmax, frame.C)
     return out
 
 
@@ -354,9 +346,7 @@ def warp_perspective(frame, M, out=None):
     H, W, C = _check_frame(frame)
     B, keep, mp, stride = _matrices(frame, M, 9, "3x3")
     out = torch.empty_like(frame)
-    with _lib.device_guard(frame.device):
-        rc = _lib.load().hdn_frame_warp_perspective_batch_u8(_lib.ptr(frame), mp, stride, _lib.ptr(out), B, H, W, C, _lib.stream_ptr(frame.device))
-    _lib.check(rc, "warp_perspective")
+    _lib.launch("warp_perspective", frame.device, _lib.load().hdn_frame_warp_perspective_batch_u8, _lib.ptr(frame), mp, stride, _lib.ptr(out), B, H, W, C)
     return out
 
 
@@ -369,9 +359,7 @@ def warp_affine_cubic(frame, M, out=None):
     H, W, C = _check_frame(frame)
     B, keep, mp, stride = _matrices(frame, M, 6, "2x3")
     out = torch.empty_like(frame)
-    with _lib.device_guard(frame.device):
-        rc = _lib.load().hdn_frame_warp_affine_cubic_batch_u8(_lib.ptr(frame), mp, stride, _lib.ptr(out), B, H, W, C, _lib.stream_ptr(frame.device))
-    _lib.check(rc, "warp_affine_cubic")
+    _lib.launch("warp_affine_cubic", frame.device, _lib.load().hdn_frame_warp_affine_cubic_batch_u8, _lib.ptr(frame), mp, stride, _lib.ptr(out), B, H, W, C)
     return out
 
 

@@ -28,10 +28,8 @@ def avgpool_fc(x, fc, in_domain=0):
         x, nhwc = x.contiguous(), 0
     w = fc.weight.detach().contiguous()
     out = torch.empty((B, w.shape[0]), dtype=torch.float32, device=dev)
-    with _lib.device_guard(dev):
-        rc = _lib.load().hdn_avgpool_fc_f32(_lib.ptr(x), _lib.ptr(w), _lib.ptr(fc.bias.detach()) if fc.bias is not None else None, _lib.ptr(out),
-                                            B, C, H * W, w.shape[0], nhwc, int(in_domain), _lib.stream_ptr(dev))
-    _lib.check(rc, "avgpool_fc")
+    _lib.launch("avgpool_fc", dev, _lib.load().hdn_avgpool_fc_f32, _lib.ptr(x), _lib.ptr(w), _lib.opt(fc.bias), _lib.ptr(out),
+                B, C, H * W, w.shape[0], nhwc, int(in_domain))
     return out
 
 

@@ -30,9 +30,7 @@ def _dlt_solve(src_p: torch.Tensor, off_set: torch.Tensor) -> torch.Tensor:
     if B == 0:
         raise ValueError("empty batch")
     H = torch.empty((B, 9), dtype=torch.float32, device=dev)
-    with _lib.device_guard(dev):
-        rc = _lib.load().hdn_dlt_solve_f32(_lib.ptr(s), _lib.ptr(o), _lib.ptr(H), B, _lib.stream_ptr(dev))
-    _lib.check(rc, "DLT_solve")
+    _lib.launch("DLT_solve", dev, _lib.load().hdn_dlt_solve_f32, _lib.ptr(s), _lib.ptr(o), _lib.ptr(H), B)
     return H
 
 
@@ -51,10 +49,7 @@ def dlt_solve_backward(src_p: torch.Tensor, off_set: torch.Tensor, grad_H: torch
     s, o, g = src_p.detach().contiguous(), off_set.detach().contiguous(), grad_H.detach().reshape(B, 9).contiguous()
     gs = torch.empty_like(s) if need_src else None
     go = torch.empty_like(o) if need_off else None
-    with _lib.device_guard(dev):
-        rc = _lib.load().hdn_dlt_solve_bwd_f32(_lib.ptr(s), _lib.ptr(o), _lib.ptr(g), _lib.ptr(gs) if need_src else None,
-                                               _lib.ptr(go) if need_off else None, B, _lib.stream_ptr(dev))
-    _lib.check(rc, "dlt_solve_backward")
+    _lib.launch("dlt_solve_backward", dev, _lib.load().hdn_dlt_solve_bwd_f32, _lib.ptr(s), _lib.ptr(o), _lib.ptr(g), _lib.opt(gs), _lib.opt(go), B)
     return gs, go
 
 
@@ -100,10 +95,7 @@ def _warp(img: torch.Tensor, th: torch.Tensor, want_condition: bool):
     img, th = img.detach().contiguous(), th.detach().contiguous()
     out = torch.empty((B, H, W, C), dtype=torch.float32, device=dev)
     count = torch.empty((1,), dtype=torch.int32, device=dev) if want_condition else None  # zeroed by the call
-    with _lib.device_guard(dev):
-        rc = _lib.load().hdn_warp_count_f32(_lib.ptr(img), _lib.ptr(th), _lib.ptr(out),
-                                            _lib.ptr(count) if want_condition else None, B, C, H, W, _lib.stream_ptr(dev))
-    _lib.check(rc, "transformer")
+    _lib.launch("transformer", dev, _lib.load().hdn_warp_count_f32, _lib.ptr(img), _lib.ptr(th), _lib.ptr(out), _lib.opt(count), B, C, H, W)
     return out, (count[0].to(torch.float32) if want_condition else None)
 
 
@@ -124,18 +116,12 @@ def transformer_backward(U: torch.Tensor, theta: torch.Tensor, grad_out: torch.T
     img, th, g = U.detach().contiguous(), theta.detach().reshape(B, 9).contiguous(), grad_out.detach().contiguous()
     lib = _lib.load()
     gU = torch.empty_like(img) if need_U else None          # zero-filled by the call
-    gth = ws = None
-    ws_bytes = 0
+    gth, ws, ws_bytes = None, None, 0
     if need_theta:
         gth = torch.empty((B, 9), dtype=torch.float32, device=dev)
-        ws_bytes = lib.hdn_warp_bwd_workspace_bytes(B, H, W)
-        _lib.check(min(ws_bytes, 0), "transformer_backward")
-        ws = torch.empty((ws_bytes // 4,), dtype=torch.float32, device=dev)
-    with _lib.device_guard(dev):
-        rc = lib.hdn_warp_bwd_f32(_lib.ptr(img), _lib.ptr(th), _lib.ptr(g), _lib.ptr(gth) if need_theta else None,
-                                  _lib.ptr(gU) if need_U else None, _lib.ptr(ws) if need_theta else None, ws_bytes, B, C, H, W,
-                                  _lib.stream_ptr(dev))
-    _lib.check(rc, "transformer_backward")
+        ws, ws_bytes = _lib.workspace("transformer_backward", lib.hdn_warp_bwd_workspace_bytes(B, H, W), dev)
+    _lib.launch("transformer_backward", dev, lib.hdn_warp_bwd_f32, _lib.ptr(img), _lib.ptr(th), _lib.ptr(g), _lib.opt(gth), _lib.opt(gU), _lib.opt(ws),
+                ws_bytes, B, C, H, W)
     return gU, gth
 
 
@@ -228,10 +214,8 @@ def dlt_warp(h4p: torch.Tensor, off_set: torch.Tensor, img: torch.Tensor):
     bstride = im.stride(0) if B > 1 else H * W
     Hm = torch.empty((B, 9), dtype=torch.float32, device=dev)
     warped = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
-    with _lib.device_guard(dev):
-        rc = _lib.load().hdn_dlt_warp_strided_f32(_lib.ptr(p), _lib.ptr(o), _lib.ptr(im), bstride, _lib.ptr(Hm), _lib.ptr(warped), B, H, W,
-                                                  _lib.stream_ptr(dev))
-    _lib.check(rc, "dlt_warp")
+    _lib.launch("dlt_warp", dev, _lib.load().hdn_dlt_warp_strided_f32, _lib.ptr(p), _lib.ptr(o), _lib.ptr(im), bstride, _lib.ptr(Hm), _lib.ptr(warped),
+                B, H, W)
     return Hm.view(B, 3, 3), warped
 
 
@@ -242,9 +226,7 @@ def l1_score(a: torch.Tensor, b: torch.Tensor, scale: float) -> torch.Tensor:
         raise ValueError("l1_score needs two non-empty tensors of equal size")
     ac, bc = a.detach().contiguous(), b.detach().contiguous()
     out = torch.empty((1,), dtype=torch.float32, device=dev)
-    with _lib.device_guard(dev):
-        rc = _lib.load().hdn_l1_score_f32(_lib.ptr(ac), _lib.ptr(bc), _lib.ptr(out), ac.numel(), float(scale), _lib.stream_ptr(dev))
-    _lib.check(rc, "l1_score")
+    _lib.launch("l1_score", dev, _lib.load().hdn_l1_score_f32, _lib.ptr(ac), _lib.ptr(bc), _lib.ptr(out), ac.numel(), float(scale))
     return out[0]
 
 
@@ -256,10 +238,7 @@ def l1_score2(a: torch.Tensor, b0: torch.Tensor, b1: torch.Tensor, scale: float)
         raise ValueError("l1_score2 needs three non-empty tensors of equal size")
     ac, b0c, b1c = a.detach().contiguous(), b0.detach().contiguous(), b1.detach().contiguous()
     out = torch.empty((2,), dtype=torch.float32, device=dev)
-    with _lib.device_guard(dev):
-        rc = _lib.load().hdn_l1_score2_f32(_lib.ptr(ac), _lib.ptr(b0c), _lib.ptr(b1c), _lib.ptr(out), ac.numel(), float(scale),
-                                           _lib.stream_ptr(dev))
-    _lib.check(rc, "l1_score2")
+    _lib.launch("l1_score2", dev, _lib.load().hdn_l1_score2_f32, _lib.ptr(ac), _lib.ptr(b0c), _lib.ptr(b1c), _lib.ptr(out), ac.numel(), float(scale))
     return out[0], out[1]
 
 
@@ -274,8 +253,6 @@ def l1_score2_batch(a: torch.Tensor, b0: torch.Tensor, b1: torch.Tensor, scale: 
     B, n = a.shape[0], a.shape[2] * a.shape[3]
     ac, b0c, b1c = a.detach().contiguous(), b0.detach().contiguous(), b1.detach().contiguous()
     out = torch.empty((B, 2), dtype=torch.float32, device=dev)
-    with _lib.device_guard(dev):
-        rc = _lib.load().hdn_l1_score2_batch_f32(_lib.ptr(ac), _lib.ptr(b0c), _lib.ptr(b1c), _lib.ptr(out), n, n, B, float(scale), _lib.stream_ptr(dev))
-    _lib.check(rc, "l1_score2_batch")
+    _lib.launch("l1_score2_batch", dev, _lib.load().hdn_l1_score2_batch_f32, _lib.ptr(ac), _lib.ptr(b0c), _lib.ptr(b1c), _lib.ptr(out), n, n, B, float(scale))
     return out[:, 0], out[:, 1]
 

@@ -41,11 +41,8 @@ def _launch(x: torch.Tensor, polar: torch.Tensor, tabs, want_grid: bool):
     xc, pc = x.detach().contiguous(), polar.detach().contiguous()
     out = torch.empty((B, C, S, S), dtype=torch.float32, device=dev)
     grid = torch.empty((B, S, S, 2), dtype=torch.float32, device=dev) if want_grid else None
-    with _lib.device_guard(dev):
-        rc = _lib.load().hdn_logpolar_sample_f32(
-            _lib.ptr(xc), _lib.ptr(pc), _lib.ptr(rho), _lib.ptr(c), _lib.ptr(s), _lib.ptr(out),
-            _lib.ptr(grid) if want_grid else None, B, C, H, W, S, _lib.stream_ptr(dev))
-    _lib.check(rc, "STN_Polar")
+    _lib.launch("STN_Polar", dev, _lib.load().hdn_logpolar_sample_f32, _lib.ptr(xc), _lib.ptr(pc), _lib.ptr(rho), _lib.ptr(c), _lib.ptr(s), _lib.ptr(out),
+                _lib.opt(grid), B, C, H, W, S)
     return out, grid
 
 
@@ -68,18 +65,12 @@ def logpolar_sample_backward(x: torch.Tensor, polar: torch.Tensor, tabs, grad_ou
     xc, pc, gc = x.detach().contiguous(), polar.detach().contiguous(), grad_out.detach().contiguous()
     lib = _lib.load()
     gx = torch.empty_like(xc) if need_x else None          # zero-filled by the call
-    gp = ws = None
-    ws_bytes = 0
+    gp, ws, ws_bytes = None, None, 0
     if need_polar:
         gp = torch.empty((B, 2), dtype=torch.float32, device=dev)
-        ws_bytes = lib.hdn_logpolar_sample_bwd_workspace_bytes(B, S)
-        _lib.check(min(ws_bytes, 0), "logpolar_sample_backward")
-        ws = torch.empty((ws_bytes // 4,), dtype=torch.float32, device=dev)
-    with _lib.device_guard(dev):
-        rc = lib.hdn_logpolar_sample_bwd_f32(_lib.ptr(xc), _lib.ptr(pc), _lib.ptr(rho), _lib.ptr(c), _lib.ptr(s), _lib.ptr(gc),
-                                             _lib.ptr(gp) if need_polar else None, _lib.ptr(gx) if need_x else None,
-                                             _lib.ptr(ws) if need_polar else None, ws_bytes, B, C, H, W, S, _lib.stream_ptr(dev))
-    _lib.check(rc, "logpolar_sample_backward")
+        ws, ws_bytes = _lib.workspace("logpolar_sample_backward", lib.hdn_logpolar_sample_bwd_workspace_bytes(B, S), dev)
+    _lib.launch("logpolar_sample_backward", dev, lib.hdn_logpolar_sample_bwd_f32, _lib.ptr(xc), _lib.ptr(pc), _lib.ptr(rho), _lib.ptr(c), _lib.ptr(s),
+                _lib.ptr(gc), _lib.opt(gp), _lib.opt(gx), _lib.opt(ws), ws_bytes, B, C, H, W, S)
     return gx, gp
 
 

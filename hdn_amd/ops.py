@@ -6,8 +6,6 @@ torch's caching allocator and launches on torch's current stream.  There is no f
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 import torch.nn as nn
 
@@ -147,23 +145,13 @@ def _pack_conv_search(ws):
     n, CO = len(host), host[0].shape[0]
     if any(tuple(t.shape) != (CO, 256, 3, 3) for t in host):
         raise ValueError("conv_search weights must be [CO, 256, 3, 3]")
-    lib, ptrs = _lib.load(), _ptr_array(host)
+    lib, ptrs = _lib.load(), _lib.ptr_array(host)
     return _c_pack("pack_head_conv3x3", lib.hdn_pack_head_conv3x3_bytes(n, CO),
                    lambda o, nb: lib.hdn_pack_head_conv3x3_f32(ptrs, n, CO, o, nb)).to(ws[0].device)
 
 
 # ------------------------------------------------------------------------------------------------------------------------- launch helpers
 _CL = torch.channels_last
-
-
-def _opt(t):
-    """The device pointer of an optional tensor (NULL for None)."""
-    return _lib.ptr(t) if t is not None else None
-
-
-def _ptr_array(tensors):
-    """The data pointers of `tensors` as the `const float* const*` of the C side (the caller keeps the tensors alive until the call is made)."""
-    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
 
 
 def _square_cl(x):
@@ -174,20 +162,6 @@ def _square_cl(x):
 def _stream_ok(wpacked, dev, numel):
     """Is `wpacked` a packer's stream (int16) of `numel` elements on `dev`?"""
     return wpacked.dtype == torch.int16 and wpacked.device == dev and wpacked.numel() == numel
-
-
-def _workspace(what, nws, dev):
-    """(workspace or None, its size in bytes) for what a hdn_*_workspace_bytes query answered (a negative answer is its error code)."""
-    if nws < 0:
-        _lib.check(int(nws), what)
-    return (torch.empty(nws // 4, dtype=torch.float32, device=dev) if nws else None), nws   # (from torch's caching allocator: no sync, graph-safe)
-
-
-def _launch(what, dev, fn, *args):
-    """fn(*args, stream) on `dev`'s current stream; a non-zero return code raises (_lib.check)."""
-    with _lib.device_guard(dev):
-        rc = fn(*args, _lib.stream_ptr(dev))
-    _lib.check(rc, what)
 
 
 def _empty_cl(shape, dev):
@@ -210,7 +184,7 @@ def bias_relu_(y, bias, residual=None):
         raise ValueError("bias_relu_: y must be NCHW-contiguous or channels-last")
     if residual is not None and not (residual.is_contiguous(memory_format=_CL) if nhwc else residual.is_contiguous()):
         residual = residual.contiguous(memory_format=_CL if nhwc else torch.contiguous_format)
-    _launch("bias_relu", dev, _lib.load().hdn_bias_relu_f32, _lib.ptr(y), _lib.ptr(bias), _opt(residual), B, C, H * W, nhwc)
+    _lib.launch("bias_relu", dev, _lib.load().hdn_bias_relu_f32, _lib.ptr(y), _lib.ptr(bias), _lib.opt(residual), B, C, H * W, nhwc)
     return y
 
 
@@ -228,10 +202,10 @@ def conv3x3_bias_relu(x, wpacked, bias, residual=None, wpacked_v2=None, act_doma
     v2 = wpacked_v2 is not None and B >= V2_MIN_BATCH
     if v2 and not _stream_ok(wpacked_v2, dev, 9 * SPLIT_PIECES * C * C):
         raise ValueError("conv3x3_bias_relu: wpacked_v2 must come from pack_conv3x3_v2 for this channel count, on the input's device")
-    ws, nws = _workspace("conv3x3_bias_relu", lib.hdn_conv3x3_v2_workspace_bytes(B, S, C) if v2 else lib.hdn_conv3x3_workspace_bytes(B, S, C, 1), dev)
+    ws, nws = _lib.workspace("conv3x3_bias_relu", lib.hdn_conv3x3_v2_workspace_bytes(B, S, C) if v2 else lib.hdn_conv3x3_workspace_bytes(B, S, C, 1), dev)
     out = torch.empty_like(x, memory_format=_CL)
-    _launch("conv3x3_bias_relu", dev, lib.hdn_conv3x3_v2_f32 if v2 else lib.hdn_conv3x3_bias_relu_f32, _lib.ptr(x), _lib.ptr(wpacked_v2 if v2 else wpacked),
-            _lib.ptr(bias), _opt(residual), _lib.ptr(out), _opt(ws), nws, B, S, C, int(act_domain))
+    _lib.launch("conv3x3_bias_relu", dev, lib.hdn_conv3x3_v2_f32 if v2 else lib.hdn_conv3x3_bias_relu_f32, _lib.ptr(x), _lib.ptr(wpacked_v2 if v2 else wpacked),
+                _lib.ptr(bias), _lib.opt(residual), _lib.ptr(out), _lib.opt(ws), nws, B, S, C, int(act_domain))
     return out
 
 
@@ -251,12 +225,12 @@ def conv3x3s2_ds(x, wpacked, bias, wpacked_v2=None, act_domain=0):
     lib = _lib.load()
     out, out_ds = _empty_cl((B, CO, S, S), dev), _empty_cl((B, CO, S, S), dev)
     if v2:
-        _launch("conv3x3s2_v2", dev, lib.hdn_conv3x3s2_v2_f32, _lib.ptr(x), _lib.ptr(wpacked_v2), _lib.ptr(bias), _lib.ptr(out), _lib.ptr(out_ds),
-                B, S, CI, int(act_domain))
+        _lib.launch("conv3x3s2_v2", dev, lib.hdn_conv3x3s2_v2_f32, _lib.ptr(x), _lib.ptr(wpacked_v2), _lib.ptr(bias), _lib.ptr(out), _lib.ptr(out_ds),
+                    B, S, CI, int(act_domain))
     else:
-        ws, nws = _workspace("conv3x3s2_ds", lib.hdn_conv3x3_workspace_bytes(B, S, CI, 2), dev)
-        _launch("conv3x3s2_ds", dev, lib.hdn_conv3x3s2_ds_f32, _lib.ptr(x), _lib.ptr(wpacked), _lib.ptr(bias), _lib.ptr(out), _lib.ptr(out_ds),
-                _opt(ws), nws, B, S, CI, int(act_domain))
+        ws, nws = _lib.workspace("conv3x3s2_ds", lib.hdn_conv3x3_workspace_bytes(B, S, CI, 2), dev)
+        _lib.launch("conv3x3s2_ds", dev, lib.hdn_conv3x3s2_ds_f32, _lib.ptr(x), _lib.ptr(wpacked), _lib.ptr(bias), _lib.ptr(out), _lib.ptr(out_ds),
+                    _lib.opt(ws), nws, B, S, CI, int(act_domain))
     return out, out_ds
 
 
@@ -297,7 +271,7 @@ class LazyAct:
         dev = self.slices.device
         out = _empty_cl((B, C, S, S), dev)
         rp, rz = self.res_args()
-        _launch("conv3x3_finish", dev, _lib.load().hdn_conv3x3_finish_f32, _lib.ptr(self.slices), z, _lib.ptr(self.bias), rp, rz, _lib.ptr(out), B, S, C)
+        _lib.launch("conv3x3_finish", dev, _lib.load().hdn_conv3x3_finish_f32, _lib.ptr(self.slices), z, _lib.ptr(self.bias), rp, rz, _lib.ptr(out), B, S, C)
         return out
 
 
@@ -322,8 +296,8 @@ def chain_conv(x, wpacked, stride=1, want_x=False, act_domain=0):
     out_ds = torch.empty_like(out) if stride == 2 else None
     x_out = _empty_cl((B, CI, SI, SI), dev) if (lazy and want_x) else None
     rp, rz = x.res_args() if lazy else (None, 0)
-    _launch("conv3x3_chain", dev, lib.hdn_conv3x3_chain_f32, _lib.ptr(src), src.shape[0] if lazy else 0, _lib.ptr(x.bias) if lazy else None, rp, rz,
-            _opt(x_out), _lib.ptr(wpacked), _lib.ptr(out), _opt(out_ds), B, S, CI, stride, int(act_domain))
+    _lib.launch("conv3x3_chain", dev, lib.hdn_conv3x3_chain_f32, _lib.ptr(src), src.shape[0] if lazy else 0, _lib.opt(x.bias if lazy else None), rp, rz,
+                _lib.opt(x_out), _lib.ptr(wpacked), _lib.ptr(out), _lib.opt(out_ds), B, S, CI, stride, int(act_domain))
     return out, out_ds, x_out
 
 
@@ -340,8 +314,8 @@ def conv1x1(x, wpacked, bias, residual=None, stride=1, relu=True, act_domain=0):
     if residual is not None and (tuple(residual.shape) != (B, CO, So, So) or not residual.is_contiguous(memory_format=_CL)):
         raise ValueError(f"conv1x1: residual must be channels-last {(B, CO, So, So)}")
     out = _empty_cl((B, CO, So, So), dev)
-    _launch("conv1x1", dev, _lib.load().hdn_conv1x1_f32, _lib.ptr(x), _lib.ptr(wpacked), _lib.ptr(bias), _opt(residual), _lib.ptr(out), B, S, CI, CO,
-            int(stride), int(bool(relu)), int(act_domain))
+    _lib.launch("conv1x1", dev, _lib.load().hdn_conv1x1_f32, _lib.ptr(x), _lib.ptr(wpacked), _lib.ptr(bias), _lib.opt(residual), _lib.ptr(out), B, S, CI, CO,
+                int(stride), int(bool(relu)), int(act_domain))
     return out
 
 
@@ -356,9 +330,10 @@ def conv3x3s2(x, wpacked, bias, act_domain=0):
     if not _stream_ok(wpacked, dev, 9 * SPLIT_PIECES * C * C) or bias.numel() != C:
         raise ValueError("conv3x3s2: weights must come from pack_conv3x3s2 for this channel count, on the input's device")
     lib = _lib.load()
-    ws, nws = _workspace("conv3x3s2", lib.hdn_conv3x3s2_workspace_bytes(B, S, C), dev)
+    ws, nws = _lib.workspace("conv3x3s2", lib.hdn_conv3x3s2_workspace_bytes(B, S, C), dev)
     out = _empty_cl((B, C, S, S), dev)
-    _launch("conv3x3s2", dev, lib.hdn_conv3x3s2_f32, _lib.ptr(x), _lib.ptr(wpacked), _lib.ptr(bias), _lib.ptr(out), _opt(ws), nws, B, S, C, int(act_domain))
+    _lib.launch("conv3x3s2", dev, lib.hdn_conv3x3s2_f32, _lib.ptr(x), _lib.ptr(wpacked), _lib.ptr(bias), _lib.ptr(out), _lib.opt(ws), nws,
+                B, S, C, int(act_domain))
     return out
 
 
@@ -374,11 +349,11 @@ def _conv3x3_dv(valid, x, wpacked, bias, step, relu, act_domain):
     if CO <= 0 or not _stream_ok(wpacked, dev, 9 * SPLIT_PIECES * CO * CI) or (bias is not None and bias.numel() != CO):
         raise ValueError(f"{name}: weights must come from pack_conv3x3d for this CI (and the bias's CO), on the input's device")
     lib = _lib.load()
-    ws, nws = _workspace(name, getattr(lib, f"hdn_{name}_workspace_bytes")(B, S, CI, CO, int(step)), dev)     # (also refuses a step or side without a kernel)
+    ws, nws = _lib.workspace(name, getattr(lib, f"hdn_{name}_workspace_bytes")(B, S, CI, CO, int(step)), dev)   # (also refuses a step or side without a kernel)
     So = (S - 3) // int(step) + 1 if valid else S
     out = _empty_cl((B, CO, So, So), dev)
-    _launch(name, dev, getattr(lib, f"hdn_{name}_f32"), _lib.ptr(x), _lib.ptr(wpacked), _opt(bias), _lib.ptr(out), _opt(ws), nws, B, S, CI, CO, int(step),
-            int(bool(relu)), int(act_domain))
+    _lib.launch(name, dev, getattr(lib, f"hdn_{name}_f32"), _lib.ptr(x), _lib.ptr(wpacked), _lib.opt(bias), _lib.ptr(out), _lib.opt(ws), nws, B, S, CI, CO,
+                int(step), int(bool(relu)), int(act_domain))
     return out
 
 
@@ -409,7 +384,7 @@ def simi_stem(x, wpacked, bias):
         raise ValueError(f"simi_stem: side {S} outside 7 .. {SIMI_STEM_MAX_SIDE}")
     Sp = ((S - 7) // 2) // 2 + 1
     out = _empty_cl((B, 64, Sp, Sp), dev)
-    _launch("simi_stem", dev, lib.hdn_simi_stem_f32, _lib.ptr(x), _lib.ptr(wpacked), _lib.ptr(bias), _lib.ptr(out), B, S, 0)
+    _lib.launch("simi_stem", dev, lib.hdn_simi_stem_f32, _lib.ptr(x), _lib.ptr(wpacked), _lib.ptr(bias), _lib.ptr(out), B, S, 0)
     return out
 
 
@@ -442,8 +417,8 @@ def head_conv_batch(x_fs, wsp, bsp, groups=2):
     xs, xbs = _head_levels(x_fs, nhwc)
     CO = bsp.shape[1]
     out = torch.empty((n, groups, B, CO // groups, Hi - 2, Wi - 2), dtype=torch.float32, device=dev)
-    _launch("head_conv_batch", dev, _lib.load().hdn_head_conv3x3_batch_f32, _ptr_array(xs), _lib.ptr(wsp), _lib.ptr(bsp), _lib.ptr(out),
-            n, B, groups, CO, Hi, Wi, nhwc, xbs)
+    _lib.launch("head_conv_batch", dev, _lib.load().hdn_head_conv3x3_batch_f32, _lib.ptr_array(xs), _lib.ptr(wsp), _lib.ptr(bsp), _lib.ptr(out),
+                n, B, groups, CO, Hi, Wi, nhwc, xbs)
     return out
 
 
@@ -457,8 +432,8 @@ def head_conv_search(x_fs, pk):
     xs, _ = _head_levels(x_fs, nhwc)
     CO = pk.bsp.shape[1]
     out = torch.empty((n, CO, Hi - 2, Wi - 2), dtype=torch.float32, device=dev)
-    _launch("head_conv_search", dev, _lib.load().hdn_head_conv3x3_f32, _ptr_array(xs), _lib.ptr(pk.wsp), _lib.ptr(pk.bsp), _ptr_array(list(out)),
-            n, CO, Hi, Wi, nhwc)
+    _lib.launch("head_conv_search", dev, _lib.load().hdn_head_conv3x3_f32, _lib.ptr_array(xs), _lib.ptr(pk.wsp), _lib.ptr(pk.bsp), _lib.ptr_array(list(out)),
+                n, CO, Hi, Wi, nhwc)
     return out
 
 
@@ -467,8 +442,8 @@ def head_tail(feats, pk, n):
     dev = _lib.require_device(feats)
     H, P, om = feats.shape[1], feats.shape[2] * feats.shape[3], pk.wf.shape[1]
     out = torch.empty((2, om, P), dtype=torch.float32, device=dev)
-    _launch("head_tail", dev, _lib.load().hdn_head_tail_f32, _lib.ptr(feats), _lib.ptr(pk.w1p), _lib.ptr(pk.b1), _lib.ptr(pk.wf), _lib.ptr(pk.bf),
-            _lib.ptr(out), n, H, P, om)
+    _lib.launch("head_tail", dev, _lib.load().hdn_head_tail_f32, _lib.ptr(feats), _lib.ptr(pk.w1p), _lib.ptr(pk.b1), _lib.ptr(pk.wf), _lib.ptr(pk.bf),
+                _lib.ptr(out), n, H, P, om)
     return out
 
 
@@ -481,7 +456,7 @@ def head_tail_batch(feats, pk, n, B):
     H, Ho, Wo = feats.shape[2:]
     P = Ho * Wo
     out = torch.empty(B * (pk.oc + pk.ol) * P, dtype=torch.float32, device=dev)
-    _launch("head_tail_batch", dev, _lib.load().hdn_head_tail_batch_f32, _lib.ptr(feats), _lib.ptr(pk.w1p), _lib.ptr(pk.b1), _lib.ptr(pk.wf), _lib.ptr(pk.bf),
-            _lib.ptr(out), n, B, H, P, pk.oc, pk.ol)
+    _lib.launch("head_tail_batch", dev, _lib.load().hdn_head_tail_batch_f32, _lib.ptr(feats), _lib.ptr(pk.w1p), _lib.ptr(pk.b1), _lib.ptr(pk.wf),
+                _lib.ptr(pk.bf), _lib.ptr(out), n, B, H, P, pk.oc, pk.ol)
     split = B * pk.oc * P
     return out[:split].view(B, pk.oc, Ho, Wo), out[split:].view(B, pk.ol, Ho, Wo)

@@ -60,9 +60,7 @@ def share_feature(x: torch.Tensor, folded: torch.Tensor) -> torch.Tensor:
     if B == 0:
         raise ValueError("empty batch")
     out = torch.empty_like(xc)
-    with _lib.device_guard(dev):
-        rc = _lib.load().hdn_share_feature_f32(_lib.ptr(xc), _lib.ptr(folded), _lib.ptr(out), B, H, W, _lib.stream_ptr(dev))
-    _lib.check(rc, "PreShareFeature")
+    _lib.launch("PreShareFeature", dev, _lib.load().hdn_share_feature_f32, _lib.ptr(xc), _lib.ptr(folded), _lib.ptr(out), B, H, W)
     return out
 
 
@@ -87,18 +85,13 @@ def share_feature_train_forward(x, w1, w2, w3, gamma, bias, eps=(BN_EPS,) * 3, m
     mv = None if mean_var is None else mean_var.detach().contiguous()
     B, _, H, W = xc.shape
     lib = _lib.load()
-    ws_bytes = lib.hdn_share_feature_train_workspace_bytes(B, H, W)
-    _lib.check(min(ws_bytes, 0), "PreShareFeature (train)")
+    ws, ws_bytes = _lib.workspace("PreShareFeature (train)", lib.hdn_share_feature_train_workspace_bytes(B, H, W), dev)
     out = torch.empty_like(xc)
     saved = torch.empty((13 * xc.numel(),), dtype=torch.float32, device=dev)
     stats = torch.empty((39,), dtype=torch.float32, device=dev)
-    ws = torch.empty((ws_bytes // 4,), dtype=torch.float32, device=dev)
-    with _lib.device_guard(dev):
-        rc = lib.hdn_share_feature_train_fwd_f32(_lib.ptr(xc), _lib.ptr(w1), _lib.ptr(w2), _lib.ptr(w3), _lib.ptr(gamma), _lib.ptr(bias),
-                                                 None if mv is None else _lib.ptr(mv), float(eps[0]), float(eps[1]), float(eps[2]),
-                                                 0 if mv is None else 1, _lib.ptr(out), _lib.ptr(saved), _lib.ptr(stats), _lib.ptr(ws), ws_bytes,
-                                                 B, H, W, _lib.stream_ptr(dev))
-    _lib.check(rc, "PreShareFeature (train)")
+    _lib.launch("PreShareFeature (train)", dev, lib.hdn_share_feature_train_fwd_f32, _lib.ptr(xc), _lib.ptr(w1), _lib.ptr(w2), _lib.ptr(w3), _lib.ptr(gamma),
+                _lib.ptr(bias), _lib.opt(mv), float(eps[0]), float(eps[1]), float(eps[2]), 0 if mv is None else 1, _lib.ptr(out),
+                _lib.ptr(saved), _lib.ptr(stats), _lib.ptr(ws), ws_bytes, B, H, W)
     return out, saved, stats
 
 
@@ -116,16 +109,11 @@ def share_feature_train_backward(x, w1, w2, w3, gamma, bias, saved, stats, grad_
     if saved.numel() != 13 * xc.numel() or stats.numel() != 39:
         raise ValueError("saved / stats are not this input's")
     lib = _lib.load()
-    ws_bytes = lib.hdn_share_feature_train_workspace_bytes(B, H, W)
-    _lib.check(min(ws_bytes, 0), "PreShareFeature backward")
+    ws, ws_bytes = _lib.workspace("PreShareFeature backward", lib.hdn_share_feature_train_workspace_bytes(B, H, W), dev)
     gx = torch.empty_like(xc) if need_x else None
     gp = torch.empty((N_PARAMS,), dtype=torch.float32, device=dev) if need_params else None
-    ws = torch.empty((ws_bytes // 4,), dtype=torch.float32, device=dev)
-    with _lib.device_guard(dev):
-        rc = lib.hdn_share_feature_bwd_f32(_lib.ptr(xc), _lib.ptr(w1), _lib.ptr(w2), _lib.ptr(w3), _lib.ptr(gamma), _lib.ptr(bias), _lib.ptr(saved),
-                                           _lib.ptr(stats), _lib.ptr(gc), _lib.ptr(gx) if need_x else None, _lib.ptr(gp) if need_params else None,
-                                           _lib.ptr(ws), ws_bytes, 1 if frozen else 0, B, H, W, _lib.stream_ptr(dev))
-    _lib.check(rc, "PreShareFeature backward")
+    _lib.launch("PreShareFeature backward", dev, lib.hdn_share_feature_bwd_f32, _lib.ptr(xc), _lib.ptr(w1), _lib.ptr(w2), _lib.ptr(w3), _lib.ptr(gamma),
+                _lib.ptr(bias), _lib.ptr(saved), _lib.ptr(stats), _lib.ptr(gc), _lib.opt(gx), _lib.opt(gp), _lib.ptr(ws), ws_bytes, 1 if frozen else 0, B, H, W)
     return gx, gp
 
 

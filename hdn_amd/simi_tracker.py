@@ -209,10 +209,8 @@ class SimiTracker:
 
     def _update(self):
         c = self.cfg
-        with _lib.device_guard(self.dev):
-            _lib.check(_lib.load().hdn_simi_track_update_f64(_lib.ptr(self.state), _lib.ptr(self.track), _lib.ptr(self.seq), _lib.ptr(self._out), self.n,
-                                                             self.frame_hw[1], self.frame_hw[0], self.scale_score_thresh, c.context_amount, self.ratio,
-                                                             _lib.stream_ptr(self.dev)), "simi track update")
+        _lib.launch("simi track update", self.dev, _lib.load().hdn_simi_track_update_f64, _lib.ptr(self.state), _lib.ptr(self.track), _lib.ptr(self.seq),
+                    _lib.ptr(self._out), self.n, self.frame_hw[1], self.frame_hw[0], self.scale_score_thresh, c.context_amount, self.ratio)
 
     def _rotated_first(self):
         return FR.warp_affine_cubic(self.init_frame, self.track[:, 32:38])
@@ -358,10 +356,8 @@ class BatchedSimiTracker(SimiTracker):
         if self._arena is None:
             return super()._update()
         c, a = self.cfg, self._arena
-        with _lib.device_guard(self.dev):
-            _lib.check(_lib.load().hdn_simi_track_update_ragged_f64(_lib.ptr(self.state), _lib.ptr(self.track), _lib.ptr(self.seq), _lib.ptr(self._out),
-                                                                    _lib.ptr(a.dims), self.n, a.Hmax, a.Wmax, self.scale_score_thresh, c.context_amount,
-                                                                    self.ratio, _lib.stream_ptr(self.dev)), "simi track update (ragged)")
+        _lib.launch("simi track update (ragged)", self.dev, _lib.load().hdn_simi_track_update_ragged_f64, _lib.ptr(self.state), _lib.ptr(self.track),
+                    _lib.ptr(self.seq), _lib.ptr(self._out), _lib.ptr(a.dims), self.n, a.Hmax, a.Wmax, self.scale_score_thresh, c.context_amount, self.ratio)
 
     def _rotated_first(self):
         if self._arena is None:

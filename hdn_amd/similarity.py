@@ -108,11 +108,9 @@ class SimilarityDecoder:
         cls, loc_c = self._maps(cls, self.cfg.cls_out_channels, self.S, "cls"), self._maps(loc_c, 2, self.S, "loc_c")
         self._records(seq, state, B)
         c = self.cfg
-        with _lib.device_guard(dev):
-            rc = _lib.load().hdn_similarity_translation_f32(_lib.ptr(cls), _lib.ptr(loc_c), _lib.ptr(self.window), _lib.ptr(self.points),
-                                                            _lib.ptr(seq), _lib.ptr(state), B, self.S, c.window_influence, 8.0,
-                                                            float(c.exemplar_size), c.cls_out_channels, _lib.stream_ptr(dev))   # (_convert_c hard-codes 8)
-        _lib.check(rc, "similarity translation decode")
+        _lib.launch("similarity translation decode", dev, _lib.load().hdn_similarity_translation_f32, _lib.ptr(cls), _lib.ptr(loc_c), _lib.ptr(self.window),
+                    _lib.ptr(self.points), _lib.ptr(seq), _lib.ptr(state), B, self.S, c.window_influence, 8.0,   # (_convert_c hard-codes 8)
+                    float(c.exemplar_size), c.cls_out_channels)
 
     def logpolar(self, cls_lp, loc_lp, seq, state):
         """cls_lp [B,cls_out_channels,S,S], loc_lp [B,4,S,S] + the record the translation call wrote -> state[:, 16:46]."""
@@ -120,11 +118,8 @@ class SimilarityDecoder:
         B = cls_lp.shape[0]
         cls_lp, loc_lp = self._maps(cls_lp, self.cfg.cls_out_channels, self.S_lp, "cls_lp"), self._maps(loc_lp, 4, self.S_lp, "loc_lp")
         self._records(seq, state, B)
-        with _lib.device_guard(dev):
-            rc = _lib.load().hdn_similarity_logpolar_f32(_lib.ptr(cls_lp), _lib.ptr(loc_lp), _lib.ptr(self.points_lp), _lib.ptr(seq),
-                                                         _lib.ptr(state), B, self.S_lp, float(self.cfg.stride_lp), self.mag, self.rot_unit,
-                                                         self.cfg.cls_out_channels, _lib.stream_ptr(dev))
-        _lib.check(rc, "similarity log-polar decode")
+        _lib.launch("similarity log-polar decode", dev, _lib.load().hdn_similarity_logpolar_f32, _lib.ptr(cls_lp), _lib.ptr(loc_lp), _lib.ptr(self.points_lp),
+                    _lib.ptr(seq), _lib.ptr(state), B, self.S_lp, float(self.cfg.stride_lp), self.mag, self.rot_unit, self.cfg.cls_out_channels)
 
 
 # views into one state record (1-D, length STATE_DOUBLES)

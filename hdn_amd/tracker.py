@@ -114,11 +114,10 @@ class HomoTracker:
         host reads, no allocations that depend on data: capturable in a hipGraph when the frames are a static buffer.  H_total ([3,3] / [n,3,3]
         float64, a buffer of this object) advances in place.
         -> (out float32 [n, 2 * points + 1] = corners (x, y) + best_score per sequence (a buffer of this object), the gating score)."""
-        lib, st, n = _lib.load(), _lib.stream_ptr(self.dev), self.n
+        lib, n = _lib.load(), self.n
         # :150-155  undo the accumulated motion (a singular H_total is reset to the identity, as the reference does).
         # hdn_frame_warp_perspective_u8 inverts its matrix itself (cv2 semantics), so it is handed inv(H_total), every sequence its own.
-        with _lib.device_guard(self.dev):
-            _lib.check(lib.hdn_track_prepare_f64(_lib.ptr(self.H_total), _lib.ptr(self._Ht), _lib.ptr(self._Hinv), n, st), "track prepare")
+        _lib.launch("track prepare", self.dev, lib.hdn_track_prepare_f64, _lib.ptr(self.H_total), _lib.ptr(self._Ht), _lib.ptr(self._Hinv), n)
         frames = FR.warp_perspective(frames, self._Hinv.view(n, 9))
         sim_state = None
         if self.similarity is not None:
@@ -135,11 +134,9 @@ class HomoTracker:
                                             per_sample=self._per_sample)
         # :251-272  un-scale, un-shift, gate, accumulate, project the initial corners
         score = homo_score.detach().reshape(-1).to(torch.float32).contiguous()
-        with _lib.device_guard(self.dev):
-            _lib.check(lib.hdn_track_accumulate_f64(_lib.ptr(self._Ht), _lib.ptr(sim_state) if sim_state is not None else None, _lib.ptr(H_comp),
-                                                    _lib.ptr(score), _lib.ptr(self._consts), _lib.ptr(self.init_points), self.n_points,
-                                                    _lib.ptr(self.H_total), _lib.ptr(self._out), n, st),
-                       "track accumulate")     # (in place: the kernel reads Ht, the copy hdn_track_prepare_f64 made)
+        _lib.launch("track accumulate", self.dev, lib.hdn_track_accumulate_f64, _lib.ptr(self._Ht), _lib.opt(sim_state), _lib.ptr(H_comp), _lib.ptr(score),
+                    _lib.ptr(self._consts), _lib.ptr(self.init_points), self.n_points,
+                    _lib.ptr(self.H_total), _lib.ptr(self._out), n)     # (in place: the kernel reads Ht, the copy hdn_track_prepare_f64 made)
         return self._out, (score if self._per_sample else homo_score)
 
     def _static_input(self, img):

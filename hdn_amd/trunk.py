@@ -17,7 +17,7 @@ import torch.nn.functional as F
 from . import _lib
 # the launch wrappers and packers live in hdn_amd.ops; every name is kept importable from here
 from .ops import (ACT_SCALE_LOG2, MATRIX_CORE_CHANNELS, S2_CHANNELS, SIMI_STEM_MAX_SIDE, SPLIT_PIECES, V2_MIN_BATCH, _MC_SIDE,  # noqa: F401
-                  LazyAct, _c_pack, _host_f32, _launch, bias_relu_, chain_conv, conv1x1, conv3x3_bias_relu, conv3x3d, conv3x3s2, conv3x3s2_ds, conv3x3v,
+                  LazyAct, _c_pack, _host_f32, bias_relu_, chain_conv, conv1x1, conv3x3_bias_relu, conv3x3d, conv3x3s2, conv3x3s2_ds, conv3x3v,
                   fold_conv_bn, pack_conv1x1, pack_conv3x3, pack_conv3x3_v2, pack_conv3x3d, pack_conv3x3s2, pack_conv3x3s2_ds, pack_conv3x3s2_ds_v2,
                   pack_simi_stem, pack_stem_mfma, simi_stem)
 
@@ -174,11 +174,11 @@ class FusedStem(nn.Module):
         out = torch.empty((B, 64, Hp, Wp), dtype=x.dtype, device=dev,
                           memory_format=torch.channels_last if self.channels_last else torch.contiguous_format)
         if self.channels_last and H == 127 and W == 127 and B >= STEM_MFMA_MIN_BATCH and not self.mfma_disabled:
-            _launch("trunk_stem_mfma", dev, _lib.load().hdn_trunk_stem_mfma_f32, _lib.ptr(xs), _lib.ptr(self.wfrag), _lib.ptr(self.b), _lib.ptr(out),
-                    B, H, W, self.out_domain)
+            _lib.launch("trunk_stem_mfma", dev, _lib.load().hdn_trunk_stem_mfma_f32, _lib.ptr(xs), _lib.ptr(self.wfrag), _lib.ptr(self.b), _lib.ptr(out),
+                        B, H, W, self.out_domain)
             return out
-        _launch("trunk_stem", dev, _lib.load().hdn_trunk_stem_f32, _lib.ptr(xs), _lib.ptr(self.wT), _lib.ptr(self.b), _lib.ptr(out), B, H, W,
-                1 if self.channels_last else 0)
+        _lib.launch("trunk_stem", dev, _lib.load().hdn_trunk_stem_f32, _lib.ptr(xs), _lib.ptr(self.wT), _lib.ptr(self.b), _lib.ptr(out), B, H, W,
+                    1 if self.channels_last else 0)
         return out.mul_(2.0 ** -ACT_SCALE_LOG2) if self.out_domain else out
 
 

@@ -13,7 +13,6 @@ xcorr_depthwise_multi, xcorr_fast and xcorr_slow are inference only: their resul
 """
 from __future__ import annotations
 
-import ctypes
 from typing import List, Sequence
 
 import torch
@@ -51,9 +50,7 @@ def _xcorr(x: torch.Tensor, kernel: torch.Tensor, circular: bool) -> torch.Tenso
     B, C, Hx, Wx = xc.shape
     Hk, Wk = kc.shape[2:]
     fn = lib.hdn_xcorr_depthwise_circ_f32 if circular else lib.hdn_xcorr_depthwise_f32
-    with _lib.device_guard(dev):
-        rc = fn(_lib.ptr(xc), _lib.ptr(kc), _lib.ptr(out), B, C, Hx, Wx, Hk, Wk, _lib.stream_ptr(dev))
-    _lib.check(rc, "xcorr_depthwise_circular" if circular else "xcorr_depthwise")
+    _lib.launch("xcorr_depthwise_circular" if circular else "xcorr_depthwise", dev, fn, _lib.ptr(xc), _lib.ptr(kc), _lib.ptr(out), B, C, Hx, Wx, Hk, Wk)
     return out
 
 
@@ -73,11 +70,8 @@ def xcorr_depthwise_backward(x: torch.Tensor, kernel: torch.Tensor, grad_out: to
     gk = torch.empty_like(kc) if need_k else None
     B, C, Hx, Wx = xc.shape
     Hk, Wk = kc.shape[2:]
-    with _lib.device_guard(dev):
-        rc = _lib.load().hdn_xcorr_depthwise_bwd_f32(_lib.ptr(xc), _lib.ptr(kc), _lib.ptr(gc), _lib.ptr(gx) if need_x else None,
-                                                     _lib.ptr(gk) if need_k else None, int(bool(circular)), B, C, Hx, Wx, Hk, Wk,
-                                                     _lib.stream_ptr(dev))
-    _lib.check(rc, "xcorr_depthwise_backward")
+    _lib.launch("xcorr_depthwise_backward", dev, _lib.load().hdn_xcorr_depthwise_bwd_f32, _lib.ptr(xc), _lib.ptr(kc), _lib.ptr(gc), _lib.opt(gx), _lib.opt(gk),
+                int(bool(circular)), B, C, Hx, Wx, Hk, Wk)
     return gx, gk
 
 
@@ -148,15 +142,10 @@ def xcorr_depthwise_multi(xs: Sequence[torch.Tensor], kernels: Sequence[torch.Te
         if len(outs) != n or any(tuple(o.shape) != tuple(shape) or o.dtype != torch.float32 or o.device != dev or not o.is_contiguous()
                                  for o in outs):
             raise ValueError(f"outs must be {n} contiguous float32 tensors of shape {tuple(shape)} on {dev}")
-    arr = ctypes.c_void_p * n
     B, C, Hx, Wx = xcs[0].shape
     Hk, Wk = kcs[0].shape[2:]
-    with _lib.device_guard(dev):
-        rc = lib.hdn_xcorr_depthwise_multi_f32(
-            arr(*[t.data_ptr() for t in xcs]), arr(*[t.data_ptr() for t in kcs]), arr(*[t.data_ptr() for t in outs]),
-            n, int(bool(circular)), B, C, Hx, Wx, Hk, Wk, _lib.stream_ptr(dev),
-        )
-    _lib.check(rc, "xcorr_depthwise_multi")
+    _lib.launch("xcorr_depthwise_multi", dev, lib.hdn_xcorr_depthwise_multi_f32, _lib.ptr_array(xcs), _lib.ptr_array(kcs), _lib.ptr_array(outs),
+                n, int(bool(circular)), B, C, Hx, Wx, Hk, Wk)
     return outs
 
 
@@ -177,10 +166,7 @@ def xcorr_fast(x: torch.Tensor, kernel: torch.Tensor) -> torch.Tensor:
         raise ValueError(f"kernel {Hk}x{Wk} does not fit the search plane {Hx}x{Wx}")
     dev, xc, kc = _prep(x, kernel)
     out = torch.empty((B, O, Hx - Hk + 1, Wx - Wk + 1), dtype=torch.float32, device=dev)
-    with _lib.device_guard(dev):
-        rc = _lib.load().hdn_xcorr_fast_f32(_lib.ptr(xc), _lib.ptr(kc), _lib.ptr(out), B, C, O, Hx, Wx, Hk, Wk,
-                                            _lib.stream_ptr(dev))
-    _lib.check(rc, "xcorr_fast")
+    _lib.launch("xcorr_fast", dev, _lib.load().hdn_xcorr_fast_f32, _lib.ptr(xc), _lib.ptr(kc), _lib.ptr(out), B, C, O, Hx, Wx, Hk, Wk)
     return out
 
 

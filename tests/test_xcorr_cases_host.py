@@ -158,9 +158,11 @@ def test_restated_constants_match_the_sources():
     # the direct 61 x 61 kernel: 4 waves of one plane each, grid capped at 512 / n
     assert _ints(r"const int gw = blockIdx\.x \* (\d+) \+ wave;", xc) == [XC.NORTH_WAVES] and _ints(r"const int nw = gridDim\.x \* (\d+);", xc) == [XC.NORTH_WAVES]
     assert _ints(r"const int per_problem = max\(1, min\(cdiv\(planes, (\d+)\), cap / n\)\);", xc) == [XC.NORTH_WAVES]
-    assert _ints(r"int v = e \? atoi\(e\) : 0; return v > 0 \? v : (\d+);", xc) == [XC.CAP_DIRECT]
-    assert _ints(r"int c = e \? atoi\(e\) : 0; return c > 0 \? c : (\d+);", xc) == [XC.CAP_FFT]
-    assert len(re.findall(r'getenv\("%s"\)' % XC.CAP_ENV, xc)) == 2
+    direct, fftc = xc[xc.index("static int launch_north("):xc.index("g_last_variant = \"north_61x61_31x31\";")], xc[xc.index("if (v == HDN_NORTH_FFT_COL) {"):]
+    assert _ints(r'static const int cap = env_positive\("%s", (\d+)\);' % XC.CAP_ENV, direct) == [XC.CAP_DIRECT]
+    assert _ints(r'static const int cap = env_positive\("%s", (\d+)\);' % XC.CAP_ENV, fftc) == [XC.CAP_FFT]
+    assert len(re.findall(r'"%s"' % XC.CAP_ENV, xc)) == 2 and "getenv(name);" in common       # (read nowhere else; env_positive reads it)
+    assert "const int v = e ? atoi(e) : 0;\n  return v > 0 ? v : fallback;" in common[common.index("inline int env_positive(const char* name, int fallback) {"):]
     # the FFT kernel: pairs, nmain workers + one tail worker, 4 workers per workgroup, the stagger condition, the prefetch index
     assert len(re.findall(r"xcorr_north_fft4_kernel<%d>" % XC.FFT_WPG, fft)) == 3 and len(re.findall(r"xcorr_north_fft4_kernel<\d+>", fft)) == 3
     assert len(re.findall(r"dim3\(\(workers \+ 3\) / 4\), dim3\(256\)", fft)) == 2
