@@ -140,6 +140,9 @@ SIGNATURES = {
     "hdn_dlt_solve_bwd_f32": (_i, [_c_float_p] * 5 + [_i, ctypes.c_void_p]),
     "hdn_warp_bwd_workspace_bytes": (ctypes.c_longlong, [_i, _i, _i]),
     "hdn_warp_bwd_f32": (_i, [_c_float_p] * 6 + [ctypes.c_longlong] + [_i] * 4 + [ctypes.c_void_p]),
+    "hdn_affine_sample_f32": (_i, [_c_float_p] * 3 + [_i] * 6 + [ctypes.c_void_p]),
+    "hdn_affine_sample_bwd_workspace_bytes": (ctypes.c_longlong, [_i] * 3),
+    "hdn_affine_sample_bwd_f32": (_i, [_c_float_p] * 6 + [ctypes.c_longlong] + [_i] * 6 + [ctypes.c_void_p]),
 }
 
 ERRORS = {

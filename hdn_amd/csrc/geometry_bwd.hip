@@ -7,7 +7,7 @@
 //
 // grad_polar / grad_theta (a sum over every pixel and channel of a sample) are deterministic and use no atomics: a lane adds its channels (and, in
 // the warp, its pixels) in ascending order, a wave adds its lanes in a fixed xor tree (32 .. 1), the block's waves are added in ascending order through
-// LDS and written as one partial per (sample, block) into the caller's workspace; reduce_partials_kernel, a second launch of the same call, has one
+// LDS (block_sum_store, geometry.h) and written as one partial per (sample, block) into the caller's workspace; reduce_partials_kernel (geometry.h), a second launch of the same call, has one
 // wave per sample add the partials (lane l takes blocks l, l + 64, ... in ascending order, then the same tree).  Nothing depends on the batch size:
 // sample b of a batch has the bits of that sample run alone.
 // grad_img is a scatter: plain fp32 atomicAdd (one global_atomic_add_f32) into the buffer that the call zero-fills on the stream first.  The order in
@@ -18,47 +18,6 @@
 
 namespace hdn {
 namespace gbwd {
-
-constexpr int WAVES = HDN_BLOCK / HDN_WAVE;
-
-// v[q] summed over the block in a fixed order; thread q < N then writes the sum to dst[q].  lds: WAVES * N floats.  Every thread of the block calls it.
-template <int N>
-__device__ __forceinline__ void block_sum_store(float (&v)[N], float* lds, float* __restrict__ dst) {
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int q = 0; q < N; ++q) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v[q] = rn_add(v[q], __shfl_xor(v[q], m, HDN_WAVE));
-  }
-  if ((tid & (HDN_WAVE - 1)) == 0) {
-#pragma unroll
-    for (int q = 0; q < N; ++q) lds[(tid >> 6) * N + q] = v[q];
-  }
-  __syncthreads();
-  if (tid < N) {
-    float s = lds[tid];
-#pragma unroll
-    for (int w = 1; w < WAVES; ++w) s = rn_add(s, lds[w * N + tid]);
-    dst[tid] = s;
-  }
-}
-
-// out[b][q] = scale[q] * (partials part[b][0 .. nblk)[q] added in a fixed order); one wave per sample.
-template <int N>
-__global__ __launch_bounds__(HDN_WAVE) void reduce_partials_kernel(const float* __restrict__ part, float* __restrict__ out, int nblk, const float s0,
-                                                                    const float s1) {
-  const size_t b = blockIdx.x;
-  const int lane = threadIdx.x;
-  const float* p = part + b * nblk * N;
-#pragma unroll
-  for (int q = 0; q < N; ++q) {
-    float s = 0.f;
-    for (int k = lane; k < nblk; k += HDN_WAVE) s = rn_add(s, p[size_t(k) * N + q]);
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) s = rn_add(s, __shfl_xor(s, m, HDN_WAVE));
-    if (lane == 0) out[b * N + q] = rn_mul(q == 0 ? s0 : s1, s);
-  }
-}
 
 // ---------------------------------------------------------------------------------------------------------------- log-polar sampler
 __global__ __launch_bounds__(HDN_BLOCK) void logpolar_bwd_kernel(const float* __restrict__ img, const float* __restrict__ polar,
@@ -278,18 +237,6 @@ __global__ __launch_bounds__(HDN_BLOCK) void warp_bwd_kernel(const float* __rest
     }
   }
   if (part) block_sum_store<9>(acc, red, part + (size_t(b) * gridDim.x + blockIdx.x) * 9);  // kernel-uniform branch
-}
-
-static int zero_fill(float* p, long long floats, hipStream_t st) {
-  const hipError_t e = hipMemsetAsync(p, 0, size_t(floats) * sizeof(float), st);
-  return e == hipSuccess ? HDN_OK : -(1000 + (int)e);
-}
-
-// an output may not be an input or the other output
-static bool aliases(const float* out, const float* const* others, int n) {
-  for (int q = 0; q < n; ++q)
-    if (out && out == others[q]) return true;
-  return false;
 }
 
 }  // namespace gbwd

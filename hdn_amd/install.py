@@ -19,12 +19,14 @@ attribute the reference resolves at call time:
     ModelBuilder.track_new_lp                            same ops, the zero `polar` argument cached on the device (:145: a pageable
                                                          host->device copy per frame, which a hipGraph capture cannot hold)
     ModelBuilder.template                                unchanged, then drops the heads' cached template-branch features
+    ModelBuilder.stn_with_theta                          (install(train=True), while AFFINE_STN_TRAIN_BOUND) the differentiable HIP affine sampler
     hdn.tracker.tracker_builder.TRACKS['hdnTrackerHomoProje2e']   (install(tracker=True)) the device-resident tracker loop
 
 Training under install(train=True): every statement of the reference's training forwards that resolves to a drop-in is differentiable on the device -
 xcorr_depthwise{,_circular} (hdn_amd/xcorr.py), DLT_solve / transform / transformer (hdn_amd/homography.py) and, with train=True, STN_Polar
 (STN_PolarTrain, hdn_amd/logpolar.py; without train=True the STN_Polar drop-in raises on a grad-carrying input rather than detach) and
-PreShareFeature (PreShareFeatureTrain, hdn_amd/share_feature.py: batch statistics and the backward on HIP, and an eval mode that carries the graph).  The rebound head
+PreShareFeature (PreShareFeatureTrain, hdn_amd/share_feature.py: batch statistics and the backward on HIP, and an eval mode that carries the graph) and
+ModelBuilder.stn_with_theta (hdn_amd/affine.py: the affine sampler of :407, :408, :418, forward and backward on HIP).  The rebound head
 forwards defer to the classes' own forward in .train() mode.  What still needs uninstall(): anything that calls the fused inference paths with
 autograd expected - the fused track_proj, dlt_warp, the fused heads in eval mode, xcorr_fast / xcorr_slow, xcorr_depthwise_multi (they detach).
 """
@@ -36,7 +38,7 @@ import weakref
 
 import torch
 
-from . import heads, homo_model, homography, logpolar, share_feature, xcorr
+from . import affine, heads, homo_model, homography, logpolar, share_feature, xcorr
 
 _DLT = "homo_estimator.Deep_homography.Oneline_DLTv1"
 
@@ -124,6 +126,10 @@ def _make_template_method(orig):
 # (profiles/share_feature_train.json): True only while the HIP path is faster than the stock nn.Sequential on the step's six calls at B = 32.
 SHARE_FEATURE_TRAIN_BOUND = True
 
+# Does install(train=True) bind hdn_amd.affine.stn_with_theta at ModelBuilder.stn_with_theta?  Set by the outcome of tools/affine_stn_train_bench.py
+# (profiles/affine_stn_train.json): True only while the HIP path is faster than F.affine_grid + F.grid_sample on the step's three calls at B = 32.
+AFFINE_STN_TRAIN_BOUND = True
+
 _MISSING = object()
 _saved = []  # (owner, attribute or dict key, original value, is_dict_item) in application order; undone by uninstall()
 
@@ -173,7 +179,8 @@ def install(strict: bool = False, modules: dict = None, tracker: bool = False, t
     (hdn_amd.homo_model.optimize_trunk(self.hm_net, channels_last=True)) at its first eval-mode call with CUDA float32 weights, for users of the
     rebindings without the device tracker; off by default.  train=True: the two STN_Polar sites are bound to hdn_amd.logpolar.STN_PolarTrain (the same
     module with differentiable=True) and, while SHARE_FEATURE_TRAIN_BOUND, preprocess.head['PreShareFeature'] to hdn_amd.share_feature.PreShareFeatureTrain
-    (hip_train=True), so that the reference's training forward runs on the drop-ins; everything else is unchanged.  Returns the list of (module, attribute) pairs that were rebound;
+    (hip_train=True) and, while AFFINE_STN_TRAIN_BOUND, ModelBuilder.stn_with_theta to hdn_amd.affine.stn_with_theta, so that the reference's training
+    forward runs on the drop-ins; everything else is unchanged.  Returns the list of (module, attribute) pairs that were rebound;
     with strict=True a site that cannot be imported raises instead of being skipped.  uninstall() reverses it."""
     done = []
 
@@ -223,6 +230,9 @@ def install(strict: bool = False, modules: dict = None, tracker: bool = False, t
         if orig_t is not None and not hasattr(orig_t, "_hdn_wraps"):
             _rebind(mb.ModelBuilder, "template", _make_template_method(orig_t))
             done.append(("hdn.models.model_builder_e2e_unconstrained_v2", "ModelBuilder.template"))
+        if train and AFFINE_STN_TRAIN_BOUND and "stn_with_theta" in mb.ModelBuilder.__dict__:
+            _rebind(mb.ModelBuilder, "stn_with_theta", affine.stn_with_theta)
+            done.append(("hdn.models.model_builder_e2e_unconstrained_v2", "ModelBuilder.stn_with_theta"))
 
     if tracker:
         tb = get("hdn.tracker.tracker_builder")

@@ -335,6 +335,49 @@ int hdn_warp_bwd_f32(const float* img, const float* theta, const float* grad_out
                      float* workspace, long long workspace_bytes, int B, int C, int H, int W, void* stream);
 
 /*
+ * Affine spatial transformer (csrc/affine_stn.hip): out[b,c,i,j] = bilinear(img[b,c], p(i,j)) where p is what F.affine_grid(theta, size) followed
+ * by F.grid_sample with PyTorch's defaults (mode='bilinear', padding_mode='zeros', align_corners=False) samples; the grid is never materialised.
+ *   X_j = (2j+1)/Wo - 1,  Y_i = (2i+1)/Ho - 1
+ *   gx = t00 X_j + t01 Y_i + t02,   gy = t10 X_j + t11 Y_i + t12            (t = theta[b])
+ *   px = ((gx+1) W - 1)/2,          py = ((gy+1) H - 1)/2
+ *   x0 = floor(px), y0 = floor(py), w = px - x0, n = py - y0
+ *   out = (1-n)(1-w) I_nw + (1-n) w I_ne + n (1-w) I_sw + n w I_se          a tap outside [0,W) x [0,H) reads 0
+ * px, py, x0, y0 and the differences px - x0, py - y0 are formed in float64 from the fp32 theta (every operation rounded on its own, in the order
+ * written) and w, n, e = 1 - w, s = 1 - n each rounded to fp32 once: an fp32 px of size 100 would leave a bilinear weight 1e-5 of absolute error.
+ * The blend is fp32, every operation rounded on its own: out = ((I_nw (s e) + I_ne (s w)) + I_sw (n e)) + I_se (n w).  Guard: a sample whose px is not strictly inside (-1, W) or whose
+ * py is not strictly inside (-1, H) - NaN, +-inf and values beyond any int included - gives out = 0 and contributes to no gradient; the decision is
+ * a float comparison made before any conversion to an integer and before any address is formed (PyTorch's zeros padding gives 0 for a finite position outside too).
+ * img[B,C,H,W], theta[B,2,3] -> out[B,C,Ho,Wo], all fp32 contiguous.  Checked before the launch, in this order: a NULL pointer -> HDN_E_NULL; a size
+ * <= 0 -> HDN_E_SHAPE; B > 65535, H W or Ho Wo > 2^30 -> HDN_E_LIMIT; out equal to img or theta -> HDN_E_ALIAS.
+ * Replaces ModelBuilder.stn_with_theta(x, theta, size), model_builder_e2e_unconstrained_v2.py:233-237 (training forward: :407, :408, :418).
+ */
+int hdn_affine_sample_f32(const float* img, const float* theta, float* out, int B, int C, int H, int W, int Ho, int Wo, void* stream);
+
+/*
+ * hdn_affine_sample_bwd_f32: the sampler above, under the common rules of the geometry backwards (see hdn_logpolar_sample_bwd_f32 above): a NULL
+ * output is not computed and asking for no gradient is HDN_E_SHAPE; the checks run in the same order (NULL, shape, limit, workspace, alias); the
+ * sample point, the guard included, is recomputed by the forward's own statements (one __device__ function shared by both kernels); grad_theta is
+ * DETERMINISTIC (no atomics, fixed-order block reduction by wave shuffles then LDS, one partial of six floats per (sample, block) in `workspace`, a
+ * second launch of the same call adds the partials in a fixed order: two calls are bit-equal and sample b of a batch has the bits of that sample run
+ * alone); grad_img is an fp32 atomicAdd scatter into the buffer the call zero-fills on `stream` and is NOT bit-reproducible between calls.
+ * With the forward's w, n and the four taps (a tap outside the plane is 0; zeros padding has no clip mask):
+ *   d out / d px = (1-n)(I_ne - I_nw) + n (I_se - I_sw)
+ *   d out / d py = (1-w)(I_sw - I_nw) + w (I_se - I_ne)
+ *   d px / d gx = W/2,  d py / d gy = H/2
+ *   grad_theta[b,0,:] = sum over c, i, j of grad_out[b,c,i,j] d out / d px (W/2) (X_j, Y_i, 1)
+ *   grad_theta[b,1,:] = sum over c, i, j of grad_out[b,c,i,j] d out / d py (H/2) (X_j, Y_i, 1)
+ *   grad_img[b,c] += grad_out[b,c,i,j] {(1-n)(1-w), (1-n) w, n (1-w), n w} at the four taps; outside taps receive nothing.
+ * A guarded sample (see the forward) contributes 0 to both.
+ * img[B,C,H,W], theta[B,2,3], grad_out[B,C,Ho,Wo] -> grad_theta[B,2,3] and/or grad_img[B,C,H,W].  Limits: the forward's.
+ * workspace: hdn_affine_sample_bwd_workspace_bytes(B, Ho, Wo) bytes (B ceil(Ho Wo / 256) partials of 24 bytes; negative = HDN_E_*), 16-byte aligned,
+ * needed for grad_theta only (else it may be NULL).
+ * Differentiates ModelBuilder.stn_with_theta; two of the step's three calls take affine_m, which carries sim_loss and homo_unsup_loss to both heads.
+ */
+long long hdn_affine_sample_bwd_workspace_bytes(int B, int Ho, int Wo);
+int hdn_affine_sample_bwd_f32(const float* img, const float* theta, const float* grad_out, float* grad_theta_or_null, float* grad_img_or_null,
+                              float* workspace, long long workspace_bytes, int B, int C, int H, int W, int Ho, int Wo, void* stream);
+
+/*
  * Device-resident frame handling: the uint8 frame [H,W,C] (HWC, BGR as cv2.imread delivers it) is
  * uploaded once; crops and warps are kernels.  `params` / `M` are DEVICE float64 arrays so that positions and homographies
  * produced on the device never visit the host.
