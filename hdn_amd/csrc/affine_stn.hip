@@ -13,7 +13,8 @@
 // any int included - is dead: the decision is a float comparison made before any conversion to an integer, its out is 0 and it contributes to no
 // gradient (PyTorch's zeros padding gives 0 there too).
 //
-// grad_theta is deterministic: a lane adds its channels in ascending order, then block_sum_store / reduce_partials_kernel of geometry.h (wave xor
+// grad_theta is deterministic: a lane adds its channels in ascending order (channels_bwd of geometry.h, the channel walk of every sampler backward),
+// then block_sum_store / reduce_partials_kernel of geometry.h (wave xor
 // tree, waves in ascending order through LDS, one partial of six floats per (sample, block) in the workspace, a second launch of the same call adds
 // them in a fixed order).  64 partials per sample at 127 x 127: the second launch's one wave per sample reads each partial once.  grad_img is an fp32
 // atomicAdd scatter into the buffer the call zero-fills on the stream, NOT bit-reproducible between calls.
@@ -96,31 +97,11 @@ __global__ __launch_bounds__(HDN_BLOCK) void sample_bwd_kernel(const float* __re
     float th[6];
     load_theta(theta, b, th);
     const Point p = sample_point(th, pix, H, W, Ho, Wo);
-    const float nw = rn_mul(p.s, p.e), ne = rn_mul(p.s, p.w), sw = rn_mul(p.n, p.e), se = rn_mul(p.n, p.w);
+    const gbwd::Taps t = {p.i_nw, p.i_ne, p.i_sw, p.i_se, p.k_nw, p.k_ne, p.k_sw, p.k_se, p.e, p.w, p.s, p.n};
     const size_t HW = size_t(H) * W, SS = size_t(Ho) * Wo;
-    const float* im = img + size_t(b) * C * HW;
-    const float* g = gout + size_t(b) * C * SS + pix;
-    float* gi = gimg ? gimg + size_t(b) * C * HW : nullptr;
     float ax = 0.f, ay = 0.f;  // sum over channels of gout * d out / d px, d out / d py
-    for (int c = 0; c < C; ++c) {
-      const float go = g[size_t(c) * SS];
-      if (part) {
-        const float* pl = im + c * HW;
-        const float l_nw = pl[p.i_nw], l_ne = pl[p.i_ne], l_sw = pl[p.i_sw], l_se = pl[p.i_se];
-        const float v_nw = p.k_nw ? l_nw : 0.f, v_ne = p.k_ne ? l_ne : 0.f, v_sw = p.k_sw ? l_sw : 0.f, v_se = p.k_se ? l_se : 0.f;
-        const float dpx = rn_add(rn_mul(p.s, rn_sub(v_ne, v_nw)), rn_mul(p.n, rn_sub(v_se, v_sw)));
-        const float dpy = rn_add(rn_mul(p.e, rn_sub(v_sw, v_nw)), rn_mul(p.w, rn_sub(v_se, v_ne)));
-        ax = rn_add(ax, rn_mul(go, dpx));
-        ay = rn_add(ay, rn_mul(go, dpy));
-      }
-      if (gi) {
-        float* pl = gi + c * HW;
-        if (p.k_nw) atomicAdd(pl + p.i_nw, rn_mul(go, nw));
-        if (p.k_ne) atomicAdd(pl + p.i_ne, rn_mul(go, ne));
-        if (p.k_sw) atomicAdd(pl + p.i_sw, rn_mul(go, sw));
-        if (p.k_se) atomicAdd(pl + p.i_se, rn_mul(go, se));
-      }
-    }
+    gbwd::channels_bwd(t, img + size_t(b) * C * HW, gimg ? gimg + size_t(b) * C * HW : nullptr, HW, gout + size_t(b) * C * SS + pix, SS, C,
+                       part != nullptr, ax, ay);
     // d px / d gx = W/2, d py / d gy = H/2;  g_r = theta[r,0] X + theta[r,1] Y + theta[r,2]
     ax = rn_mul(ax, rn_mul((float)W, 0.5f));
     ay = rn_mul(ay, rn_mul((float)H, 0.5f));
@@ -166,24 +147,13 @@ int hdn_affine_sample_bwd_f32(const float* img, const float* theta, const float*
   if (affine::check_dims(B, C, H, W, Ho, Wo) || (!grad_theta_or_null && !grad_img_or_null)) return HDN_E_SHAPE;
   if (affine::over_limit(B, (long long)H * W, (long long)Ho * Wo)) return HDN_E_LIMIT;
   const long long img_floats = (long long)B * C * H * W, out_floats = (long long)B * C * Ho * Wo;
-  float* part = nullptr;
-  if (grad_theta_or_null) {
-    const int rc = check_workspace(workspace, workspace_bytes, hdn_affine_sample_bwd_workspace_bytes(B, Ho, Wo), img, img_floats * 4, grad_out,
-                                   out_floats * 4);
-    if (rc) return rc;
-    part = workspace;
-  }
-  const float* ins[5] = {img, theta, grad_out, part, grad_img_or_null};
-  if (gbwd::aliases(grad_theta_or_null, ins, 5) || gbwd::aliases(grad_img_or_null, ins, 4)) return HDN_E_ALIAS;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (grad_img_or_null) {
-    const int rc = gbwd::zero_fill(grad_img_or_null, img_floats, st);
-    if (rc) return rc;
-  }
   const int nblk = cdiv(Ho * Wo, HDN_BLOCK);
-  hipLaunchKernelGGL(affine::sample_bwd_kernel, dim3(nblk, B), dim3(HDN_BLOCK), 0, st, img, theta, grad_out, part, grad_img_or_null, C, H, W, Ho, Wo);
-  if (part) hipLaunchKernelGGL(gbwd::reduce_partials_kernel<6>, dim3(B), dim3(HDN_WAVE), 0, st, part, grad_theta_or_null, nblk, 1.0f, 1.0f);
-  return launch_status();
+  return gbwd::sampler_bwd<6>({img, theta, grad_out}, img_floats, out_floats, grad_theta_or_null, grad_img_or_null, workspace, workspace_bytes,
+                              hdn_affine_sample_bwd_workspace_bytes(B, Ho, Wo), nblk, B, 1.0f, 1.0f, st, [&](float* part) {
+                                hipLaunchKernelGGL(affine::sample_bwd_kernel, dim3(nblk, B), dim3(HDN_BLOCK), 0, st, img, theta, grad_out, part,
+                                                   grad_img_or_null, C, H, W, Ho, Wo);
+                              });
 }
 
 }  // extern "C"

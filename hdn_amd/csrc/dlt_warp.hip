@@ -2,9 +2,9 @@
 // Reference: homo_estimator/Deep_homography/Oneline_DLTv1/utils.py:7-67 (DLT_solve),
 //            :70-254 (transformer), :257-274 (transform).
 //
-// DLT: the 8x8 system is solved by 8 lanes (lane r owns row r of [A|b], 9 float64 registers)
-// with Gauss-Jordan elimination and partial pivoting; pivot search and pivot-row broadcast are
-// wave shuffles, so nothing touches memory.  The reference inverts A in fp32 and multiplies;
+// DLT: the 8x8 system (dlt_row, geometry.h) is solved by 8 lanes (lane r owns row r of [A|b], 9 float64
+// registers) with Gauss-Jordan elimination and partial pivoting (solve8, geometry.h); pivot search and pivot-row
+// broadcast are wave shuffles, so nothing touches memory.  The reference inverts A in fp32 and multiplies;
 // for the production corners its result is within 7e-7 of the exact solution, which is what
 // this kernel returns (rounded once to fp32).
 //
@@ -13,8 +13,9 @@
 // the reference's CPU kernels do not fuse, so that tap selection and the degenerate cases
 // (both taps clamped to one index -> exact cancellation, |t| < 1e-7 nudge, float->int
 // conversion of out-of-range coordinates) come out as the reference's PyTorch-CPU path gives
-// them.  See DESIGN.md "warp semantics".
-#include "geometry.h"   // dlt_point, grid_coord, f2i_x86, clampi, WARP_PX_PER_*: shared with the backward (geometry_bwd.hip)
+// them.  See DESIGN.md "warp semantics".  The sample point itself (grid coordinate, theta's rows, nudge, taps)
+// is warp_point of geometry.h, which the backward calls too.
+#include "geometry.h"   // warp_point, dlt_row, solve8, WARP_PX_PER_*: shared with the backward (geometry_bwd.hip)
 
 // The reference's CPU kernels round after every multiply and add here: rn_mul/rn_add/rn_sub/rn_div (hdn_common.h) are
 // compiled with contraction off; fusion is spelled out with __builtin_fmaf where the reference fuses.
@@ -27,52 +28,7 @@ namespace hdn {
 __device__ __forceinline__ double dlt_solve_rows(const float* __restrict__ src, const float* __restrict__ off,
                                                  int lane) {
   const int r = lane & 7;
-  const int p = dlt_point(r >> 1);
-  const double x = (double)src[2 * p], y = (double)src[2 * p + 1];
-  // dst = src + off is an fp32 add in the reference (utils.py:36)
-  const double u = (double)rn_add(src[2 * p], off[2 * p]);
-  const double v = (double)rn_add(src[2 * p + 1], off[2 * p + 1]);
-  double a[9];
-  if ((r & 1) == 0) {
-    a[0] = x; a[1] = y; a[2] = 1.0; a[3] = 0.0; a[4] = 0.0; a[5] = 0.0; a[6] = -u * x; a[7] = -u * y; a[8] = u;
-  } else {
-    a[0] = 0.0; a[1] = 0.0; a[2] = 0.0; a[3] = x; a[4] = y; a[5] = 1.0; a[6] = -v * x; a[7] = -v * y; a[8] = v;
-  }
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    // partial pivoting over rows >= k; ties resolve to the lowest row (as LAPACK's idamax does)
-    double best = (r >= k) ? fabs(a[k]) : -1.0;
-    int bidx = r;
-#pragma unroll
-    for (int m = 4; m >= 1; m >>= 1) {
-      const double ob = __shfl_xor(best, m, 8);
-      const int oi = __shfl_xor(bidx, m, 8);
-      if (ob > best || (ob == best && oi < bidx)) { best = ob; bidx = oi; }
-    }
-    double prow[9], krow[9];
-#pragma unroll
-    for (int j = k; j < 9; ++j) {
-      prow[j] = __shfl(a[j], bidx, 8);
-      krow[j] = __shfl(a[j], k, 8);
-    }
-    if (r == k) {
-#pragma unroll
-      for (int j = k; j < 9; ++j) a[j] = prow[j];
-    } else if (r == bidx) {
-#pragma unroll
-      for (int j = k; j < 9; ++j) a[j] = krow[j];
-    }
-    if (r != k) {
-      const double f = a[k] / prow[k];
-#pragma unroll
-      for (int j = k; j < 9; ++j) a[j] = fma(-f, prow[j], a[j]);
-    }
-  }
-  // after Gauss-Jordan row r is [0 .. a[r] .. 0 | a[8]]
-  double diag = a[0];
-#pragma unroll
-  for (int j = 1; j < 8; ++j) diag = (r == j) ? a[j] : diag;
-  return a[8] / diag;
+  return solve8(dlt_row(src, off, r), r);
 }
 
 // The same elimination with the 8 x 9 system in LDS and one wave sharing the work (element (r, j) on lane r*9 + j, the last 8
@@ -81,17 +37,9 @@ __device__ __forceinline__ double dlt_solve_rows(const float* __restrict__ src, 
 // control flow); A: 72 doubles of LDS owned by that wave.  On return lane r < 8 holds h[r].
 __device__ __forceinline__ double dlt_solve_lds(const float* __restrict__ src, const float* __restrict__ off, double* A, int lane) {
   if (lane < 8) {
-    const int r = lane, p = dlt_point(r >> 1);
-    const double x = (double)src[2 * p], y = (double)src[2 * p + 1];
-    const double u = (double)rn_add(src[2 * p], off[2 * p]), v = (double)rn_add(src[2 * p + 1], off[2 * p + 1]);
-    double a[9];
-    if ((r & 1) == 0) {
-      a[0] = x; a[1] = y; a[2] = 1.0; a[3] = 0.0; a[4] = 0.0; a[5] = 0.0; a[6] = -u * x; a[7] = -u * y; a[8] = u;
-    } else {
-      a[0] = 0.0; a[1] = 0.0; a[2] = 0.0; a[3] = x; a[4] = y; a[5] = 1.0; a[6] = -v * x; a[7] = -v * y; a[8] = v;
-    }
+    const Row9 row = dlt_row(src, off, lane);
 #pragma unroll
-    for (int j = 0; j < 9; ++j) A[r * 9 + j] = a[j];
+    for (int j = 0; j < 9; ++j) A[lane * 9 + j] = row.v[j];
   }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   const int e1 = lane, e2 = lane + 64;
@@ -149,26 +97,10 @@ __device__ __forceinline__ void normalise_H(const float* Hm, float ax, float ay,
 // Returns the pixel's term of the reference's `condition` count: |t| > 1e-7 after the nudge (utils.py:241).
 __device__ __forceinline__ bool warp_pixel(const float* __restrict__ img, const float* th, float* __restrict__ out,
                                            int i, int j, int C, int H, int W) {
-  const float gx = grid_coord(j, W), gy = grid_coord(i, H);
-  // T = theta @ [gx, gy, 1]: fma(t1, gy, t0*gx) + t2   (the reference's sgemm order; utils.py:230)
-  const float T0 = rn_add(__builtin_fmaf(th[1], gy, rn_mul(th[0], gx)), th[2]);
-  const float T1 = rn_add(__builtin_fmaf(th[4], gy, rn_mul(th[3], gx)), th[5]);
-  float t = rn_add(__builtin_fmaf(th[7], gy, rn_mul(th[6], gx)), th[8]);
-  // utils.py:236-240: t += 1e-6 * (1 - [|t| >= 1e-7])
-  t = rn_add(t, rn_mul(1e-6f, (fabsf(t) >= 1e-7f) ? 0.0f : 1.0f));
-  const float xs = rn_div(T0, t), ys = rn_div(T1, t);
-  // utils.py:128-129: x = (x_s + 1) * W / 2
-  const float x = rn_mul(rn_mul(rn_add(xs, 1.0f), (float)W), 0.5f);
-  const float y = rn_mul(rn_mul(rn_add(ys, 1.0f), (float)H), 0.5f);
-  const int xf = f2i_x86(floorf(x)), yf = f2i_x86(floorf(y));
-  const int x0 = clampi(xf, 0, W - 1), x1 = clampi((int)((unsigned)xf + 1u), 0, W - 1);
-  const int y0 = clampi(yf, 0, H - 1), y1 = clampi((int)((unsigned)yf + 1u), 0, H - 1);
-  // utils.py:181-184: weights from the CLAMPED taps and the UNCLAMPED coordinate
-  const float x0f = (float)x0, x1f = (float)x1, y0f = (float)y0, y1f = (float)y1;
-  const float wa = rn_mul(rn_sub(x1f, x), rn_sub(y1f, y));
-  const float wb = rn_mul(rn_sub(x1f, x), rn_sub(y, y0f));
-  const float wc = rn_mul(rn_sub(x, x0f), rn_sub(y1f, y));
-  const float wd = rn_mul(rn_sub(x, x0f), rn_sub(y, y0f));
+  const WarpPoint p = warp_point(th, i, j, H, W);
+  const int x0 = p.x0, x1 = p.x1, y0 = p.y0, y1 = p.y1;
+  // utils.py:181-185: wa .. wd, the weights of taps a = (y0, x0), b = (y1, x0), c = (y0, x1), d = (y1, x1)
+  const float wa = rn_mul(p.ax, p.ay), wb = rn_mul(p.ax, p.by), wc = rn_mul(p.bx, p.ay), wd = rn_mul(p.bx, p.by);
   const size_t HW = size_t(H) * W;
   float* o = out + (size_t(i) * W + j) * C;
   for (int c = 0; c < C; ++c) {
@@ -177,7 +109,7 @@ __device__ __forceinline__ bool warp_pixel(const float* __restrict__ img, const 
     // utils.py:185: wa*Ia + wb*Ib + wc*Ic + wd*Id, left to right, no fusion
     o[c] = rn_add(rn_add(rn_add(rn_mul(wa, Ia), rn_mul(wb, Ib)), rn_mul(wc, Ic)), rn_mul(wd, Id));
   }
-  return fabsf(t) > 1e-7f;
+  return fabsf(p.t) > 1e-7f;
 }
 
 __global__ __launch_bounds__(HDN_BLOCK) void dlt_solve_kernel(const float* __restrict__ src,

@@ -17,7 +17,7 @@
 
 #include <mutex>
 
-#include "hdn_common.h"
+#include "cv_warp.h"
 
 #pragma clang fp contract(off)
 
@@ -134,35 +134,24 @@ __global__ __launch_bounds__(HDN_BLOCK) void subwindow_ragged_kernel(const uint8
 typedef uint32_t u32u __attribute__((aligned(1)));
 __device__ __forceinline__ uint32_t ld4(const uint8_t* p) { return *reinterpret_cast<const u32u*>(p); }
 __device__ __forceinline__ int byte_of(uint32_t w, int i) { return (int)((w >> (8 * i)) & 0xffu); }
-__device__ __forceinline__ void inv3(const double* m, double* o) {
-  const double d = m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
-  const double id = d != 0.0 ? 1.0 / d : 0.0;
-  o[0] = (m[4] * m[8] - m[5] * m[7]) * id; o[1] = (m[2] * m[7] - m[1] * m[8]) * id; o[2] = (m[1] * m[5] - m[2] * m[4]) * id;
-  o[3] = (m[5] * m[6] - m[3] * m[8]) * id; o[4] = (m[0] * m[8] - m[2] * m[6]) * id; o[5] = (m[2] * m[3] - m[0] * m[5]) * id;
-  o[6] = (m[3] * m[7] - m[4] * m[6]) * id; o[7] = (m[1] * m[6] - m[0] * m[7]) * id; o[8] = (m[0] * m[4] - m[1] * m[3]) * id;
-}
-__device__ __forceinline__ int cv_round_sat(double v) { return (int)rint(fmax(-2147483648.0, fmin(2147483647.0, v))); }
 
+// The walk (inverse, block geometry, 1/32-pixel coordinates, clamped taps) is cv_warp.h, shared with refine_warp.hip; the integer
+// weights and the byte paths are here.
 __device__ __forceinline__ void frame_warp_perspective_body(const uint8_t* __restrict__ src, const double* __restrict__ M,
                                                             uint8_t* __restrict__ dst, int H, int W, int C, int bw) {
   double m[9], mi[9];
 #pragma unroll
   for (int q = 0; q < 9; ++q) m[q] = M[q];
-  inv3(m, mi);
+  inv3_f64(m, mi);
   const size_t n = size_t(H) * W;
   for (size_t base = size_t(blockIdx.x) * HDN_BLOCK; base < n; base += size_t(gridDim.x) * HDN_BLOCK) {
     const bool valid = base + threadIdx.x < n;
     const size_t pix = valid ? base + threadIdx.x : n - 1;
     const int y = (int)(pix / W), x = (int)(pix - size_t(y) * W);
-    const int bx = (x / bw) * bw, x1 = x - bx;
-    const double X0 = mi[0] * bx + mi[1] * y + mi[2], Y0 = mi[3] * bx + mi[4] * y + mi[5], W0 = mi[6] * bx + mi[7] * y + mi[8];
-    double Wd = W0 + mi[6] * x1;
-    Wd = Wd != 0.0 ? 32.0 / Wd : 0.0;
-    const int X = cv_round_sat((X0 + mi[0] * x1) * Wd), Y = cv_round_sat((Y0 + mi[3] * x1) * Wd);
-    const int sx = X >> 5, sy = Y >> 5, ax = X & 31, ay = Y & 31;
+    const CvPoint p = cv_warp_point(mi, x, y, bw, H, W);
+    const int ax = p.X & 31, ay = p.Y & 31;
     const int w00 = (32 - ay) * (32 - ax) * 32, w01 = (32 - ay) * ax * 32, w10 = ay * (32 - ax) * 32, w11 = ay * ax * 32;
-    const int x0 = min(max(sx, 0), W - 1), x1c = (int)min(max((long long)sx + 1, 0LL), (long long)W - 1);
-    const int y0 = min(max(sy, 0), H - 1), y1c = (int)min(max((long long)sy + 1, 0LL), (long long)H - 1);
+    const int x0 = p.x0, x1c = p.x1, y0 = p.y0, y1c = p.y1;
     const uint8_t* p00 = src + (size_t(y0) * W + x0) * C;
     const uint8_t* p01 = src + (size_t(y0) * W + x1c) * C;
     const uint8_t* p10 = src + (size_t(y1c) * W + x0) * C;
@@ -198,12 +187,6 @@ __global__ __launch_bounds__(HDN_BLOCK) void frame_warp_perspective_kernel(const
                               C, bw);
 }
 
-// OpenCV's block walk (BLOCK_SZ 32): it fixes the summation order of x.  The batch entry computes it on the host; a ragged slot has its own.
-__host__ __device__ __forceinline__ int perspective_bw(int H, int W) {
-  const int bh = H < 16 ? H : 16;
-  return 1024 / bh < W ? 1024 / bh : W;
-}
-
 __global__ __launch_bounds__(HDN_BLOCK) void frame_warp_perspective_ragged_kernel(const uint8_t* __restrict__ src, long long slot_stride,
                                                                                   const int* __restrict__ dims, const double* __restrict__ M,
                                                                                   uint8_t* __restrict__ dst, int Hmax, int Wmax, int C,
@@ -212,7 +195,7 @@ __global__ __launch_bounds__(HDN_BLOCK) void frame_warp_perspective_ragged_kerne
   if (!slot_dims(dims, Hmax, Wmax, C, slot_stride, H, W)) return;
   // (the 4-byte fast path's guard inside uses this slot's own H * W: a frame's last pixels never read the next slot's bytes as their own)
   frame_warp_perspective_body(src + size_t(blockIdx.y) * slot_stride, M + size_t(blockIdx.y) * m_stride, dst + size_t(blockIdx.y) * slot_stride, H,
-                              W, C, perspective_bw(H, W));
+                              W, C, cv_block(H, W).bw);  // (a ragged slot has its own block walk)
 }
 
 // ---- cv2.warpAffine, 8U, INTER_CUBIC, BORDER_REPLICATE ---------------------------------------------------------------
@@ -401,7 +384,7 @@ int hdn_frame_warp_perspective_batch_u8(const unsigned char* src, const double* 
     const unsigned char* const de = dst + (size_t)B * H * W * C;
     if (src < de && dst < se) return HDN_E_ALIAS;
   }
-  const int bw = hdn::perspective_bw(H, W);
+  const int bw = hdn::cv_block(H, W).bw;
   hipLaunchKernelGGL(hdn::frame_warp_perspective_kernel, dim3(hdn::frame_grid((size_t)H * W), B), dim3(HDN_BLOCK), 0,
                      static_cast<hipStream_t>(stream), src, M, dst, H, W, C, bw, m_stride);
   return hdn::launch_status();

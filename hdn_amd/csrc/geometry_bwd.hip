@@ -1,9 +1,10 @@
 // Backward of the three geometry operators for gfx950 (training only): hdn_logpolar_sample_bwd_f32 (logpolar.hip), hdn_dlt_solve_bwd_f32 and
 // hdn_warp_bwd_f32 (dlt_warp.hip).  The formulas are in include/hdn_hip.h.
 //
-// Each kernel recomputes its forward's sample point with the forward's own statements (the same rn_* helpers, contraction off, the shared helpers of
-// geometry.h), so the taps it differentiates through are the taps the forward read.  The launch shapes are the forward's: HDN_BLOCK threads, one
-// pixel per lane in the sampler, WARP_PX_PER_THREAD per thread in the warp, one 8-lane group per sample in the solve.
+// Each kernel recomputes its forward's sample point by calling the function the forward calls (logpolar_point, warp_point, dlt_row + solve8 of
+// geometry.h), so the taps it differentiates through are the taps the forward read; the channel walk of the two samplers is channels_bwd
+// (geometry.h), shared with affine_stn.hip, and the entry points' host sequence is sampler_bwd.  The launch shapes are the forward's: HDN_BLOCK
+// threads, one pixel per lane in the sampler, WARP_PX_PER_THREAD per thread in the warp, one 8-lane group per sample in the solve.
 //
 // grad_polar / grad_theta (a sum over every pixel and channel of a sample) are deterministic and use no atomics: a lane adds its channels (and, in
 // the warp, its pixels) in ascending order, a wave adds its lanes in a fixed xor tree (32 .. 1), the block's waves are added in ascending order through
@@ -29,50 +30,14 @@ __global__ __launch_bounds__(HDN_BLOCK) void logpolar_bwd_kernel(const float* __
   const int pix = blockIdx.x * HDN_BLOCK + threadIdx.x;
   float acc[2] = {0.f, 0.f};  // sum over channels of gout * d out / d px, d out / d py, times the border rule
   if (pix < S * S) {
-    // ---- the statements of logpolar_kernel ----
-    const int a = pix / S, b = pix - a * S;
-    const float r = rho[b];
-    const float gx = rn_div(rn_add(rn_mul(r, cosT[a]), polar[2 * n]), (float)(H / 2));
-    const float gy = rn_div(rn_add(rn_mul(r, sinT[a]), polar[2 * n + 1]), (float)(W / 2));
-    const float pxu = rn_sub(rn_mul(rn_add(gx, 1.0f), rn_mul((float)W, 0.5f)), 0.5f);
-    const float pyu = rn_sub(rn_mul(rn_add(gy, 1.0f), rn_mul((float)H, 0.5f)), 0.5f);
-    const float px = fminf((float)(W - 1), fmaxf(0.0f, pxu));
-    const float py = fminf((float)(H - 1), fmaxf(0.0f, pyu));
-    const float xw = floorf(px), yn = floorf(py);
-    const float w = rn_sub(px, xw), e = rn_sub(1.0f, w);
-    const float nn = rn_sub(py, yn), s = rn_sub(1.0f, nn);
-    const float nw = rn_mul(s, e), ne = rn_mul(s, w), sw = rn_mul(nn, e), se = rn_mul(nn, w);
-    const int x0 = (int)xw, y0 = (int)yn;
-    const bool e_ok = x0 + 1 < W, s_ok = y0 + 1 < H;
-    const int x1 = e_ok ? x0 + 1 : x0, y1 = s_ok ? y0 + 1 : y0;
-    // ---- clip_coordinates_set_grad: a coordinate that the clamp moved (or that sits on the border) has derivative 0 ----
-    const float mx = (pxu <= 0.0f || pxu >= (float)(W - 1)) ? 0.f : 1.f;
-    const float my = (pyu <= 0.0f || pyu >= (float)(H - 1)) ? 0.f : 1.f;
+    const LogpolarPoint p = logpolar_point(polar, rho, cosT, sinT, n, pix, H, W, S);
+    // clip_coordinates_set_grad: a coordinate that the clamp moved (or that sits on the border) has derivative 0
+    const float mx = (p.pxu <= 0.0f || p.pxu >= (float)(W - 1)) ? 0.f : 1.f;
+    const float my = (p.pyu <= 0.0f || p.pyu >= (float)(H - 1)) ? 0.f : 1.f;
+    const Taps t = {p.y0 * W + p.x0, p.y0 * W + p.x1, p.y1 * W + p.x0, p.y1 * W + p.x1, true, p.e_ok, p.s_ok, p.e_ok && p.s_ok, p.e, p.w, p.s, p.nn};
     const size_t HW = size_t(H) * W, SS = size_t(S) * S;
-    const float* im = img + size_t(n) * C * HW;
-    const float* g = gout + size_t(n) * C * SS + pix;
-    float* gi = gimg ? gimg + size_t(n) * C * HW : nullptr;
-    for (int c = 0; c < C; ++c) {
-      const float go = g[size_t(c) * SS];
-      if (part) {
-        const float* pl = im + c * HW;
-        const float v_nw = pl[y0 * W + x0];
-        const float v_ne = e_ok ? pl[y0 * W + x1] : 0.f;
-        const float v_sw = s_ok ? pl[y1 * W + x0] : 0.f;
-        const float v_se = (e_ok && s_ok) ? pl[y1 * W + x1] : 0.f;
-        const float dpx = rn_add(rn_mul(s, rn_sub(v_ne, v_nw)), rn_mul(nn, rn_sub(v_se, v_sw)));
-        const float dpy = rn_add(rn_mul(e, rn_sub(v_sw, v_nw)), rn_mul(w, rn_sub(v_se, v_ne)));
-        acc[0] = rn_add(acc[0], rn_mul(go, dpx));
-        acc[1] = rn_add(acc[1], rn_mul(go, dpy));
-      }
-      if (gi) {
-        float* pl = gi + c * HW;
-        atomicAdd(pl + y0 * W + x0, rn_mul(go, nw));
-        if (e_ok) atomicAdd(pl + y0 * W + x1, rn_mul(go, ne));
-        if (s_ok) atomicAdd(pl + y1 * W + x0, rn_mul(go, sw));
-        if (e_ok && s_ok) atomicAdd(pl + y1 * W + x1, rn_mul(go, se));
-      }
-    }
+    channels_bwd(t, img + size_t(n) * C * HW, gimg ? gimg + size_t(n) * C * HW : nullptr, HW, gout + size_t(n) * C * SS + pix, SS, C, part != nullptr,
+                 acc[0], acc[1]);
     acc[0] = rn_mul(acc[0], mx);
     acc[1] = rn_mul(acc[1], my);
   }
@@ -80,57 +45,6 @@ __global__ __launch_bounds__(HDN_BLOCK) void logpolar_bwd_kernel(const float* __
 }
 
 // ---------------------------------------------------------------------------------------------------------------- DLT solve
-// Element (j, c) of [A|b] (c == 8: b) of one sample, rows as dlt_solve_rows builds them.
-__device__ __forceinline__ double dlt_elem(const float* __restrict__ src, const float* __restrict__ off, int j, int c) {
-  const int p = dlt_point(j >> 1);
-  const double x = (double)src[2 * p], y = (double)src[2 * p + 1];
-  const int k = 2 * p + (j & 1);
-  const double d = (double)rn_add(src[k], off[k]);  // u on an even row, v on an odd one: an fp32 add in the reference (utils.py:36)
-  const int c3 = (j & 1) ? c - 3 : c;                // the odd rows hold (x, y, 1) three columns further
-  if (c == 8) return d;
-  if (c == 6) return -d * x;
-  if (c == 7) return -d * y;
-  return c3 == 0 ? x : (c3 == 1 ? y : (c3 == 2 ? 1.0 : 0.0));
-}
-
-// Gauss-Jordan with partial pivoting on the 8 x 9 system whose row r = lane & 7 is a[0..8], in an aligned group of 8 lanes: the elimination of
-// dlt_solve_rows (dlt_warp.hip).  Every lane of the wave calls it.  Returns the r-th unknown.
-__device__ __forceinline__ double solve8(double (&a)[9], int r) {
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    double best = (r >= k) ? fabs(a[k]) : -1.0;
-    int bidx = r;
-#pragma unroll
-    for (int m = 4; m >= 1; m >>= 1) {
-      const double ob = __shfl_xor(best, m, 8);
-      const int oi = __shfl_xor(bidx, m, 8);
-      if (ob > best || (ob == best && oi < bidx)) { best = ob; bidx = oi; }
-    }
-    double prow[9], krow[9];
-#pragma unroll
-    for (int j = k; j < 9; ++j) {
-      prow[j] = __shfl(a[j], bidx, 8);
-      krow[j] = __shfl(a[j], k, 8);
-    }
-    if (r == k) {
-#pragma unroll
-      for (int j = k; j < 9; ++j) a[j] = prow[j];
-    } else if (r == bidx) {
-#pragma unroll
-      for (int j = k; j < 9; ++j) a[j] = krow[j];
-    }
-    if (r != k) {
-      const double f = a[k] / prow[k];
-#pragma unroll
-      for (int j = k; j < 9; ++j) a[j] = fma(-f, prow[j], a[j]);
-    }
-  }
-  double diag = a[0];
-#pragma unroll
-  for (int j = 1; j < 8; ++j) diag = (r == j) ? a[j] : diag;
-  return a[8] / diag;
-}
-
 __global__ __launch_bounds__(HDN_BLOCK) void dlt_solve_bwd_kernel(const float* __restrict__ src, const float* __restrict__ off,
                                                                   const float* __restrict__ gH, float* __restrict__ gsrc,
                                                                   float* __restrict__ goff, int B) {
@@ -139,14 +53,12 @@ __global__ __launch_bounds__(HDN_BLOCK) void dlt_solve_bwd_kernel(const float* _
   const int r = threadIdx.x & 7;
   const float* s = src + size_t(b) * 8;
   const float* o = off + size_t(b) * 8;
-  double a[9];
+  const double h = solve8(dlt_row(s, o, r), r);  // A h = b, the forward's own solve
+  Row9 at;
 #pragma unroll
-  for (int c = 0; c < 9; ++c) a[c] = dlt_elem(s, o, r, c);
-  const double h = solve8(a, r);  // A h = b
-#pragma unroll
-  for (int j = 0; j < 8; ++j) a[j] = dlt_elem(s, o, j, r);  // row r of A^T
-  a[8] = (double)gH[size_t(b) * 9 + r];                     // gH[8] meets the constant 1
-  const double lam = solve8(a, r);  // A^T lambda = grad_h;  grad_b = lambda, grad_A = -lambda h^T
+  for (int j = 0; j < 8; ++j) at.v[j] = dlt_elem(s, o, j, r);  // row r of A^T
+  at.v[8] = (double)gH[size_t(b) * 9 + r];                     // gH[8] meets the constant 1
+  const double lam = solve8(at, r);  // A^T lambda = grad_h;  grad_b = lambda, grad_A = -lambda h^T
   double hc[8];
 #pragma unroll
   for (int c = 0; c < 8; ++c) hc[c] = __shfl(h, c, 8);
@@ -190,50 +102,21 @@ __global__ __launch_bounds__(HDN_BLOCK) void warp_bwd_kernel(const float* __rest
     const int pix = base + q * HDN_BLOCK;
     if (pix >= H * W) continue;
     const int i = pix / W, j = pix - i * W;
-    // ---- the statements of warp_pixel ----
-    const float gx = grid_coord(j, W), gy = grid_coord(i, H);
-    const float T0 = rn_add(__builtin_fmaf(th[1], gy, rn_mul(th[0], gx)), th[2]);
-    const float T1 = rn_add(__builtin_fmaf(th[4], gy, rn_mul(th[3], gx)), th[5]);
-    float t = rn_add(__builtin_fmaf(th[7], gy, rn_mul(th[6], gx)), th[8]);
-    t = rn_add(t, rn_mul(1e-6f, (fabsf(t) >= 1e-7f) ? 0.0f : 1.0f));
-    const float xs = rn_div(T0, t), ys = rn_div(T1, t);
-    const float x = rn_mul(rn_mul(rn_add(xs, 1.0f), (float)W), 0.5f);
-    const float y = rn_mul(rn_mul(rn_add(ys, 1.0f), (float)H), 0.5f);
-    const int xf = f2i_x86(floorf(x)), yf = f2i_x86(floorf(y));
-    const int x0 = clampi(xf, 0, W - 1), x1 = clampi((int)((unsigned)xf + 1u), 0, W - 1);
-    const int y0 = clampi(yf, 0, H - 1), y1 = clampi((int)((unsigned)yf + 1u), 0, H - 1);
-    const float x0f = (float)x0, x1f = (float)x1, y0f = (float)y0, y1f = (float)y1;
-    const float ax = rn_sub(x1f, x), bx = rn_sub(x, x0f), ay = rn_sub(y1f, y), by = rn_sub(y, y0f);
-    // ---- the integer taps are constants; the nudge has derivative 1 ----
-    const float* g = gb + size_t(pix) * C;
+    const WarpPoint p = warp_point(th, i, j, H, W);
+    // the integer taps are constants; the nudge has derivative 1.  Taps a, b, c, d of the forward are nw, sw, ne, se; its weights wa .. wd are
+    // ax ay, ax by, bx ay, bx by, so (ax, bx, ay, by) stand where a sampler has (e, w, s, n).  Every tap is clamped into the plane and kept.
+    const Taps t = {p.y0 * W + p.x0, p.y0 * W + p.x1, p.y1 * W + p.x0, p.y1 * W + p.x1, true, true, true, true, p.ax, p.bx, p.ay, p.by};
     float sx = 0.f, sy = 0.f;  // sum over channels of gout * d out / d x, d out / d y
-    for (int c = 0; c < C; ++c) {
-      const float go = g[c];
-      if (part) {
-        const float* pl = im + c * HW;
-        const float Ia = pl[y0 * W + x0], Ib = pl[y1 * W + x0], Ic = pl[y0 * W + x1], Id = pl[y1 * W + x1];
-        const float dx = rn_add(rn_mul(rn_sub(Ic, Ia), ay), rn_mul(rn_sub(Id, Ib), by));
-        const float dy = rn_add(rn_mul(rn_sub(Ib, Ia), ax), rn_mul(rn_sub(Id, Ic), bx));
-        sx = rn_add(sx, rn_mul(go, dx));
-        sy = rn_add(sy, rn_mul(go, dy));
-      }
-      if (gi) {
-        float* pl = gi + c * HW;
-        atomicAdd(pl + y0 * W + x0, rn_mul(go, rn_mul(ax, ay)));  // wa
-        atomicAdd(pl + y1 * W + x0, rn_mul(go, rn_mul(ax, by)));  // wb
-        atomicAdd(pl + y0 * W + x1, rn_mul(go, rn_mul(bx, ay)));  // wc
-        atomicAdd(pl + y1 * W + x1, rn_mul(go, rn_mul(bx, by)));  // wd
-      }
-    }
+    channels_bwd(t, im, gi, HW, gb + size_t(pix) * C, 1, C, part != nullptr, sx, sy);
     if (part) {
       // x = (xs + 1) W / 2, xs = T0 / t:  d x / d T0 = (W/2) / t,  d x / d t = -(W/2) xs / t
       const float gxs = rn_mul(sx, rn_mul((float)W, 0.5f)), gys = rn_mul(sy, rn_mul((float)H, 0.5f));
-      const float g0 = rn_div(gxs, t), g1 = rn_div(gys, t);
-      const float g2 = -rn_div(rn_add(rn_mul(gxs, xs), rn_mul(gys, ys)), t);
+      const float g0 = rn_div(gxs, p.t), g1 = rn_div(gys, p.t);
+      const float g2 = -rn_div(rn_add(rn_mul(gxs, p.xs), rn_mul(gys, p.ys)), p.t);
       // T_r = theta[3r] gx + theta[3r+1] gy + theta[3r+2]
-      acc[0] = rn_add(acc[0], rn_mul(g0, gx)); acc[1] = rn_add(acc[1], rn_mul(g0, gy)); acc[2] = rn_add(acc[2], g0);
-      acc[3] = rn_add(acc[3], rn_mul(g1, gx)); acc[4] = rn_add(acc[4], rn_mul(g1, gy)); acc[5] = rn_add(acc[5], g1);
-      acc[6] = rn_add(acc[6], rn_mul(g2, gx)); acc[7] = rn_add(acc[7], rn_mul(g2, gy)); acc[8] = rn_add(acc[8], g2);
+      acc[0] = rn_add(acc[0], rn_mul(g0, p.gx)); acc[1] = rn_add(acc[1], rn_mul(g0, p.gy)); acc[2] = rn_add(acc[2], g0);
+      acc[3] = rn_add(acc[3], rn_mul(g1, p.gx)); acc[4] = rn_add(acc[4], rn_mul(g1, p.gy)); acc[5] = rn_add(acc[5], g1);
+      acc[6] = rn_add(acc[6], rn_mul(g2, p.gx)); acc[7] = rn_add(acc[7], rn_mul(g2, p.gy)); acc[8] = rn_add(acc[8], g2);
     }
   }
   if (part) block_sum_store<9>(acc, red, part + (size_t(b) * gridDim.x + blockIdx.x) * 9);  // kernel-uniform branch
@@ -264,29 +147,15 @@ int hdn_logpolar_sample_bwd_f32(const float* img, const float* polar, const floa
   if (B <= 0 || C <= 0 || H <= 1 || W <= 1 || S <= 0 || (!grad_polar_or_null && !grad_img_or_null)) return HDN_E_SHAPE;
   if (B > 65535 || (long long)H * W > (1LL << 30) || (long long)S * S > (1LL << 30)) return HDN_E_LIMIT;
   const long long img_floats = (long long)B * C * H * W, out_floats = (long long)B * C * S * S;
-  float* part = nullptr;
-  if (grad_polar_or_null) {
-    const int rc = check_workspace(workspace, workspace_bytes, hdn_logpolar_sample_bwd_workspace_bytes(B, S), img, img_floats * 4, grad_out,
-                                   out_floats * 4);
-    if (rc) return rc;
-    part = workspace;
-  }
-  const float* ins[8] = {img, polar, rho, cos_theta, sin_theta, grad_out, part, grad_img_or_null};
-  if (gbwd::aliases(grad_polar_or_null, ins, 8) || gbwd::aliases(grad_img_or_null, ins, 7)) return HDN_E_ALIAS;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (grad_img_or_null) {
-    const int rc = gbwd::zero_fill(grad_img_or_null, img_floats, st);
-    if (rc) return rc;
-  }
   const int nblk = cdiv(S * S, HDN_BLOCK);
-  hipLaunchKernelGGL(gbwd::logpolar_bwd_kernel, dim3(nblk, B), dim3(HDN_BLOCK), 0, st, img, polar, rho, cos_theta, sin_theta, grad_out, part,
-                     grad_img_or_null, C, H, W, S);
-  if (part) {
-    // d px / d polar_x = (W/2) / (H//2), d py / d polar_y = (H/2) / (W//2): the forward's (sic) pairing
-    const float fx = (float)W * 0.5f / (float)(H / 2), fy = (float)H * 0.5f / (float)(W / 2);
-    hipLaunchKernelGGL(gbwd::reduce_partials_kernel<2>, dim3(B), dim3(HDN_WAVE), 0, st, part, grad_polar_or_null, nblk, fx, fy);
-  }
-  return launch_status();
+  // d px / d polar_x = (W/2) / (H//2), d py / d polar_y = (H/2) / (W//2): the forward's (sic) pairing
+  const float fx = (float)W * 0.5f / (float)(H / 2), fy = (float)H * 0.5f / (float)(W / 2);
+  return gbwd::sampler_bwd<2>({img, polar, rho, cos_theta, sin_theta, grad_out}, img_floats, out_floats, grad_polar_or_null, grad_img_or_null,
+                              workspace, workspace_bytes, hdn_logpolar_sample_bwd_workspace_bytes(B, S), nblk, B, fx, fy, st, [&](float* part) {
+                                hipLaunchKernelGGL(gbwd::logpolar_bwd_kernel, dim3(nblk, B), dim3(HDN_BLOCK), 0, st, img, polar, rho, cos_theta,
+                                                   sin_theta, grad_out, part, grad_img_or_null, C, H, W, S);
+                              });
 }
 
 int hdn_dlt_solve_bwd_f32(const float* src, const float* off, const float* grad_H, float* grad_src_or_null, float* grad_off_or_null, int B,
@@ -309,23 +178,13 @@ int hdn_warp_bwd_f32(const float* img, const float* theta, const float* grad_out
   if (B <= 0 || C <= 0 || H <= 1 || W <= 1 || (!grad_theta_or_null && !grad_img_or_null)) return HDN_E_SHAPE;
   if (B > 65535 || (long long)H * W > (1LL << 30) || (long long)C * H * W > 0x7fffffffLL) return HDN_E_LIMIT;
   const long long img_floats = (long long)B * C * H * W;
-  float* part = nullptr;
-  if (grad_theta_or_null) {
-    const int rc = check_workspace(workspace, workspace_bytes, hdn_warp_bwd_workspace_bytes(B, H, W), img, img_floats * 4, grad_out, img_floats * 4);
-    if (rc) return rc;
-    part = workspace;
-  }
-  const float* ins[5] = {img, theta, grad_out, part, grad_img_or_null};
-  if (gbwd::aliases(grad_theta_or_null, ins, 5) || gbwd::aliases(grad_img_or_null, ins, 4)) return HDN_E_ALIAS;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (grad_img_or_null) {
-    const int rc = gbwd::zero_fill(grad_img_or_null, img_floats, st);
-    if (rc) return rc;
-  }
   const int nblk = cdiv(H * W, WARP_PX_PER_BLOCK);
-  hipLaunchKernelGGL(gbwd::warp_bwd_kernel, dim3(nblk, B), dim3(HDN_BLOCK), 0, st, img, theta, grad_out, part, grad_img_or_null, C, H, W);
-  if (part) hipLaunchKernelGGL(gbwd::reduce_partials_kernel<9>, dim3(B), dim3(HDN_WAVE), 0, st, part, grad_theta_or_null, nblk, 1.0f, 1.0f);
-  return launch_status();
+  return gbwd::sampler_bwd<9>({img, theta, grad_out}, img_floats, img_floats, grad_theta_or_null, grad_img_or_null, workspace, workspace_bytes,
+                              hdn_warp_bwd_workspace_bytes(B, H, W), nblk, B, 1.0f, 1.0f, st, [&](float* part) {
+                                hipLaunchKernelGGL(gbwd::warp_bwd_kernel, dim3(nblk, B), dim3(HDN_BLOCK), 0, st, img, theta, grad_out, part,
+                                                   grad_img_or_null, C, H, W);
+                              });
 }
 
 }  // extern "C"

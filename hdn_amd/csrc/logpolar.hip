@@ -8,7 +8,8 @@
 //   g = (rho*cos + polar) / (size//2);  p = (g + 1) * (size/2) - 0.5;  p = min(size-1, max(p, 0));
 //   w = p - floor(p), e = 1 - w (same for rows: n, s);  nw = s*e, ne = s*w, sw = n*e, se = n*w;
 //   east / south taps beyond the last index are masked;  out = nw*I_nw + ne*I_ne + sw*I_sw + se*I_se.
-#include "hdn_common.h"
+// Everything up to the taps is logpolar_point of geometry.h, which the backward (geometry_bwd.hip) calls too.
+#include "geometry.h"
 
 // The reference's CPU kernels round after every multiply and add here: rn_mul/rn_add/rn_sub/rn_div (hdn_common.h) are
 // compiled with contraction off; fusion is spelled out with __builtin_fmaf where the reference fuses.
@@ -25,27 +26,15 @@ __global__ __launch_bounds__(HDN_BLOCK) void logpolar_kernel(const float* __rest
   const int n = blockIdx.y;
   const int pix = blockIdx.x * HDN_BLOCK + threadIdx.x;
   if (pix >= S * S) return;
-  const int a = pix / S, b = pix - a * S;  // a = angle row, b = log-radius column
-  const float r = rho[b];
-  // logpolar.py:112-116: the x coordinate is divided by sz[2]//2 (= H//2), the y coordinate by sz[3]//2 (= W//2)
-  const float gx = rn_div(rn_add(rn_mul(r, cosT[a]), polar[2 * n]), (float)(H / 2));
-  const float gy = rn_div(rn_add(rn_mul(r, sinT[a]), polar[2 * n + 1]), (float)(W / 2));
+  const LogpolarPoint p = logpolar_point(polar, rho, cosT, sinT, n, pix, H, W, S);
   if (grid) {
     float* g = grid + (size_t(n) * S * S + pix) * 2;
-    g[0] = gx;
-    g[1] = gy;
+    g[0] = p.gx;
+    g[1] = p.gy;
   }
-  float px = rn_sub(rn_mul(rn_add(gx, 1.0f), rn_mul((float)W, 0.5f)), 0.5f);
-  float py = rn_sub(rn_mul(rn_add(gy, 1.0f), rn_mul((float)H, 0.5f)), 0.5f);
-  px = fminf((float)(W - 1), fmaxf(0.0f, px));  // NaN -> 0, as the reference's clamp order does
-  py = fminf((float)(H - 1), fmaxf(0.0f, py));
-  const float xw = floorf(px), yn = floorf(py);
-  const float w = rn_sub(px, xw), e = rn_sub(1.0f, w);
-  const float nn = rn_sub(py, yn), s = rn_sub(1.0f, nn);
-  const float nw = rn_mul(s, e), ne = rn_mul(s, w), sw = rn_mul(nn, e), se = rn_mul(nn, w);
-  const int x0 = (int)xw, y0 = (int)yn;
-  const bool e_ok = x0 + 1 < W, s_ok = y0 + 1 < H;
-  const int x1 = e_ok ? x0 + 1 : x0, y1 = s_ok ? y0 + 1 : y0;
+  const float nw = rn_mul(p.s, p.e), ne = rn_mul(p.s, p.w), sw = rn_mul(p.nn, p.e), se = rn_mul(p.nn, p.w);
+  const int x0 = p.x0, y0 = p.y0, x1 = p.x1, y1 = p.y1;
+  const bool e_ok = p.e_ok, s_ok = p.s_ok;
   const size_t HW = size_t(H) * W;
   const float* im = img + size_t(n) * C * HW;
   float* o = out + size_t(n) * C * S * S + pix;

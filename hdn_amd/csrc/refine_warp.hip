@@ -17,33 +17,13 @@
 // PARITY UNPINNED: without cv2 there is no reference output to hold this against; oracle/hdn_oracle.py carries the same
 // restatement in numpy and the tests compare the two (and check the properties that do not depend on OpenCV: identity,
 // integer shifts, border replication, the 1/32-pixel quantisation).  It lives behind its own entry point for that reason.
-#include "hdn_common.h"
+// The walk itself (inverse, block geometry, rounding, taps) is cv_warp.h, shared with the 8-bit warp of frame.hip; the float
+// weights and the sum are here.
+#include "cv_warp.h"
 
 #pragma clang fp contract(off)
 
 namespace hdn {
-
-__device__ __forceinline__ void inv3_f64(const double* m, double* o) {
-  // adjugate / determinant, as cv::invert does for 3x3 (DECOMP_LU special case)
-  const double d = m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
-  const double id = d != 0.0 ? 1.0 / d : 0.0;
-  o[0] = (m[4] * m[8] - m[5] * m[7]) * id;
-  o[1] = (m[2] * m[7] - m[1] * m[8]) * id;
-  o[2] = (m[1] * m[5] - m[2] * m[4]) * id;
-  o[3] = (m[5] * m[6] - m[3] * m[8]) * id;
-  o[4] = (m[0] * m[8] - m[2] * m[6]) * id;
-  o[5] = (m[2] * m[3] - m[0] * m[5]) * id;
-  o[6] = (m[3] * m[7] - m[4] * m[6]) * id;
-  o[7] = (m[1] * m[6] - m[0] * m[7]) * id;
-  o[8] = (m[0] * m[4] - m[1] * m[3]) * id;
-}
-
-__device__ __forceinline__ int cv_round_sat(double v) {
-  v = fmax(-2147483648.0, fmin(2147483647.0, v));
-  return (int)rint(v);  // round half to even, as cvRound (lrint) does
-}
-
-constexpr int RW_BW = 64, RW_BH = 16;  // OpenCV's block walk for a 127 x 127 INTER_LINEAR warp (BLOCK_SZ 32)
 
 // H[B,9] (fp32, what DLT_solve returned) -> per sample: H_hm = fp32(inv(H) / inv(H)[2,2]); M = fp32(inv(H_hm)) is what
 // the reference hands to cv2; cv2 inverts it again in float64.  warped = sampler(search, M); Hcomp <- Hcomp @ H_hm (fp64).
@@ -77,19 +57,10 @@ __global__ __launch_bounds__(HDN_BLOCK) void refine_warp_kernel(const float* __r
   float* ob = out + size_t(b) * H * W;
   for (int pix = blockIdx.x * HDN_BLOCK + threadIdx.x; pix < H * W; pix += gridDim.x * HDN_BLOCK) {
     const int y = pix / W, x = pix - y * W;
-    const int bx = (x / bw) * bw, x1 = x - bx;
-    const double X0 = mi[0] * bx + mi[1] * y + mi[2];
-    const double Y0 = mi[3] * bx + mi[4] * y + mi[5];
-    const double W0 = mi[6] * bx + mi[7] * y + mi[8];
-    double Wd = W0 + mi[6] * x1;
-    Wd = Wd != 0.0 ? 32.0 / Wd : 0.0;
-    const int X = cv_round_sat((X0 + mi[0] * x1) * Wd), Y = cv_round_sat((Y0 + mi[3] * x1) * Wd);
-    const int sx = X >> 5, sy = Y >> 5;
-    const float fx = (float)(X & 31) * (1.0f / 32.0f), fy = (float)(Y & 31) * (1.0f / 32.0f);
+    const CvPoint p = cv_warp_point(mi, x, y, bw, H, W);
+    const float fx = (float)(p.X & 31) * (1.0f / 32.0f), fy = (float)(p.Y & 31) * (1.0f / 32.0f);
     const float w00 = rn_mul(1.0f - fy, 1.0f - fx), w01 = rn_mul(1.0f - fy, fx), w10 = rn_mul(fy, 1.0f - fx), w11 = rn_mul(fy, fx);
-    const int x0 = min(max(sx, 0), W - 1), x1c = min(max((long long)sx + 1, 0LL), (long long)W - 1);
-    const int y0 = min(max(sy, 0), H - 1), y1c = min(max((long long)sy + 1, 0LL), (long long)H - 1);
-    const float v00 = im[y0 * W + x0], v01 = im[y0 * W + x1c], v10 = im[y1c * W + x0], v11 = im[y1c * W + x1c];
+    const float v00 = im[p.y0 * W + p.x0], v01 = im[p.y0 * W + p.x1], v10 = im[p.y1 * W + p.x0], v11 = im[p.y1 * W + p.x1];
     ob[pix] = rn_add(rn_add(rn_add(rn_mul(v00, w00), rn_mul(v01, w01)), rn_mul(v10, w10)), rn_mul(v11, w11));
   }
 }
@@ -102,12 +73,9 @@ extern "C" int hdn_refine_warp_f32(const float* H_mat, const float* search, floa
   if (B <= 0 || H <= 0 || W <= 0) return HDN_E_SHAPE;
   if (B > 65535 || (long long)H * W > (1LL << 30)) return HDN_E_LIMIT;
   if (warped == search) return HDN_E_ALIAS;
-  // OpenCV's block geometry (imgwarp.cpp, WarpPerspectiveInvoker): BLOCK_SZ = 32
-  int bh = H < 16 ? H : 16;
-  int bw = 1024 / bh < W ? 1024 / bh : W;
-  bh = 1024 / bw < H ? 1024 / bw : H;
+  const hdn::CvBlock blk = hdn::cv_block(H, W);
   const int blocks = hdn::cdiv(H * W, HDN_BLOCK);
   hipLaunchKernelGGL(hdn::refine_warp_kernel, dim3(blocks < 64 ? blocks : 64, B), dim3(HDN_BLOCK), 0,
-                     static_cast<hipStream_t>(stream), H_mat, search, warped, H_comp_or_null, H, W, bw, bh);
+                     static_cast<hipStream_t>(stream), H_mat, search, warped, H_comp_or_null, H, W, blk.bw, blk.bh);
   return hdn::launch_status();
 }

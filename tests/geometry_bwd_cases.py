@@ -65,7 +65,7 @@ def logpolar_rs(x, polar, tabs, dtype=torch.float64):
 
 
 def logpolar_coords(polar, tabs, H, W, dtype):
-    """The unclamped pixel position (pxu, pyu) [B,S,S] of every sample by the statements of logpolar_kernel, each op rounded in `dtype`."""
+    """The unclamped pixel position (pxu, pyu) [B,S,S] of every sample by the statements of logpolar_point (csrc/geometry.h), each op rounded in `dtype`."""
     rho, c, s = (t.to(dtype) for t in tabs)
     p = polar.detach().to(dtype)
     B = p.shape[0]
@@ -313,7 +313,7 @@ def transformer_rs(U, theta, dtype=torch.float64):
 
 
 def warp_coords(theta, B, H, W, dtype):
-    """(gx, gy [HW]; t, xs, ys, x, y [B,HW]) by the statements of warp_pixel, each op rounded in `dtype`."""
+    """(gx, gy [HW]; t, xs, ys, x, y [B,HW]) by the statements of warp_point (csrc/geometry.h), each op rounded in `dtype`."""
     gx = torch.linspace(-1.0, 1.0, W).unsqueeze(0).expand(H, W).reshape(-1)
     gy = torch.linspace(-1.0, 1.0, H).unsqueeze(1).expand(H, W).reshape(-1)
     grid = torch.stack([gx, gy, torch.ones_like(gx)], dim=0).to(dtype)

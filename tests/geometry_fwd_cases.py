@@ -50,16 +50,16 @@ SOURCE_FACTS = (
     ("geometry.h", "constexpr int WARP_PX_PER_BLOCK = HDN_BLOCK * WARP_PX_PER_THREAD;"),
     ("dlt_warp.hip", f"constexpr int L1_THREADS = {L1_THREADS}, L1_PER_THREAD = {L1_PER_THREAD};"),
     ("dlt_warp.hip", "base += L1_THREADS * L1_PER_THREAD"), ("dlt_warp.hip", "min(base + q * L1_THREADS + (int)threadIdx.x, n - 1)"),
-    ("dlt_warp.hip", f"const int groups_per_block = HDN_BLOCK / {DLT_LANES};"), ("dlt_warp.hip", f"__shfl_xor(best, m, {DLT_LANES})"),
+    ("dlt_warp.hip", f"const int groups_per_block = HDN_BLOCK / {DLT_LANES};"), ("geometry.h", f"__shfl_xor(best, m, {DLT_LANES})"),
     ("dlt_warp.hip", "const int r = lane & %d;" % (DLT_LANES - 1)), ("dlt_warp.hip", "dim3 grid(hdn::cdiv(H * W, hdn::WARP_PX_PER_BLOCK), B);"),
-    ("dlt_warp.hip", "if (ob > best || (ob == best && oi < bidx))"), ("dlt_warp.hip", "if (v > best) { best = v; p = r; }"),
-    ("dlt_warp.hip", "(fabsf(t) >= 1e-7f) ? 0.0f : 1.0f"), ("dlt_warp.hip", "return fabsf(t) > 1e-7f;"),
+    ("geometry.h", "if (ob > best || (ob == best && oi < bidx))"), ("dlt_warp.hip", "if (v > best) { best = v; p = r; }"),
+    ("geometry.h", "(fabsf(t) >= 1e-7f) ? 0.0f : 1.0f"), ("dlt_warp.hip", "return fabsf(p.t) > 1e-7f;"),
     ("geometry.h", "return p == 2 ? 3 : (p == 3 ? 2 : p);"), ("geometry.h", "(f >= -2147483648.0f && f < 2147483648.0f) ? (int)f : (int)0x80000000"),
     ("logpolar.hip", "dim3 grid(hdn::cdiv(S * S, HDN_BLOCK), B);"), ("logpolar.hip", "(e_ok && s_ok) ? pl[y1 * W + x1] : 0.f"),
-    ("refine_warp.hip", f"constexpr int RW_BW = {RW_BW}, RW_BH = {RW_BH};"),
-    ("refine_warp.hip", f"int bh = H < {RW_BH} ? H : {RW_BH};"),
-    ("refine_warp.hip", f"int bw = {RW_BW * RW_BH} / bh < W ? {RW_BW * RW_BH} / bh : W;"),
-    ("refine_warp.hip", f"bh = {RW_BW * RW_BH} / bw < H ? {RW_BW * RW_BH} / bw : H;"),
+    ("cv_warp.h", f"constexpr int RW_BW = {RW_BW}, RW_BH = {RW_BH};"),
+    ("cv_warp.h", f"int bh = H < {RW_BH} ? H : {RW_BH};"),
+    ("cv_warp.h", f"int bw = {RW_BW * RW_BH} / bh < W ? {RW_BW * RW_BH} / bh : W;"),
+    ("cv_warp.h", f"bh = {RW_BW * RW_BH} / bw < H ? {RW_BW * RW_BH} / bw : H;"),
     ("refine_warp.hip", f"dim3(blocks < {RW_CAP} ? blocks : {RW_CAP}, B)"), ("refine_warp.hip", "pix += gridDim.x * HDN_BLOCK"),
 )
 
@@ -169,7 +169,7 @@ def grid_coord32(n):
 
 
 def warp_xy32(theta, H, W):
-    """(t after the nudge, x, y) [B, H W] in fp32 by the statements of warp_pixel (csrc/dlt_warp.hip), every operation rounded once."""
+    """(t after the nudge, x, y) [B, H W] in fp32 by the statements of warp_point (csrc/geometry.h), every operation rounded once."""
     th = np.asarray(theta, f32).reshape(-1, 9)[:, :, None]
     gx = np.broadcast_to(grid_coord32(W)[None, :], (H, W)).reshape(1, -1)
     gy = np.broadcast_to(grid_coord32(H)[:, None], (H, W)).reshape(1, -1)
@@ -196,7 +196,7 @@ def _inc32(v):
 
 
 def warp_taps(x, y, H, W):
-    """The clamped tap indices (x0, x1, y0, y1) that warp_pixel forms from fp32 coordinates: floor, f2i_x86, + 1, clamp."""
+    """The clamped tap indices (x0, x1, y0, y1) that warp_point forms from fp32 coordinates: floor, f2i_x86, + 1, clamp."""
     with np.errstate(all="ignore"):
         xf, yf = f2i_x86(np.floor(x)), f2i_x86(np.floor(y))
     return np.clip(xf, 0, W - 1), np.clip(_inc32(xf), 0, W - 1), np.clip(yf, 0, H - 1), np.clip(_inc32(yf), 0, H - 1)
@@ -537,7 +537,7 @@ N_LOGPOLAR_EXACT = len(LOGPOLAR_EXACT) + len(LOGPOLAR_DYADIC)
 
 
 def logpolar_grid32(polar, tabs, H, W):
-    """The two statements of logpolar_kernel that form the grid, in numpy fp32: [B,S,S,2]."""
+    """The two statements of logpolar_point (csrc/geometry.h) that form the grid, in numpy fp32: [B,S,S,2]."""
     rho, c, s = (t.numpy().astype(f32) for t in tabs)
     p = polar.numpy().astype(f32)
     gx = ((rho[None, None, :] * c[None, :, None]).astype(f32) + p[:, 0, None, None]).astype(f32) / f32(H // 2)
