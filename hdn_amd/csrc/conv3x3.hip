@@ -19,8 +19,8 @@
 // (consecutive in (b, y, x) order: whole image rows) x BN output channels.
 //   LDS A image: the tile's input pixels with a one-pixel halo (zeros outside the image), one K chunk of 16 * KS input channels at
 //                a time, as [piece][k step][k half][pixel] x 16 B: an MFMA A fragment (lane = (pixel row i, k half g), 8 fp16) is
-//                one ds_read_b128 and a tap is a constant address offset; conflict-free through the row / image pitches of Cfg and
-//                the lane -> pixel order of mrow_to_pixel().  Two images (double buffer).
+//                one ds_read_b128 and a tap is a constant address offset; conflict-free through the row / image pitches of HaloImage
+//                and the lane -> pixel order of mrow_to_pixel() (conv3x3_tile.h).  Two images (double buffer).
 //   LDS W image: [tap of the stage][k step][piece][k half][cout] x 16 B, one STAGE = one kernel row (3 taps) of one chunk, a ring
 //                of three stages, streamed from the host-packed layout (which is exactly this order).
 //   pipeline   : the producers run two stages ahead of the consumers (weights in registers two more stages ahead of that); the
@@ -31,6 +31,7 @@
 #include <type_traits>
 #include <utility>
 
+#include "conv3x3_tile.h"
 #include "hdn_common.h"
 #include "mfma_split.h"
 
@@ -61,67 +62,31 @@ namespace hdn {
 namespace cv {
 using namespace hdn::mc;
 
-// vector types, the MFMA, the fp32 -> two-fp16-piece split (x = p0 + 2^-11 p1) and static_for: mfma_split.h
+// vector types, the MFMA, the fp32 -> two-fp16-piece split (x = p0 + 2^-11 p1) and static_for: mfma_split.h; the A image, an item's
+// split-and-store, the accumulator tile -> LDS step and the LDS tile -> NHWC walk: conv3x3_tile.h
 
 // S = OUTPUT side, CI -> CO channels, STRIDE 1 or 2 (input side S * STRIDE); DS: the block's 1x1 / stride-2 downsample branch is
 // computed alongside from the same staged activations (it is the centre tap with its own weights) into a second output.
+// The A image and the lane -> pixel order of mrow_to_pixel(): HaloImage, conv3x3_tile.h.
 template <int S_, int CI_, int CO_, int STRIDE_, bool DS_, int WM_, int WN_, int MT_, int NT_, int KS_>
-struct Cfg {
-  static constexpr int S = S_, CI = CI_, CO = CO_, STRIDE = STRIDE_, WM = WM_, WN = WN_, MT = MT_, NT = NT_, KS = KS_;
+struct Cfg : HaloImage<S_, STRIDE_, WM_ * MT_ * 32, KS_> {
+  using Img = HaloImage<S_, STRIDE_, WM_ * MT_ * 32, KS_>;
+  static constexpr int CI = CI_, CO = CO_, WM = WM_, WN = WN_, MT = MT_, NT = NT_;
   static constexpr bool DS = DS_;
-  static constexpr int SI = S * STRIDE;
-  static constexpr int BM = WM * MT * 32, BN = WN * NT * 32;
+  static constexpr int BN = WN * NT * 32;
   static_assert(WM * WN == 4, "4 waves per workgroup");
-  static_assert(STRIDE == 1 || STRIDE == 2, "stride");
-  static_assert(CO % BN == 0 && CI % (16 * KS) == 0, "channel blocking");
-  static_assert((BM % S == 0) && ((S * S) % BM == 0 || BM % (S * S) == 0), "a tile is whole rows of one image, or whole images");
-  static constexpr int IMGS = BM > S * S ? BM / (S * S) : 1;      // images per tile
-  static constexpr int R = BM / (S * IMGS);                      // output rows per image in the tile
-  static constexpr int PWV = SI + 2, PH = STRIDE == 1 ? R + 2 : 2 * R + 1;  // halo'ed input patch
-  // Pitches of the LDS image.  A ds_read_b128 is served in groups of 16 lanes ({0-3,12-15,20-27}, {4-11,16-19,28-31} of a half
-  // wave), which must fall on 16 different 16-byte columns of the 256-byte bank row.  With image rows shorter than 16 pixels that
-  // takes a row pitch of 12 pixels at S = 8 and an image pitch of 40 at S = 4, together with the lane -> pixel order of
-  // mrow_to_pixel() below (40 % of the LDS cycles of those stages were bank conflicts before).
-  static constexpr int PW = (STRIDE == 1 && S == 8) ? 12 : PWV;
-  static constexpr int IPITCH = PH * PW + ((STRIDE == 1 && S == 4) ? 4 : 0);
-  // ... and the producers' ds_write_b128 (8 consecutive lanes = 8 / (2 KS) pixels x the 2 KS (k step, k half) sub-images of a pixel, one
-  // 128-byte bank row) needs the sub-images 128 / (2 KS) bytes apart modulo 128: LP = 8 / (2 KS) modulo 8.
-  static constexpr int LPV = IMGS * IPITCH;                      // LDS pixels that exist
-  static constexpr int LP = LPV + ((8 / (2 * KS) - LPV % 8) + 8) % 8;
-  static constexpr int NP = 2;                                   // fp16 pieces per value
-  static constexpr int KG_BYTES = LP * 16, KSTEP_BYTES = 2 * KG_BYTES, PIECE_BYTES = KS * KSTEP_BYTES, A_BYTES = NP * PIECE_BYTES;
-  static constexpr int WKG_BYTES = BN * 16, WPIECE_BYTES = 2 * WKG_BYTES, WSTEP_BYTES = NP * WPIECE_BYTES;   // one (tap, k step)
+  static_assert(CO % BN == 0 && CI % (16 * Img::KS) == 0, "channel blocking");
+  static constexpr int WKG_BYTES = BN * 16, WPIECE_BYTES = 2 * WKG_BYTES, WSTEP_BYTES = Img::NP * WPIECE_BYTES;   // one (tap, k step)
   static constexpr int NTAP = DS ? 4 : 3;                        // taps of a stage: a kernel row (+ the downsample tap, used in the middle row)
-  static constexpr int WSTAGE_BYTES = NTAP * KS * WSTEP_BYTES;   // one kernel row of one chunk
-  static constexpr int EPI_STRIDE = BN + 4;                      // floats per pixel row of the output staging (pad: bank spread of the two half waves)
-  static constexpr int EPI_BYTES = BM * EPI_STRIDE * 4;
-  static constexpr int LDS_BYTES = (2 * A_BYTES + 3 * WSTAGE_BYTES) > EPI_BYTES ? (2 * A_BYTES + 3 * WSTAGE_BYTES) : EPI_BYTES;   // two A images, a ring of three W stages
+  static constexpr int WSTAGE_BYTES = NTAP * Img::KS * WSTEP_BYTES;   // one kernel row of one chunk
+  static constexpr int EPI_STRIDE = epi_stride(BN);
+  static constexpr int EPI_BYTES = Img::BM * EPI_STRIDE * 4;
+  static constexpr int LDS_BYTES = (2 * Img::A_BYTES + 3 * WSTAGE_BYTES) > EPI_BYTES ? (2 * Img::A_BYTES + 3 * WSTAGE_BYTES) : EPI_BYTES;   // two A images, a ring of three W stages
   static_assert(LDS_BYTES <= 160 * 1024, "tile does not fit the LDS");
-  static constexpr int NCHUNK = CI / (16 * KS), NB = CO / BN, NSTAGE = 3 * NCHUNK;
+  static constexpr int NCHUNK = CI / (16 * Img::KS), NB = CO / BN, NSTAGE = 3 * NCHUNK;
   static constexpr int W4 = WSTAGE_BYTES / 16;                   // 16-byte words of one stage's weights
   static constexpr int WITER = cdiv(W4, HDN_BLOCK);
-  static constexpr int AITEMS = LP * 2 * KS, AITER = cdiv(AITEMS, HDN_BLOCK);   // (pixel, k step, k half) items of 8 channels
 };
-
-// Row i (0..31) of an MFMA tile -> pixel of the tile's 32-pixel block, (image, y, x) order.  Stride-1 tiles with rows shorter than
-// 32 pixels hand the two 16-lane access groups of a fragment read pixel sets that are 16 distinct columns of the bank row:
-// group = which of the two, k = rank inside it; S = 16: group = row; S = 8: rows (0, 2) | (1, 3); S = 4: even | odd rows of two images.
-template <int S>
-__host__ __device__ constexpr __forceinline__ int mrow_to_pixel_s1(int i) {   // stride-1 tiles of side S
-  if constexpr (S >= 32) {
-    return i;
-  } else {
-    const int q = i >> 2, grp = (0x96 >> q) & 1, k = ((q >> 1) << 2) | (i & 3);
-    if constexpr (S == 16) return grp * 16 + k;
-    else if constexpr (S == 8) return (2 * (k >> 3) + grp) * 8 + (k & 7);
-    else return (k >> 3) * 16 + (2 * ((k >> 2) & 1) + grp) * 4 + (k & 3);
-  }
-}
-template <class Cf>
-__host__ __device__ constexpr __forceinline__ int mrow_to_pixel(int i) {
-  if constexpr (Cf::STRIDE != 1) return i;
-  else return mrow_to_pixel_s1<Cf::S>(i);
-}
 
 // A convolution input that was never written out as an activation (B = 1: every launch is a dependent step of ~5 us, and the
 // launch that only adds the K slices up was half of them): the raw K-slice sums [zx][B][SI][SI][CI] of the convolution that
@@ -192,11 +157,7 @@ __global__ __launch_bounds__(2 * HDN_BLOCK) void conv3x3_kernel(const float* __r
   // ---- per-lane LDS byte offsets: A fragments of this wave's M tiles (centre tap), B fragments of its N tiles
   uint32_t aoff[MT];
 #pragma unroll
-  for (int mt = 0; mt < MT; ++mt) {
-    const int i = (wm * MT + mt) * 32 + mrow_to_pixel<Cf>(li);   // pixel inside the tile
-    const int img = i / (Cf::R * S), yy = (i / S) % Cf::R, xx = i % S;
-    aoff[mt] = lds_addr(sA) + g * Cf::KG_BYTES + (img * Cf::IPITCH + (ST * yy + 1) * Cf::PW + (ST * xx + 1)) * 16;
-  }
+  for (int mt = 0; mt < MT; ++mt) aoff[mt] = lds_addr(sA) + Cf::aoff((wm * MT + mt) * 32 + mrow_to_pixel<Cf>(li), g, 1);
   const uint32_t boff = lds_addr(sW) + g * Cf::WKG_BYTES + (wn * NT * 32 + li) * 16;
 
   f32x16 acc[MT][NT], accl[MT][NT];        // hi: x0 w0; lo: x0 w1 + x1 w0 (scaled by 2^11)
@@ -242,10 +203,9 @@ __global__ __launch_bounds__(2 * HDN_BLOCK) void conv3x3_kernel(const float* __r
     for (int q = 0; q < Cf::AITER; ++q) {
       const int item = tid + q * HDN_BLOCK;
       const int px = min(item / (2 * KS), Cf::LP - 1), sub = item % (2 * KS);
-      const int img = px / Cf::IPITCH, ry = (px % Cf::IPITCH) / Cf::PW, rx = px % Cf::IPITCH % Cf::PW;   // (pad pixels: zeros)
-      const int b = b0 + img, y = ST * y0 + ry - 1, xx = rx - 1;
-      const bool ok = item < Cf::AITEMS && img < Cf::IMGS && b < B && ry < Cf::PH && y >= 0 && y < SI && xx >= 0 && xx < SI;
-      const f4* src = reinterpret_cast<const f4*>(x + (((size_t)b * SI + y) * SI + xx) * CI + (chunk0 + chunk) * (16 * KS) + sub * 8);
+      const auto s = Cf::source(px, b0, y0, B);                       // (halo and pad pixels: zeros)
+      const bool ok = item < Cf::AITEMS && s.ok;
+      const f4* src = reinterpret_cast<const f4*>(x + s.pix * CI + (chunk0 + chunk) * (16 * KS) + sub * 8);
       av[q][0] = ok ? src[0] : f4{0.f, 0.f, 0.f, 0.f};
       av[q][1] = ok ? src[1] : f4{0.f, 0.f, 0.f, 0.f};
     }
@@ -255,14 +215,7 @@ __global__ __launch_bounds__(2 * HDN_BLOCK) void conv3x3_kernel(const float* __r
 #pragma unroll
     for (int q = 0; q < Cf::AITER; ++q) {
       const int item = tid + q * HDN_BLOCK;
-      if (item < Cf::AITEMS) {
-        const int px = item / (2 * KS), sub = item % (2 * KS);   // sub = k step * 2 + k half
-        u32x4 p0, p1;
-        split8<SD>(av[q][0], av[q][1], p0, p1);
-        unsigned char* dst = sA + ab * Cf::A_BYTES + sub * Cf::KG_BYTES + px * 16;
-        *reinterpret_cast<u32x4*>(dst) = p0;
-        *reinterpret_cast<u32x4*>(dst + Cf::PIECE_BYTES) = p1;
-      }
+      if (item < Cf::AITEMS) split_store<Cf, SD>(av[q][0], av[q][1], sA + ab * Cf::A_BYTES + Cf::item_off(item / (2 * KS), item % (2 * KS)));
     }
   };
 
@@ -277,13 +230,11 @@ __global__ __launch_bounds__(2 * HDN_BLOCK) void conv3x3_kernel(const float* __r
     for (int it = threadIdx.x; it < nchunk * Cf::AITEMS; it += 2 * HDN_BLOCK) {
       const int chunk = it / Cf::AITEMS, item = it % Cf::AITEMS;
       const int px = item / (2 * KS), sub = item % (2 * KS);
-      const int img = px / Cf::IPITCH, ry = (px % Cf::IPITCH) / Cf::PW, rx = px % Cf::IPITCH % Cf::PW;
-      const int b = b0 + img, y = ST * y0 + ry - 1, xx = rx - 1;
-      const bool ok = img < Cf::IMGS && b < B && ry < Cf::PH && y >= 0 && y < SI && xx >= 0 && xx < SI;
+      const auto s = Cf::source(px, b0, y0, B);
       f4 s0 = f4{0.f, 0.f, 0.f, 0.f}, s1 = s0;
-      if (ok) {
+      if (s.ok) {
         const int ch = (chunk0 + chunk) * (16 * KS) + sub * 8;
-        const size_t off = (((size_t)b * SI + y) * SI + xx) * CI + ch;
+        const size_t off = s.pix * CI + ch;
         const f4 b0v = *reinterpret_cast<const f4*>(lz.bias + ch), b1v = *reinterpret_cast<const f4*>(lz.bias + ch + 4);
         f4 r0 = s0, r1 = s0;
         if (lz.res) sum_slices(lz.res + off, MX, lz.zr, r0, r1);
@@ -291,16 +242,12 @@ __global__ __launch_bounds__(2 * HDN_BLOCK) void conv3x3_kernel(const float* __r
         s0 = s0 + b0v; s1 = s1 + b1v;
         if (lz.res) { s0 = s0 + r0; s1 = s1 + r1; }
         s0 = relu4(s0); s1 = relu4(s1);
-        if (lz.xout && nb == 0 && ry >= 1 && ry <= Cf::PH - (ST == 1 ? 2 : 1)) {   // the tile's own input rows (not the halo)
+        if (lz.xout && nb == 0 && s.ry >= 1 && s.ry <= Cf::PH - (ST == 1 ? 2 : 1)) {   // the tile's own input rows (not the halo)
           *reinterpret_cast<f4*>(lz.xout + off) = s0;
           *reinterpret_cast<f4*>(lz.xout + off + 4) = s1;
         }
       }
-      u32x4 p0, p1;
-      split8<SD>(s0, s1, p0, p1);
-      unsigned char* dst = sA + chunk * Cf::A_BYTES + sub * Cf::KG_BYTES + px * 16;
-      *reinterpret_cast<u32x4*>(dst) = p0;
-      *reinterpret_cast<u32x4*>(dst + Cf::PIECE_BYTES) = p1;
+      split_store<Cf, SD>(s0, s1, sA + chunk * Cf::A_BYTES + Cf::item_off(px, sub));
     }
   }
 
@@ -444,71 +391,35 @@ __global__ __launch_bounds__(2 * HDN_BLOCK) void conv3x3_kernel(const float* __r
   __syncthreads();  // every wave is done with the A / W images
   HDN_ABL_CONV3X3_7()
   float* const sO = reinterpret_cast<float*>(smem);
-  // (the pixel of accumulator row d_row(r, g) is a compile-time constant for each of the two half waves: one multiply-add per store instead of
-  //  the mapping's dozen integer operations - round 5)
-  if (consume) {
-    float* const obase = sO + wm * MT * 32 * Cf::EPI_STRIDE + wn * NT * 32 + li;
-    static_for<MT>([&](auto MTc) {
-      static_for<16>([&](auto Rc) {
-        constexpr int mt = decltype(MTc)::value, r = decltype(Rc)::value, i0 = d_row(r);
-        constexpr int row0 = mt * 32 + mrow_to_pixel<Cf>(i0), row1 = mt * 32 + mrow_to_pixel<Cf>(i0 + 4);
-        float* const q = obase + (row0 + g * (row1 - row0)) * Cf::EPI_STRIDE;
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) q[nt * 32] = join<SD>(acc[mt][nt][r], accl[mt][nt][r]);
-      });
-    });
-  }
+  auto tile_to_lds = [&](const auto& hi, const auto& lo) {
+    if (consume) acc_to_lds<mrow_to_pixel<Cf>, SD, Cf::EPI_STRIDE>(hi, lo, sO + wm * MT * 32 * Cf::EPI_STRIDE + wn * NT * 32 + li, g);
+  };
+  tile_to_lds(acc, accl);
   __syncthreads();
   constexpr int ETHREADS = 2 * HDN_BLOCK;   // every thread of the workgroup stores
-  const int etid = threadIdx.x;
-  constexpr int N4 = BN / 4, TOT4 = BM * N4, EITER = cdiv(TOT4, ETHREADS);
-  f4 rv[EITER];
-  if (RES) {
-#pragma unroll
-    for (int q = 0; q < EITER; ++q) {
-      const int idx = etid + q * ETHREADS, px = idx / N4, c4 = idx % N4;
-      const long long m = min(m0 + px, M - 1);
+  f4 rv[tile_iters(BM, BN, ETHREADS)];
+  if (RES)
+    for_tile_items<BM, BN, ETHREADS, true>(threadIdx.x, m0, M, [&](int q, int, int c4, long long m) {
       rv[q] = *reinterpret_cast<const f4*>(res + m * C + nb * BN + c4 * 4);
+    });
+  for_tile_items<BM, BN, ETHREADS>(threadIdx.x, m0, M, [&](int q, int px, int c4, long long m) {
+    f4 v = *reinterpret_cast<const f4*>(sO + px * Cf::EPI_STRIDE + c4 * 4);
+    if (PARTIAL) {
+      *reinterpret_cast<f4*>(out + ((long long)blockIdx.z * M + m) * C + nb * BN + c4 * 4) = v;
+    } else {
+      v = v + *reinterpret_cast<const f4*>(bias + nb * BN + c4 * 4);
+      if (RES) v = v + rv[q];
+      *reinterpret_cast<f4*>(out + m * C + nb * BN + c4 * 4) = relu4(v);
     }
-  }
-#pragma unroll
-  for (int q = 0; q < EITER; ++q) {
-    const int idx = etid + q * ETHREADS, px = idx / N4, c4 = idx % N4;
-    const long long m = m0 + px;
-    if (idx < TOT4 && m < M) {
-      f4 v = *reinterpret_cast<const f4*>(sO + px * Cf::EPI_STRIDE + c4 * 4);
-      if (PARTIAL) {
-        *reinterpret_cast<f4*>(out + ((long long)blockIdx.z * M + m) * C + nb * BN + c4 * 4) = v;
-      } else {
-        v = v + *reinterpret_cast<const f4*>(bias + nb * BN + c4 * 4);
-        if (RES) v = v + rv[q];
-        *reinterpret_cast<f4*>(out + m * C + nb * BN + c4 * 4) = relu4(v);
-      }
-    }
-  }
-  if (DS) {   // the downsample branch: raw sums (its bias travels with the block's second convolution)
+  });
+  if constexpr (DS) {   // the downsample branch: raw sums (its bias travels with the block's second convolution)
     __syncthreads();
-    if (consume) {
-      float* const obase = sO + wm * MT * 32 * Cf::EPI_STRIDE + wn * NT * 32 + li;
-      static_for<MT>([&](auto MTc) {
-        static_for<16>([&](auto Rc) {
-          constexpr int mt = decltype(MTc)::value, r = decltype(Rc)::value, i0 = d_row(r);
-          constexpr int row0 = mt * 32 + mrow_to_pixel<Cf>(i0), row1 = mt * 32 + mrow_to_pixel<Cf>(i0 + 4);
-          float* const q = obase + (row0 + g * (row1 - row0)) * Cf::EPI_STRIDE;
-#pragma unroll
-          for (int nt = 0; nt < NT; ++nt) q[nt * 32] = join<SD>(accd[DS ? mt : 0][DS ? nt : 0][r], accdl[DS ? mt : 0][DS ? nt : 0][r]);
-        });
-      });
-    }
+    tile_to_lds(accd, accdl);
     __syncthreads();
-#pragma unroll
-    for (int q = 0; q < EITER; ++q) {
-      const int idx = etid + q * ETHREADS, px = idx / N4, c4 = idx % N4;
-      const long long m = m0 + px;
-      if (idx < TOT4 && m < M)
-        *reinterpret_cast<f4*>(out2 + ((PARTIAL ? (long long)blockIdx.z * M : 0) + m) * C + nb * BN + c4 * 4) =
-            *reinterpret_cast<const f4*>(sO + px * Cf::EPI_STRIDE + c4 * 4);
-    }
+    for_tile_items<BM, BN, ETHREADS>(threadIdx.x, m0, M, [&](int, int px, int c4, long long m) {
+      *reinterpret_cast<f4*>(out2 + ((PARTIAL ? (long long)blockIdx.z * M : 0) + m) * C + nb * BN + c4 * 4) =
+          *reinterpret_cast<const f4*>(sO + px * Cf::EPI_STRIDE + c4 * 4);
+    });
   }
 }
 
@@ -544,15 +455,15 @@ __global__ __launch_bounds__(HDN_BLOCK) void conv3x3_reduce_kernel(const f4* __r
   }
 }
 
-// K slices for a launch: 1 when the output tiles alone fill the chip, else the smallest power of two (dividing the chunk count)
-// that brings the workgroup count to ~one per CU
+// K slices for a launch: 1 when the output tiles alone fill the chip, else the smallest power of two (dividing the chunk count, a slice's
+// chunks whole unrolled periods of `period` chunks) that brings the workgroup count to ~one per CU
+constexpr int SLICE_TARGET = 200;   // (swept, flat from 200 up: profiles/round3_conv3x3.txt, profiles/round4_experiments.txt)
 template <class Cf>
-static int k_slices(int B) {
+static int k_slices(int B, int period = 1) {
   const long long M = (long long)B * Cf::S * Cf::S;
   const long long tiles = ((M + Cf::BM - 1) / Cf::BM) * Cf::NB;
-  static const int target = env_positive("HDN_CV_SLICE_TARGET", 200);  // A/B switch
   int z = 1;
-  while (tiles * z < target && z * 2 <= Cf::NCHUNK && Cf::NCHUNK % (z * 2) == 0) z *= 2;
+  while (tiles * z < SLICE_TARGET && z * 2 <= Cf::NCHUNK && Cf::NCHUNK % (z * 2) == 0 && (Cf::NCHUNK / (z * 2)) % period == 0) z *= 2;
   return z;
 }
 
@@ -567,6 +478,17 @@ template <class Cf>
 static size_t workspace_bytes(int B) {
   const int z = k_slices<Cf>(B);
   return z > 1 ? (size_t)(Cf::DS ? 2 : 1) * z * B * Cf::S * Cf::S * Cf::CO * sizeof(float) : 0;
+}
+
+// out[n] = relu(the z slices' sum + bias (+ the residual's res_slices slices)), C channels; without a bias: the plain sum (a downsample branch)
+static int finish(const float* slices, int z, const float* bias, const float* res, int res_slices, float* out, long long n, int C, hipStream_t stream) {
+  const unsigned n4 = (unsigned)(n / 4);
+  const dim3 grid((n4 + HDN_BLOCK - 1) / HDN_BLOCK < 1024 ? (n4 + HDN_BLOCK - 1) / HDN_BLOCK : 1024), blk(HDN_BLOCK);
+  auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, blk, 0, stream, (const f4*)slices, (const f4*)bias, (const f4*)res, (f4*)out, n4, C / 4, z, res ? res_slices : 1); };
+  if (!bias) go(conv3x3_reduce_kernel<false, false>);
+  else if (res) go(conv3x3_reduce_kernel<true, true>);
+  else go(conv3x3_reduce_kernel<false, true>);
+  return launch_status();
 }
 
 template <class Cf, bool SD = false>
@@ -589,13 +511,8 @@ static int launch(const float* x, const void* wp, const float* bias, const float
   }
   float* ws2 = ws + (size_t)z * M * Cf::CO;
   hipLaunchKernelGGL((conv3x3_kernel<Cf, 2, false, SD>), grid, blk, Cf::LDS_BYTES, stream, x, w4, bias, res, ws, ws2, B, Cf::NCHUNK / z, LazyIn{});
-  const unsigned n4 = (unsigned)(M * Cf::CO / 4);
-  const int blocks = (int)((n4 + HDN_BLOCK - 1) / HDN_BLOCK < 1024 ? (n4 + HDN_BLOCK - 1) / HDN_BLOCK : 1024);
-  const f4* b4 = (const f4*)bias;
-  if (res) hipLaunchKernelGGL((conv3x3_reduce_kernel<true, true>), dim3(blocks), dim3(HDN_BLOCK), 0, stream, (const f4*)ws, b4, (const f4*)res, (f4*)out, n4, Cf::CO / 4, z, 1);
-  else hipLaunchKernelGGL((conv3x3_reduce_kernel<false, true>), dim3(blocks), dim3(HDN_BLOCK), 0, stream, (const f4*)ws, b4, (const f4*)res, (f4*)out, n4, Cf::CO / 4, z, 1);
-  if (Cf::DS) hipLaunchKernelGGL((conv3x3_reduce_kernel<false, false>), dim3(blocks), dim3(HDN_BLOCK), 0, stream, (const f4*)ws2, b4, (const f4*)nullptr, (f4*)out2, n4, Cf::CO / 4, z, 1);
-  return launch_status();
+  if (const int rc = finish(ws, z, bias, res, 1, out, M * Cf::CO, Cf::CO, stream)) return rc;
+  return Cf::DS ? finish(ws2, z, nullptr, nullptr, 0, out2, M * Cf::CO, Cf::CO, stream) : HDN_OK;
 }
 
 // The chained form (small batches): raw K-slice sums out ([z][M][CO], z = k_slices; the downsample branch to out2), whatever z is,
@@ -612,14 +529,6 @@ static int launch_chain(const float* x, const LazyIn& lz, const void* wp, float*
   const u32x4* w4 = (const u32x4*)wp;
   if (lz.zx > 0) hipLaunchKernelGGL((conv3x3_kernel<Cf, 2, true, SD>), grid, blk, Cf::LDS_BYTES, stream, x, w4, nullptr, nullptr, out, out2, B, Cf::NCHUNK / z, lz);
   else hipLaunchKernelGGL((conv3x3_kernel<Cf, 2, false, SD>), grid, blk, Cf::LDS_BYTES, stream, x, w4, nullptr, nullptr, out, out2, B, Cf::NCHUNK / z, LazyIn{});
-  return launch_status();
-}
-
-static int finish(const float* slices, int z, const float* bias, const float* res, int res_slices, float* out, long long n, int C, hipStream_t stream) {
-  const unsigned n4 = (unsigned)(n / 4);
-  const int blocks = (int)((n4 + HDN_BLOCK - 1) / HDN_BLOCK < 1024 ? (n4 + HDN_BLOCK - 1) / HDN_BLOCK : 1024);
-  if (res) hipLaunchKernelGGL((conv3x3_reduce_kernel<true, true>), dim3(blocks), dim3(HDN_BLOCK), 0, stream, (const f4*)slices, (const f4*)bias, (const f4*)res, (f4*)out, n4, C / 4, z, res_slices);
-  else hipLaunchKernelGGL((conv3x3_reduce_kernel<false, true>), dim3(blocks), dim3(HDN_BLOCK), 0, stream, (const f4*)slices, (const f4*)bias, (const f4*)res, (f4*)out, n4, C / 4, z, 1);
   return launch_status();
 }
 
@@ -642,38 +551,29 @@ static int finish(const float* slices, int z, const float* bias, const float* re
 //   * the producers also own the epilogue: they ask for the residual during the last chunk and, once the partial tiles are in LDS,
 //     add them in slice order + bias (+ residual), ReLU, 16-byte NHWC stores.
 template <int S_, int C_, int WM_, int WK_, int KS_, int NT_ = 2, int TPW_ = 1>
-struct Cfg2 {
-  static constexpr int S = S_, C = C_, WM = WM_, WK = WK_, KS = KS_, NT = NT_, TPW = TPW_;
-  static_assert(WM * WK == 4 && KS % WK == 0, "four consumer waves: WM pixel tiles x WK k slices");
+struct Cfg2 : HaloImage<S_, 1, 64 * WM_, KS_> {
+  using Img = HaloImage<S_, 1, 64 * WM_, KS_>;
+  static constexpr int C = C_, WM = WM_, WK = WK_, NT = NT_, TPW = TPW_;
+  static_assert(WM * WK == 4 && Img::KS % WK == 0, "four consumer waves: WM pixel tiles x WK k slices");
   // NT = 1 (32 output channels per workgroup, a 64 x 32 tile per wave, 6 MFMAs per step): twice the workgroups for the 4 x 4 stage, whose
   // 1,024 pixels and 512 channels make 128 tiles of 64 x 64 (round 5 first split its K over two workgroups + a reduction launch instead)
   static_assert(NT == 1 || NT == 2, "n tiles per wave");
-  static constexpr int BM = 64 * WM, BN = 32 * NT, MT = 2, NP = 2;
-  static_assert(C % BN == 0 && C % (16 * KS) == 0, "channel blocking");
-  static_assert((BM % S == 0) && ((S * S) % BM == 0 || BM % (S * S) == 0), "a tile is whole rows of one image, or whole images");
-  static constexpr int IMGS = BM > S * S ? BM / (S * S) : 1;
-  static constexpr int R = BM / (S * IMGS);
-  static constexpr int PWV = S + 2, PH = R + 2;
-  static constexpr int PW = S == 8 ? 12 : PWV;                       // (bank mapping of the fragment reads: see Cfg)
-  static constexpr int IPITCH = PH * PW + (S == 4 ? 4 : 0);
-  static constexpr int LPV = IMGS * IPITCH;
-  static constexpr int LP = LPV + ((8 / (2 * KS) - LPV % 8) + 8) % 8;
-  static constexpr int KG_BYTES = LP * 16, KSTEP_BYTES = 2 * KG_BYTES, PIECE_BYTES = KS * KSTEP_BYTES, A_BYTES = NP * PIECE_BYTES;
-  static constexpr int NCHUNK = C / (16 * KS), NB = C / BN;
-  static constexpr int SPW = KS / WK, NS = 9 * SPW;                  // k steps / steps (tap, k step) of one wave per chunk
+  static constexpr int BN = 32 * NT, MT = 2;
+  static_assert(C % BN == 0 && C % (16 * Img::KS) == 0, "channel blocking");
+  static constexpr int NCHUNK = C / (16 * Img::KS), NB = C / BN;
+  static constexpr int SPW = Img::KS / WK, NS = 9 * SPW;             // k steps / steps (tap, k step) of one wave per chunk
   static constexpr int PER = (NS % 2) ? 2 : 1;                       // chunks per unrolled period (two A register sets)
   // B register sets: a step's fragments travel BSETS - 1 steps ahead.  Half-size steps (NT = 1: 6 MFMAs = 192 clk) need twice the distance.
   static constexpr int BSETS = NT == 2 ? 3 : 6, PF = BSETS - 1;
   static_assert((PER * NS) % BSETS == 0, "the B register sets rotate with the step");
-  static constexpr int WSTEP = NT * NP * 64;                         // 16-byte words of one wave step: [n tile][piece][lane]
+  static constexpr int WSTEP = NT * Img::NP * 64;                    // 16-byte words of one wave step: [n tile][piece][lane]
   static constexpr int WCHUNK = WK * NS * WSTEP;                     // ... of one (channel block, chunk): [k slice][step]
-  static constexpr int EPI_STRIDE = BN + 4;
-  static constexpr int RED_BYTES = WK * BM * EPI_STRIDE * 4;
-  static constexpr int LDS_BYTES = TPW > 1 ? 2 * A_BYTES + RED_BYTES : (2 * A_BYTES > RED_BYTES ? 2 * A_BYTES : RED_BYTES);
+  static constexpr int EPI_STRIDE = epi_stride(BN);
+  static constexpr int RED_BYTES = WK * Img::BM * EPI_STRIDE * 4;
+  static constexpr int LDS_BYTES = TPW > 1 ? 2 * Img::A_BYTES + RED_BYTES : (2 * Img::A_BYTES > RED_BYTES ? 2 * Img::A_BYTES : RED_BYTES);
   static_assert(LDS_BYTES <= 160 * 1024, "tile does not fit the LDS");
-  static_assert(TPW == 1 || (C / (16 * KS)) % 2 == 0, "several tiles per workgroup: an even number of chunks per tile keeps the image parity");
-  static constexpr int AITEMS = LP * 2 * KS, AITER = cdiv(AITEMS, HDN_BLOCK);
-  static constexpr int E4 = BM * (BN / 4), EITER = cdiv(E4, HDN_BLOCK);   // 16-byte output items per tile / per producer thread
+  static_assert(TPW == 1 || NCHUNK % 2 == 0, "several tiles per workgroup: an even number of chunks per tile keeps the image parity");
+  static constexpr int EITER = tile_iters(Img::BM, BN, HDN_BLOCK);   // 16-byte output items per producer thread
 };
 
 // MODE 0: out = relu(conv + bias); 1: out = relu(conv + bias + res); 2: raw sums of the K slice blockIdx.z (`cps` chunks) to out[blockIdx.z][M][C]
@@ -712,10 +612,9 @@ __global__ __launch_bounds__(2 * HDN_BLOCK) void conv3x3_v2_kernel(const float* 
       for (int q = 0; q < Cf::AITER; ++q) {
         const int item = tid + q * HDN_BLOCK;
         const int px = min(item / (2 * KS), Cf::LP - 1), sub = item % (2 * KS);
-        const int img = px / Cf::IPITCH, ry = (px % Cf::IPITCH) / Cf::PW, rx = px % Cf::IPITCH % Cf::PW;   // (pad pixels: zeros)
-        const int b = b0 + img, y = y0 + ry - 1, xx = rx - 1;
-        const bool ok = item < Cf::AITEMS && img < Cf::IMGS && b < B && ry < Cf::PH && y >= 0 && y < S && xx >= 0 && xx < S;
-        const f4* src = reinterpret_cast<const f4*>(x + (((size_t)b * S + y) * S + xx) * C + (chunk0 + chunk) * (16 * KS) + sub * 8);
+        const auto s = Cf::source(px, b0, y0, B);                     // (halo and pad pixels: zeros)
+        const bool ok = item < Cf::AITEMS && s.ok;
+        const f4* src = reinterpret_cast<const f4*>(x + s.pix * C + (chunk0 + chunk) * (16 * KS) + sub * 8);
         av[q][0] = ok ? src[0] : f4{0.f, 0.f, 0.f, 0.f};
         av[q][1] = ok ? src[1] : f4{0.f, 0.f, 0.f, 0.f};
       }
@@ -724,49 +623,31 @@ __global__ __launch_bounds__(2 * HDN_BLOCK) void conv3x3_v2_kernel(const float* 
 #pragma unroll
       for (int q = 0; q < Cf::AITER; ++q) {
         const int item = tid + q * HDN_BLOCK;
-        if (item < Cf::AITEMS) {
-          const int px = item / (2 * KS), sub = item % (2 * KS);
-          u32x4 p0, p1;
-          split8<SD>(av[q][0], av[q][1], p0, p1);
-          unsigned char* dst = smem + ab * Cf::A_BYTES + sub * Cf::KG_BYTES + px * 16;
-          *reinterpret_cast<u32x4*>(dst) = p0;
-          *reinterpret_cast<u32x4*>(dst + Cf::PIECE_BYTES) = p1;
-        }
+        if (item < Cf::AITEMS) split_store<Cf, SD>(av[q][0], av[q][1], smem + ab * Cf::A_BYTES + Cf::item_off(item / (2 * KS), item % (2 * KS)));
       }
     };
     f4 rv[RES ? Cf::EITER : 1];
     auto load_res = [&](int tile) {                        // the residual travels during the tile's last chunk
-      if constexpr (RES) {
-        const long long m0 = (long long)(tile0 + tile) * BM;
-#pragma unroll
-        for (int q = 0; q < Cf::EITER; ++q) {
-          const int idx = tid + q * HDN_BLOCK, px = idx / (BN / 4), c4 = idx % (BN / 4);
-          const long long m = min(m0 + px, M - 1);
+      if constexpr (RES)
+        for_tile_items<BM, BN, HDN_BLOCK, true>(tid, (long long)(tile0 + tile) * BM, M, [&](int q, int, int c4, long long m) {
           rv[q] = *reinterpret_cast<const f4*>(res + m * C + nb * BN + c4 * 4);
-        }
-      }
+        });
     };
     // sum of the WK partial tiles in slice order (+ bias (+ residual), ReLU), a pixel's BN channels = BN / 4 consecutive lanes
     auto epilogue = [&](int tile) {
       HDN_ABL_CONV3X3_8()
-      const long long m0 = (long long)(tile0 + tile) * BM;
+      for_tile_items<BM, BN, HDN_BLOCK>(tid, (long long)(tile0 + tile) * BM, M, [&](int q, int px, int c4, long long m) {
+        f4 v = *reinterpret_cast<const f4*>(red + px * Cf::EPI_STRIDE + c4 * 4);
 #pragma unroll
-      for (int q = 0; q < Cf::EITER; ++q) {
-        const int idx = tid + q * HDN_BLOCK, px = idx / (BN / 4), c4 = idx % (BN / 4);
-        const long long m = m0 + px;
-        if (idx < Cf::E4 && m < M) {
-          f4 v = *reinterpret_cast<const f4*>(red + px * Cf::EPI_STRIDE + c4 * 4);
-#pragma unroll
-          for (int w = 1; w < WK; ++w) v = v + *reinterpret_cast<const f4*>(red + (w * BM + px) * Cf::EPI_STRIDE + c4 * 4);
-          if (PARTIAL) {
-            *reinterpret_cast<f4*>(out + ((long long)blockIdx.z * M + m) * C + nb * BN + c4 * 4) = v;
-          } else {
-            v = v + *reinterpret_cast<const f4*>(bias + nb * BN + c4 * 4);
-            if (RES) v = v + rv[q];
-            *reinterpret_cast<f4*>(out + m * C + nb * BN + c4 * 4) = relu4(v);
-          }
+        for (int w = 1; w < WK; ++w) v = v + *reinterpret_cast<const f4*>(red + (w * BM + px) * Cf::EPI_STRIDE + c4 * 4);
+        if (PARTIAL) {
+          *reinterpret_cast<f4*>(out + ((long long)blockIdx.z * M + m) * C + nb * BN + c4 * 4) = v;
+        } else {
+          v = v + *reinterpret_cast<const f4*>(bias + nb * BN + c4 * 4);
+          if (RES) v = v + rv[q];
+          *reinterpret_cast<f4*>(out + m * C + nb * BN + c4 * 4) = relu4(v);
         }
-      }
+      });
     };
     load_a(0);
     store_a(0);
@@ -796,11 +677,8 @@ __global__ __launch_bounds__(2 * HDN_BLOCK) void conv3x3_v2_kernel(const float* 
   const int wm = wave / WK, wk = wave % WK;
   uint32_t aoff[2];
 #pragma unroll
-  for (int mt = 0; mt < 2; ++mt) {
-    const int i = (wm * 2 + mt) * 32 + mrow_to_pixel_s1<S>(li);       // pixel inside the workgroup's tile
-    const int img = i / (Cf::R * S), yy = (i / S) % Cf::R, xx = i % S;
-    aoff[mt] = lds_addr(smem) + g * Cf::KG_BYTES + wk * Cf::KSTEP_BYTES + (img * Cf::IPITCH + yy * Cf::PW + xx) * 16;   // top-left tap, k step wk (+ WK j)
-  }
+  for (int mt = 0; mt < 2; ++mt)   // top-left tap, k step wk (+ WK j)
+    aoff[mt] = lds_addr(smem) + wk * Cf::KSTEP_BYTES + Cf::aoff((wm * 2 + mt) * 32 + mrow_to_pixel_s1<S>(li), g, 0);
   constexpr int NT = Cf::NT, PF = Cf::PF;
   f32x16 acc[2][NT], accl[2][NT];
 
@@ -907,19 +785,8 @@ __global__ __launch_bounds__(2 * HDN_BLOCK) void conv3x3_v2_kernel(const float* 
     }
     // ---- this wave's partial tile -> LDS.  One tile per workgroup: over the images (every consumer has passed the last chunk's barrier after
     // its last read); several: into their own region, which the producers emptied during this tile's first chunk.
-    // The pixel of accumulator row d_row(r, g) is a compile-time constant for each of the two half waves: one multiply-add per store, not the
-    // mapping's dozen integer operations.
     HDN_ABL_CONV3X3_14_BEGIN
-    float* const rbase = red + (wk * BM + wm * 64) * Cf::EPI_STRIDE + li;
-    static_for<2>([&](auto MTc) {
-      static_for<16>([&](auto Rc) {
-        constexpr int mt = decltype(MTc)::value, r = decltype(Rc)::value, i0 = d_row(r);
-        constexpr int row0 = mt * 32 + mrow_to_pixel_s1<S>(i0), row1 = mt * 32 + mrow_to_pixel_s1<S>(i0 + 4);
-        float* const q = rbase + (row0 + g * (row1 - row0)) * Cf::EPI_STRIDE;
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) q[nt * 32] = join<SD>(acc[mt][nt][r], accl[mt][nt][r]);
-      });
-    });
+    acc_to_lds<mrow_to_pixel_s1<S>, SD, Cf::EPI_STRIDE>(acc, accl, red + (wk * BM + wm * 64) * Cf::EPI_STRIDE + li, g);
     HDN_ABL_CONV3X3_14_END
     __syncthreads();                                   // the tile's partial sums are in LDS (the producers take them from there)
   }
@@ -928,13 +795,13 @@ __global__ __launch_bounds__(2 * HDN_BLOCK) void conv3x3_v2_kernel(const float* 
 
 template <class Cf>
 static int k_slices_v2(int B) {
-  const long long M = (long long)B * Cf::S * Cf::S;
-  if (Cf::TPW > 1) return 1;       // (several tiles per workgroup: the launch is long enough as it is)
-  const long long tiles = ((M + Cf::BM - 1) / Cf::BM) * Cf::NB;
-  static const int target = env_positive("HDN_CV2_SLICE_TARGET", 200);  // A/B switch
-  int z = 1;
-  while (tiles * z < target && (Cf::NCHUNK / (z * 2)) % Cf::PER == 0 && Cf::NCHUNK % (z * 2) == 0 && z * 2 <= Cf::NCHUNK) z *= 2;
-  return z;
+  return Cf::TPW > 1 ? 1 : k_slices<Cf>(B, Cf::PER);   // (several tiles per workgroup: the launch is long enough as it is)
+}
+
+template <class Cf>
+static size_t workspace_bytes_v2(int B) {
+  const int z = k_slices_v2<Cf>(B);
+  return z > 1 ? (size_t)z * B * Cf::S * Cf::S * Cf::C * sizeof(float) : 0;
 }
 
 template <class Cf, bool SD = false>
@@ -944,7 +811,7 @@ static int launch_v2(const float* x, const void* wp, const float* bias, const fl
   const int z = k_slices_v2<Cf>(B);
   if (z > 1) {
     if (!ws) return HDN_E_NULL;
-    if (ws_bytes < (size_t)z * M * Cf::C * sizeof(float) || !aligned16(ws)) return HDN_E_LIMIT;
+    if (ws_bytes < workspace_bytes_v2<Cf>(B) || !aligned16(ws)) return HDN_E_LIMIT;
   }
   static PerDeviceOnce attr;
   if (const int rc = lds_opt_in(attr, Cf::LDS_BYTES, &conv3x3_v2_kernel<Cf, 0, SD>, &conv3x3_v2_kernel<Cf, 1, SD>, &conv3x3_v2_kernel<Cf, 2, SD>)) return rc;
@@ -1060,16 +927,13 @@ extern "C" int hdn_conv3x3s2_ds_f32(const float* x, const void* wpacked, const f
 // ---- round 5: the large-batch form (conv3x3_v2_kernel).                  S    C  WM WK KS
 using CV2_L1 = hdn::cv::Cfg2<32, 64, 2, 2, 2, 2, 2>;   // 2 tiles of 128 pixels (4 rows) x 64 channels per workgroup, two k slices, chunks of 32 channels
 using CV2_L2 = hdn::cv::Cfg2<16, 128, 1, 4, 4, 2, 2>;  // 2 tiles of 64 pixels (4 rows), four k slices, chunks of 64 channels
-using CV2_L1S = hdn::cv::Cfg2<32, 64, 4, 1, 2>;        // (HDN_CV2_TPW=1: one tile of 256 pixels (8 rows) per workgroup, chunks of 32 channels)
-using CV2_L2S = hdn::cv::Cfg2<16, 128, 2, 2, 4>;       // (HDN_CV2_TPW=1: one tile of 128 pixels (8 rows), two k slices, chunks of 64 channels)
 using CV2_L3 = hdn::cv::Cfg2<8, 256, 1, 4, 4>;    // 64 pixels (one image), four k slices
 using CV2_L4 = hdn::cv::Cfg2<4, 512, 1, 4, 4, 1>; // 64 pixels (four images) x 32 channels, four k slices: 256 workgroups at B = 64, no K split over workgroups
 
 template <class F>
 static int cv2_dispatch(int S, int C, F&& f) {
-  static const bool single = [] { const char* e = getenv("HDN_CV2_TPW"); return e && atoi(e) == 1; }();   // A/B switch
-  if (S == 32 && C == 64) return single ? f(CV2_L1S{}) : f(CV2_L1{});
-  if (S == 16 && C == 128) return single ? f(CV2_L2S{}) : f(CV2_L2{});
+  if (S == 32 && C == 64) return f(CV2_L1{});
+  if (S == 16 && C == 128) return f(CV2_L2{});
   if (S == 8 && C == 256) return f(CV2_L3{});
   if (S == 4 && C == 512) return f(CV2_L4{});
   return HDN_E_LIMIT;
@@ -1088,9 +952,7 @@ extern "C" long long hdn_conv3x3_v2_workspace_bytes(int B, int S, int C) {
   if (B <= 0) return HDN_E_SHAPE;
   long long out = 0;
   const int rc = cv2_dispatch(S, C, [&](auto cfg) {
-    using Cf = decltype(cfg);
-    const int z = hdn::cv::k_slices_v2<Cf>(B);
-    out = z > 1 ? (long long)z * B * Cf::S * Cf::S * Cf::C * (long long)sizeof(float) : 0;
+    out = (long long)hdn::cv::workspace_bytes_v2<decltype(cfg)>(B);
     return HDN_OK;
   });
   return rc == HDN_OK ? out : rc;

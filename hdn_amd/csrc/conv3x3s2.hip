@@ -17,6 +17,7 @@
 #include <type_traits>
 #include <utility>
 
+#include "conv3x3_tile.h"
 #include "hdn_common.h"
 #include "mfma_split.h"
 
@@ -53,7 +54,7 @@ struct Image {
   static constexpr int IPITCH = PH * PW, LPV = IMGS * IPITCH;
   static constexpr int LP = LPV + (4 - LPV % 16 + 16) % 16;          // = 4 mod 16: the four k groups a staging pass writes land on distinct banks
   static constexpr int KG_BYTES = LP * 16, KSTEP_BYTES = 2 * KG_BYTES, PIECE_BYTES = KS * KSTEP_BYTES, A_BYTES = 2 * PIECE_BYTES;
-  static constexpr int EPI_STRIDE = BN + 4;
+  static constexpr int EPI_STRIDE = epi_stride(BN);
   // byte offset in an image of tile pixel p's tap (0, 0) = padded (2 yy, 2 xx), k half g (MFMA row = lane & 31: p = 32 x the wave's pixel half + li)
   static __device__ __forceinline__ int aoff(int p, int g) {
     const int img = p / (R * SO), yy = (p / SO) % R, xx = p % SO;
@@ -103,13 +104,7 @@ struct Stager {
   __device__ __forceinline__ void store_a(unsigned char* image, SetC = {}) {
 #pragma unroll
     for (int q = 0; q < AITER; ++q) {
-      if (tid + q * HDN_BLOCK < AITEMS) {
-        u32x4 p0, p1;
-        split8<SD>(av[SetC::value][q][0], av[SetC::value][q][1], p0, p1);
-        unsigned char* dst = image + a_dst[q];
-        *reinterpret_cast<u32x4*>(dst) = p0;
-        *reinterpret_cast<u32x4*>(dst + Cf::PIECE_BYTES) = p1;
-      }
+      if (tid + q * HDN_BLOCK < AITEMS) split_store<Cf, SD>(av[SetC::value][q][0], av[SetC::value][q][1], image + a_dst[q]);
     }
   }
 };
@@ -137,8 +132,6 @@ struct CfgS : s2::Image<SO_, 2> {
   static constexpr int RED_BYTES = 2 * RED_FLOATS * 4;
   static constexpr int LDS_BYTES = 2 * Img::A_BYTES > RED_BYTES ? 2 * Img::A_BYTES : RED_BYTES;
   static_assert(LDS_BYTES <= 160 * 1024 && 2 * Img::A_BYTES < 65536 * 2, "LDS");
-  static constexpr int E4 = Img::BM * (Img::BN / 4), EITER = E4 / HDN_BLOCK;
-  static_assert(E4 % HDN_BLOCK == 0, "epilogue items");
 };
 
 template <class Cf, bool SD = false>
@@ -185,18 +178,13 @@ __global__ __launch_bounds__(2 * HDN_BLOCK) void conv3x3s2_v2_kernel(const float
     for (int o = 0; o < 2; ++o) {
       const float* const rd = red + o * Cf::RED_FLOATS;
       float* const dst = o ? out_ds : out;
+      for_tile_items<BM, BN, HDN_BLOCK>(tid, m0, M, [&](int, int px, int c4, long long m) {
+        f4 v = *reinterpret_cast<const f4*>(rd + px * Cf::EPI_STRIDE + c4 * 4);
 #pragma unroll
-      for (int q = 0; q < Cf::EITER; ++q) {
-        const int idx = tid + q * HDN_BLOCK, px = idx / (BN / 4), c4 = idx % (BN / 4);
-        const long long m = m0 + px;
-        if (m < M) {
-          f4 v = *reinterpret_cast<const f4*>(rd + px * Cf::EPI_STRIDE + c4 * 4);
-#pragma unroll
-          for (int w = 1; w < WK; ++w) v = v + *reinterpret_cast<const f4*>(rd + (w * BM + px) * Cf::EPI_STRIDE + c4 * 4);
-          if (o == 0) v = relu4(v + *reinterpret_cast<const f4*>(bias + nb * BN + c4 * 4));
-          *reinterpret_cast<f4*>(dst + m * CO + nb * BN + c4 * 4) = v;
-        }
-      }
+        for (int w = 1; w < WK; ++w) v = v + *reinterpret_cast<const f4*>(rd + (w * BM + px) * Cf::EPI_STRIDE + c4 * 4);
+        if (o == 0) v = relu4(v + *reinterpret_cast<const f4*>(bias + nb * BN + c4 * 4));
+        *reinterpret_cast<f4*>(dst + m * CO + nb * BN + c4 * 4) = v;
+      });
     }
     return;
   }
@@ -368,7 +356,6 @@ struct CfgB : s2::Image<SO_, 2> {
   static constexpr int RED_BYTES = Img::BM * Img::EPI_STRIDE * 4;
   static constexpr int LDS_BYTES = Img::A_BYTES > RED_BYTES ? Img::A_BYTES : RED_BYTES;
   static_assert(LDS_BYTES <= 64 * 1024, "static LDS");
-  static constexpr int EITER = Img::BM * (Img::BN / 4) / HDN_BLOCK;
 };
 
 // the K slices of a problem: ZC slices of the chunks x ZT (1 or 3) of the kernel rows
@@ -458,16 +445,11 @@ __global__ __launch_bounds__(HDN_BLOCK) void conv3x3s2_kernel(const float* __res
   for (int r = 0; r < 16; ++r) red[(wm * 32 + d_row(r, g)) * Cf::EPI_STRIDE + wn * 32 + li] = join<SD>(hi[r], lo[r]);
   __syncthreads();
   float* const o = FUSED ? dst : dst + (size_t)z * (size_t)M * C;
-#pragma unroll
-  for (int q = 0; q < Cf::EITER; ++q) {
-    const int idx = tid + q * HDN_BLOCK, px = idx / (BN / 4), c4 = idx % (BN / 4);
-    const long long m = m0 + px;
-    if (m < M) {
-      f4 v = *reinterpret_cast<const f4*>(red + px * Cf::EPI_STRIDE + c4 * 4);
-      if constexpr (FUSED) v = relu4(v + *reinterpret_cast<const f4*>(bias + nb * BN + c4 * 4));
-      *reinterpret_cast<f4*>(o + m * C + nb * BN + c4 * 4) = v;
-    }
-  }
+  for_tile_items<BM, BN, HDN_BLOCK>(tid, m0, M, [&](int, int px, int c4, long long m) {
+    f4 v = *reinterpret_cast<const f4*>(red + px * Cf::EPI_STRIDE + c4 * 4);
+    if constexpr (FUSED) v = relu4(v + *reinterpret_cast<const f4*>(bias + nb * BN + c4 * 4));
+    *reinterpret_cast<f4*>(o + m * C + nb * BN + c4 * 4) = v;
+  });
 }
 
 template <class Cf>

@@ -1,7 +1,8 @@
 // What every two-fp16-piece matrix-core kernel of this library shares (conv3x3.hip, conv3x3s2.hip, conv3x3d.hip, conv1x1.hip, head_conv.hip, head_tail.hip,
 // trunk_stem_mfma.hip, simi_stem.hip; epilogue.hip takes the activation scale from here): the vector types of v_mfma_f32_32x32x16_f16's operands, the
 // instruction itself and its C/D layout, the fp32 -> two-piece split (of a pair, of eight values), the register-staged chunk step,
-// the join, a compile-time loop and the entry points' dispatch on the activation domain.
+// the join, a compile-time loop and the entry points' dispatch on the activation domain.  (What only the trunk's 3x3 kernels share - the halo'ed LDS
+// image, the split-and-store of a staged item, the accumulator tile -> LDS step, the LDS tile -> NHWC walk - is conv3x3_tile.h, on top of this header.)
 //
 // fp32 value x is carried as x = p0 + 2^-11 p1 with p0 = fp16(x) and p1 = fp16((x - p0) * 2^11) (round-to-nearest-even by v_cvt_pk_f16_f32 each; the
 // residual x - p0 is exact in fp32 and so is its product with 2^11): |x - (p0 + 2^-11 p1)| <= 2^-23 |x|.  A product of two such values is accumulated
