@@ -11,7 +11,11 @@
 // used as SGPR pair operands of 8 v_pk_fma_f32 (two output channels per instruction, the input value broadcast by op_sel).
 // Pooling: vertical v_max3 over the three conv rows, horizontal v_max3 with the two neighbour lanes (DPP wave shifts; lanes
 // outside the row hold 0, which never wins after the ReLU and every window has a real element), even lanes store.
-// Zero padding is selected (v_cndmask), never multiplied in: non-finite pixels stay where the reference has them.
+// Zero padding is selected (v_cndmask), never multiplied in: a non-finite pixel reaches only the outputs whose receptive field holds
+// it (rows outside the image re-read row 0 and the last lane of an odd width re-reads column W-2: both are dropped by the select).
+// Inside that field +-inf under non-zero weights gives what the reference gives; a NaN (a NaN pixel, or inf times a zero weight) does
+// not: fmaxf(NaN, 0) = 0 behind the ReLU and the pool's fmaxf drops a NaN, where PyTorch answers NaN (docs/PARITY.md;
+// tests/test_gpu_trunk_stem.py asserts no value there).
 // fp32 throughout; the summation order is (input channel, input row, kx) per output - not MIOpen's, same 1e-5 relative class.
 #include <cstdlib>
 #include <type_traits>
