@@ -9,6 +9,7 @@ from .share_feature import PreShareFeature, PreShareFeatureTrain, fold_params  #
 from .homo_model import HomoModelBuilder, track_proj  # noqa: F401
 from .logpolar import STN_Polar, STN_PolarTrain, logpolar_sample_backward  # noqa: F401
 from .affine import affine_sample, affine_sample_backward  # noqa: F401
+from .triplet import TripletMarginLossL1, triplet_l1, triplet_l1_backward  # noqa: F401
 from .heads import MultiBAN, MultiCircBAN  # noqa: F401
 from .refine import homo_refine, refine_warp  # noqa: F401
 

@@ -143,6 +143,8 @@ SIGNATURES = {
     "hdn_affine_sample_f32": (_i, [_c_float_p] * 3 + [_i] * 6 + [ctypes.c_void_p]),
     "hdn_affine_sample_bwd_workspace_bytes": (ctypes.c_longlong, [_i] * 3),
     "hdn_affine_sample_bwd_f32": (_i, [_c_float_p] * 6 + [ctypes.c_longlong] + [_i] * 6 + [ctypes.c_void_p]),
+    "hdn_triplet_l1_f32": (_i, [_c_float_p] * 5 + [_i] * 4 + [ctypes.c_float] * 2 + [ctypes.c_void_p]),
+    "hdn_triplet_l1_bwd_f32": (_i, [_c_float_p] * 8 + [_i] * 4 + [ctypes.c_float] * 2 + [ctypes.c_void_p]),
 }
 
 ERRORS = {

@@ -1,0 +1,163 @@
+// L1 triplet margin loss over rows for gfx950, forward and backward: hdn_triplet_l1_f32, hdn_triplet_l1_bwd_f32.  The formulas are in
+// include/hdn_hip.h.  Reference: nn.TripletMarginLoss(margin=1.0, p=1, reduce=False, size_average=False) on three [n,1,127,127] ShareFeature maps
+// that were gathered by x[ids] just before (model_builder_e2e_unconstrained_v2.py:438, homo_model_builder.py:197): F.pairwise_distance adds eps to the
+// difference inside the absolute value, the loss is clamp_min((margin + d_ap) - d_an, 0).
+//
+// One wave per row, HDN_BLOCK / HDN_WAVE = 4 rows per workgroup.  A row of the reference is 127 floats and only 4-byte aligned, so lane l reads the
+// dwords l, l + 64, ... of the three rows (coalesced, no wider access anywhere) and the two distances are reduced by a xor butterfly, which leaves the
+// same sum in every lane.  The call is three reads of a 2 MB tensor at B = 32: launch and latency, not bandwidth; 3048 waves at 24 x 127 rows.
+//
+// The gather is folded into the addressing: with `ids`, row r of the result is row r % R of sample ids[r / R]; no gathered copy exists.  The sample
+// index is checked against [0, N) before any address is formed: an index outside gives NaN loss rows and takes no part in the backward.
+//
+// The backward walks the full-size gradient rows (one wave per row of [N,R,D]): the wave looks its sample up in `ids` (lanes scan the list in strides
+// of 64, the lowest matching position wins: ids are unique by contract, and a repeated one would otherwise be a race), recomputes v with row_v() - the
+// forward's own function, so the decision v >= 0 is made on the forward's bits - and writes g sgn(.) per element, or zeros for a row that is not
+// selected or not active.  Every gradient element is written exactly once by one lane: no atomics, no zero-fill pass, bit-reproducible.
+#include "hdn_common.h"
+
+#pragma clang fp contract(off)
+
+namespace hdn {
+namespace triplet {
+
+constexpr int ROWS = HDN_BLOCK / HDN_WAVE;  // rows per workgroup
+
+// |(x - y) + eps|: the subtraction rounded, then the add, as the two fp32 elementwise kernels of F.pairwise_distance do
+__device__ __forceinline__ float term(float x, float y, float eps) { return fabsf(rn_add(rn_sub(x, y), eps)); }
+
+__device__ __forceinline__ float sgn(float x) { return x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f); }  // sgn(0) = 0; NaN -> 0
+
+// v = (margin + d_ap) - d_an of one row, the same value in every lane of the wave.  Lane l adds the elements l, l + 64, ... in ascending order, then
+// the butterfly adds the 64 partial sums.  The forward and the backward both call it.
+__device__ __forceinline__ float row_v(const float* __restrict__ a, const float* __restrict__ p, const float* __restrict__ n, int D, int lane,
+                                       float margin, float eps) {
+  float d_ap = 0.f, d_an = 0.f;
+  for (int j = lane; j < D; j += HDN_WAVE) {
+    const float av = a[j], pv = p[j], nv = n[j];
+    d_ap = rn_add(d_ap, term(av, pv, eps));
+    d_an = rn_add(d_an, term(av, nv, eps));
+  }
+#pragma unroll
+  for (int m = HDN_WAVE / 2; m >= 1; m >>= 1) {
+    d_ap = rn_add(d_ap, __shfl_xor(d_ap, m, HDN_WAVE));
+    d_an = rn_add(d_an, __shfl_xor(d_an, m, HDN_WAVE));
+  }
+  return rn_sub(rn_add(margin, d_ap), d_an);
+}
+
+__global__ __launch_bounds__(HDN_BLOCK) void fwd_kernel(const float* __restrict__ a, const float* __restrict__ p, const float* __restrict__ n,
+                                                        const long long* __restrict__ ids, float* __restrict__ loss, int N, int R, int D,
+                                                        long long rows, float margin, float eps) {
+  const int lane = threadIdx.x & (HDN_WAVE - 1);
+  const long long row = (long long)blockIdx.x * ROWS + (threadIdx.x / HDN_WAVE);
+  if (row >= rows) return;                                   // wave-uniform
+  const long long k = row / R;
+  const int rr = (int)(row - k * R);
+  const long long s = ids ? ids[k] : k;
+  float out = __builtin_nanf("");
+  if (s >= 0 && s < N) {                                     // checked before any address is formed
+    const size_t off = (size_t(s) * R + rr) * size_t(D);
+    const float v = row_v(a + off, p + off, n + off, D, lane, margin, eps);
+    out = v < 0.f ? 0.f : v;                                 // clamp_min: v >= 0 and NaN pass
+  }
+  if (lane == 0) loss[row] = out;
+}
+
+__global__ __launch_bounds__(HDN_BLOCK) void bwd_kernel(const float* __restrict__ a, const float* __restrict__ p, const float* __restrict__ n,
+                                                        const long long* __restrict__ ids, const float* __restrict__ gl, float* __restrict__ ga,
+                                                        float* __restrict__ gp, float* __restrict__ gn, int N, int R, int D, int n_ids,
+                                                        float margin, float eps) {
+  const int lane = threadIdx.x & (HDN_WAVE - 1);
+  const long long row = (long long)blockIdx.x * ROWS + (threadIdx.x / HDN_WAVE);
+  if (row >= (long long)N * R) return;                       // wave-uniform
+  const long long s = row / R;
+  const int rr = (int)(row - s * R);
+  long long k = s;                                           // position of sample s in the result; -1: not selected
+  if (ids) {
+    k = -1;
+    for (int base = 0; base < n_ids && k < 0; base += HDN_WAVE) {
+      const int q = base + lane;
+      const bool hit = q < n_ids && ids[q] == s;
+      const unsigned long long m = __ballot(hit);
+      if (m) k = base + (__ffsll((long long)m) - 1);
+    }
+  }
+  const size_t off = size_t(row) * size_t(D);
+  bool active = false;
+  float g = 0.f;
+  if (k >= 0) {
+    active = row_v(a + off, p + off, n + off, D, lane, margin, eps) >= 0.f;   // clamp_min's rule: the gradient passes at exactly 0, not at NaN
+    g = gl[size_t(k) * R + rr];
+  }
+  if (!active) {                                             // wave-uniform
+    for (int j = lane; j < D; j += HDN_WAVE) {
+      if (ga) ga[off + j] = 0.f;
+      if (gp) gp[off + j] = 0.f;
+      if (gn) gn[off + j] = 0.f;
+    }
+    return;
+  }
+  for (int j = lane; j < D; j += HDN_WAVE) {
+    const float av = a[off + j];
+    const float s_ap = sgn(rn_add(rn_sub(av, p[off + j]), eps)), s_an = sgn(rn_add(rn_sub(av, n[off + j]), eps));
+    if (ga) ga[off + j] = rn_mul(g, rn_sub(s_ap, s_an));     // g {0, +-1, +-2}: exact
+    if (gp) gp[off + j] = rn_mul(-g, s_ap);
+    if (gn) gn[off + j] = rn_mul(g, s_an);
+  }
+}
+
+static int check_dims(const long long* ids, int N, int R, int D, int n_ids) {
+  if (N <= 0 || R <= 0 || D <= 0 || (ids && n_ids <= 0)) return HDN_E_SHAPE;
+  return HDN_OK;
+}
+
+static bool over_limit(const long long* ids, int N, int R, int D, int n_ids) {
+  return (long long)N * R > (1LL << 30) || (ids && (long long)n_ids * R > (1LL << 30)) || D > (1 << 20);
+}
+
+}  // namespace triplet
+}  // namespace hdn
+
+extern "C" {
+
+int hdn_triplet_l1_f32(const float* anchor, const float* positive, const float* negative, const long long* ids_or_null, float* loss, int N, int R,
+                       int D, int n_ids, float margin, float eps, void* stream) {
+  using namespace hdn;
+  if (!anchor || !positive || !negative || !loss) return HDN_E_NULL;
+  if (triplet::check_dims(ids_or_null, N, R, D, n_ids)) return HDN_E_SHAPE;
+  if (triplet::over_limit(ids_or_null, N, R, D, n_ids)) return HDN_E_LIMIT;
+  const long long rows = (long long)(ids_or_null ? n_ids : N) * R, in_bytes = (long long)N * R * D * 4, out_bytes = rows * 4;
+  for (const float* in : {anchor, positive, negative})
+    if (bytes_overlap(loss, out_bytes, in, in_bytes)) return HDN_E_ALIAS;
+  if (ids_or_null && bytes_overlap(loss, out_bytes, ids_or_null, (long long)n_ids * 8)) return HDN_E_ALIAS;
+  hipLaunchKernelGGL(triplet::fwd_kernel, dim3((unsigned)((rows + triplet::ROWS - 1) / triplet::ROWS)), dim3(HDN_BLOCK), 0,
+                     static_cast<hipStream_t>(stream), anchor, positive, negative, ids_or_null, loss, N, R, D, rows, margin, eps);
+  return launch_status();
+}
+
+int hdn_triplet_l1_bwd_f32(const float* anchor, const float* positive, const float* negative, const long long* ids_or_null, const float* grad_loss,
+                           float* grad_a_or_null, float* grad_p_or_null, float* grad_n_or_null, int N, int R, int D, int n_ids, float margin,
+                           float eps, void* stream) {
+  using namespace hdn;
+  if (!anchor || !positive || !negative || !grad_loss) return HDN_E_NULL;
+  if (triplet::check_dims(ids_or_null, N, R, D, n_ids) || (!grad_a_or_null && !grad_p_or_null && !grad_n_or_null)) return HDN_E_SHAPE;
+  if (triplet::over_limit(ids_or_null, N, R, D, n_ids)) return HDN_E_LIMIT;
+  const long long rows = (long long)N * R, in_bytes = rows * D * 4, gl_bytes = (long long)(ids_or_null ? n_ids : N) * R * 4;
+  float* const outs[3] = {grad_a_or_null, grad_p_or_null, grad_n_or_null};
+  for (int i = 0; i < 3; ++i) {
+    if (!outs[i]) continue;
+    for (const float* in : {anchor, positive, negative})
+      if (bytes_overlap(outs[i], in_bytes, in, in_bytes)) return HDN_E_ALIAS;
+    if (bytes_overlap(outs[i], in_bytes, grad_loss, gl_bytes)) return HDN_E_ALIAS;
+    if (ids_or_null && bytes_overlap(outs[i], in_bytes, ids_or_null, (long long)n_ids * 8)) return HDN_E_ALIAS;
+    for (int j = 0; j < i; ++j)
+      if (outs[j] && bytes_overlap(outs[i], in_bytes, outs[j], in_bytes)) return HDN_E_ALIAS;
+  }
+  hipLaunchKernelGGL(triplet::bwd_kernel, dim3((unsigned)((rows + triplet::ROWS - 1) / triplet::ROWS)), dim3(HDN_BLOCK), 0,
+                     static_cast<hipStream_t>(stream), anchor, positive, negative, ids_or_null, grad_loss, grad_a_or_null, grad_p_or_null,
+                     grad_n_or_null, N, R, D, n_ids, margin, eps);
+  return launch_status();
+}
+
+}  // extern "C"

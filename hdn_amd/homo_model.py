@@ -252,3 +252,59 @@ class HomoModelBuilder(nn.Module):
             "pred_I2_CnnFeature_d": pf[:1],
             "homo_neg_loss": homo_neg_loss,
         }
+
+    def training_forward(self, data):
+        """The reference's training forward (homo_model_builder.py:154-215) on the differentiable HIP operators; the returned dict has forward()'s
+        keys and every loss carries the graph to the regressor and to ShareFeature.
+
+        In the reference's order: ShareFeature on each of the two channels (two calls, as :154-155: in train() mode each normalises with its own
+        batch statistics and updates the running buffers), the module's own backbone / avgpool / fc (never the folded inference trunk),
+        hdn_amd.DLT_solve and hdn_amd.transform (M = [[63.5, 0, 63.5], [0, 63.5, 63.5], [0, 0, 1]], the literal of :139-142), ShareFeature(pred_I2).
+        The flags are handled as forward() handles them.  The triplet term is one triplet_l1(patch_2, pred_feat, patch_1, ids=pos_ids,
+        differentiable=True): the x[pos_ids] copies of :185-187 are not made, and the gradients come back full size with zero rows for the
+        samples left out.  feature_loss = sum / n_pos / (127 * 127).
+
+        Raises when ShareFeature would detach (eval() mode with hip_train False: the fused inference kernel), rather than return a loss that is
+        cut off from the regressor."""
+        from .triplet import triplet_l1
+
+        sf = self.ShareFeature
+        if not sf.training and not getattr(sf, "hip_train", False):
+            raise RuntimeError("HomoModelBuilder.training_forward: ShareFeature is in eval() mode with hip_train False, where it runs the fused "
+                               "inference kernel and detaches; call .train(), or set ShareFeature.hip_train = True to keep the running statistics "
+                               "and the graph")
+        B, H, W = _check_data(data)
+        org, inp, h4p, patch_inds = data["org_imgs"], data["input_tensors"], data["h4p"], data["patch_indices"]
+        dev = inp.device
+        p1 = sf(inp[:, :1].contiguous())
+        p2 = sf(inp[:, 1:].contiguous())
+        x = self.backbone(torch.cat((p1, p2), dim=1))
+        x = self.fc(self.avgpool(x).view(x.size(0), -1))
+        H_mat = G.DLT_solve(h4p, x).squeeze(1)
+        M = torch.tensor([[63.5, 0.0, 63.5], [0.0, 63.5, 63.5], [0.0, 0.0, 1.0]], device=dev)
+        M_tile, M_tile_inv = M.unsqueeze(0).expand(B, 3, 3), torch.inverse(M).unsqueeze(0).expand(B, 3, 3)
+        batch_inds = torch.arange(0, B * H * W, H * W, device=dev).unsqueeze(1).expand(B, H * W).reshape(-1)
+        pred = G.transform(H, W, M_tile_inv, H_mat, M_tile, org[:, :1], patch_inds, batch_inds)
+        pf = sf(pred)
+        homo_neg_loss = torch.zeros((), device=dev)
+        n_pos, ids = B * H * W, None                          # default flags [B,1,127,127] of ones: nonzero() has one row per pixel
+        if "if_pos" in data or "if_unsup" in data:
+            ones = torch.ones((B, 1, 127, 127), dtype=torch.float32, device=dev)
+            if_pos, if_unsup = data.get("if_pos", ones).to(dev), data.get("if_unsup", ones).to(dev)
+            neg_ids = if_pos.eq(0).nonzero().squeeze(1)
+            pos_ids = (if_pos * if_unsup).eq(1).nonzero().squeeze(1)
+            n_pos = pos_ids.shape[0]
+            if neg_ids.shape[0] != 0:
+                ids = pos_ids
+                homo_neg_loss = torch.sum(torch.norm(x[neg_ids, :], p=2, dim=1)) / neg_ids.shape[0]
+        loss_mat = triplet_l1(p2, pf, p1, margin=1.0, eps=1e-6, ids=ids, differentiable=True)
+        feature_loss = (torch.sum(loss_mat) / n_pos / (127 * 127)).unsqueeze(0)
+        return {
+            "feature_loss": feature_loss,
+            "pred_I2_d": pred[:1],
+            "x": x,
+            "H_mat": H_mat,
+            "patch_2_res_d": p2[:1],
+            "pred_I2_CnnFeature_d": pf[:1],
+            "homo_neg_loss": homo_neg_loss,
+        }

@@ -20,13 +20,15 @@ attribute the reference resolves at call time:
                                                          host->device copy per frame, which a hipGraph capture cannot hold)
     ModelBuilder.template                                unchanged, then drops the heads' cached template-branch features
     ModelBuilder.stn_with_theta                          (install(train=True), while AFFINE_STN_TRAIN_BOUND) the differentiable HIP affine sampler
+    {model_builder_e2e_unconstrained_v2, homo_model_builder}.triplet_loss   (install(train=True), while TRIPLET_TRAIN_BOUND) TripletMarginLossL1
     hdn.tracker.tracker_builder.TRACKS['hdnTrackerHomoProje2e']   (install(tracker=True)) the device-resident tracker loop
 
 Training under install(train=True): every statement of the reference's training forwards that resolves to a drop-in is differentiable on the device -
 xcorr_depthwise{,_circular} (hdn_amd/xcorr.py), DLT_solve / transform / transformer (hdn_amd/homography.py) and, with train=True, STN_Polar
 (STN_PolarTrain, hdn_amd/logpolar.py; without train=True the STN_Polar drop-in raises on a grad-carrying input rather than detach) and
 PreShareFeature (PreShareFeatureTrain, hdn_amd/share_feature.py: batch statistics and the backward on HIP, and an eval mode that carries the graph) and
-ModelBuilder.stn_with_theta (hdn_amd/affine.py: the affine sampler of :407, :408, :418, forward and backward on HIP).  The rebound head
+ModelBuilder.stn_with_theta (hdn_amd/affine.py: the affine sampler of :407, :408, :418, forward and backward on HIP) and the module attribute
+`triplet_loss` of both model builders (hdn_amd/triplet.py: the L1 triplet rows of :438 and homo_model_builder.py:197).  The rebound head
 forwards defer to the classes' own forward in .train() mode.  What still needs uninstall(): anything that calls the fused inference paths with
 autograd expected - the fused track_proj, dlt_warp, the fused heads in eval mode, xcorr_fast / xcorr_slow, xcorr_depthwise_multi (they detach).
 """
@@ -38,7 +40,7 @@ import weakref
 
 import torch
 
-from . import affine, heads, homo_model, homography, logpolar, share_feature, xcorr
+from . import affine, heads, homo_model, homography, logpolar, share_feature, triplet, xcorr
 
 _DLT = "homo_estimator.Deep_homography.Oneline_DLTv1"
 
@@ -130,6 +132,14 @@ SHARE_FEATURE_TRAIN_BOUND = True
 # (profiles/affine_stn_train.json): True only while the HIP path is faster than F.affine_grid + F.grid_sample on the step's three calls at B = 32.
 AFFINE_STN_TRAIN_BOUND = True
 
+# Does install(train=True) bind a hdn_amd.triplet.TripletMarginLossL1 at the two `triplet_loss` module attributes?  Set by the outcome of
+# tools/triplet_train_bench.py (profiles/triplet_train.json): True only while the HIP loss is faster than x[ids] x 3 + nn.TripletMarginLoss on the
+# step's two sites at B = 32.
+TRIPLET_TRAIN_BOUND = True
+
+# the modules whose attribute `triplet_loss` is the reference's nn.TripletMarginLoss(margin=1.0, p=1, reduce=False, size_average=False)
+TRIPLET_SITES = ("hdn.models.model_builder_e2e_unconstrained_v2", _DLT + ".models.homo_model_builder")
+
 _MISSING = object()
 _saved = []  # (owner, attribute or dict key, original value, is_dict_item) in application order; undone by uninstall()
 
@@ -179,7 +189,9 @@ def install(strict: bool = False, modules: dict = None, tracker: bool = False, t
     (hdn_amd.homo_model.optimize_trunk(self.hm_net, channels_last=True)) at its first eval-mode call with CUDA float32 weights, for users of the
     rebindings without the device tracker; off by default.  train=True: the two STN_Polar sites are bound to hdn_amd.logpolar.STN_PolarTrain (the same
     module with differentiable=True) and, while SHARE_FEATURE_TRAIN_BOUND, preprocess.head['PreShareFeature'] to hdn_amd.share_feature.PreShareFeatureTrain
-    (hip_train=True) and, while AFFINE_STN_TRAIN_BOUND, ModelBuilder.stn_with_theta to hdn_amd.affine.stn_with_theta, so that the reference's training
+    (hip_train=True) and, while AFFINE_STN_TRAIN_BOUND, ModelBuilder.stn_with_theta to hdn_amd.affine.stn_with_theta and, while TRIPLET_TRAIN_BOUND,
+    the attribute `triplet_loss` of the two TRIPLET_SITES modules to a hdn_amd.triplet.TripletMarginLossL1 of the same margin and eps (only where it
+    is an nn.TripletMarginLoss with p = 1, swap False and reduction 'none'), so that the reference's training
     forward runs on the drop-ins; everything else is unchanged.  Returns the list of (module, attribute) pairs that were rebound;
     with strict=True a site that cannot be imported raises instead of being skipped.  uninstall() reverses it."""
     done = []
@@ -233,6 +245,15 @@ def install(strict: bool = False, modules: dict = None, tracker: bool = False, t
         if train and AFFINE_STN_TRAIN_BOUND and "stn_with_theta" in mb.ModelBuilder.__dict__:
             _rebind(mb.ModelBuilder, "stn_with_theta", affine.stn_with_theta)
             done.append(("hdn.models.model_builder_e2e_unconstrained_v2", "ModelBuilder.stn_with_theta"))
+
+    if train and TRIPLET_TRAIN_BOUND:
+        for mod_name in TRIPLET_SITES:
+            m = get(mod_name)
+            loss = getattr(m, "triplet_loss", None) if m is not None else None
+            # only the loss the kernel restates: L1 distances, no distance swap, one value per row
+            if isinstance(loss, torch.nn.TripletMarginLoss) and loss.p == 1 and not loss.swap and loss.reduction == "none":
+                _rebind(m, "triplet_loss", triplet.TripletMarginLossL1(margin=loss.margin, eps=loss.eps))
+                done.append((mod_name, "triplet_loss"))
 
     if tracker:
         tb = get("hdn.tracker.tracker_builder")

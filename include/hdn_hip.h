@@ -378,6 +378,43 @@ int hdn_affine_sample_bwd_f32(const float* img, const float* theta, const float*
                               float* workspace, long long workspace_bytes, int B, int C, int H, int W, int Ho, int Wo, void* stream);
 
 /*
+ * L1 triplet margin loss over rows (csrc/triplet_loss.hip): what nn.TripletMarginLoss(margin, p=1, eps, swap=False, reduction='none') computes on
+ * three [N,R,D] tensors, one loss per row, with the x[ids] gather of the reference's two call sites folded into the addressing.  Per row, in fp32:
+ *   d_ap = sum_j |(a_j - p_j) + eps|,   d_an = sum_j |(a_j - n_j) + eps|
+ *   v = (margin + d_ap) - d_an
+ *   loss = v if v >= 0, 0 if v < 0
+ * The subtraction is rounded, then the add of eps (F.pairwise_distance's two elementwise operations); eps is inside the absolute value.  A NaN v
+ * stays NaN (clamp_min's rule, not fmaxf's).  The sums are taken by one wave: lane l adds the elements l, l + 64, ... in ascending order, a xor
+ * butterfly adds the 64 lanes; the order is fixed, so two calls are bit-equal.
+ * anchor, positive, negative [N,R,D] fp32 contiguous, 4-byte aligned (every access is one dword); the three may alias each other.  ids: NULL, or
+ * n_ids sample indices (int64, 8-byte aligned, unique, as nonzero() gives them): row r of `loss` is then row r % R of sample ids[r / R].
+ * loss [n_sel R], n_sel = n_ids with ids, N without.  An ids entry outside [0, N) is checked before any address is formed: nothing is read for it
+ * and its R loss rows are NaN.
+ * Checked before the launch, in this order: anchor, positive, negative or loss NULL -> HDN_E_NULL; N, R or D <= 0, or ids with n_ids <= 0 ->
+ * HDN_E_SHAPE; N R > 2^30, n_ids R > 2^30 or D > 2^20 -> HDN_E_LIMIT; the byte range of loss overlapping an input's or ids' -> HDN_E_ALIAS.
+ * Replaces triplet_loss(...) at model_builder_e2e_unconstrained_v2.py:438 and homo_model_builder.py:197 (with the gathers of :428-436 / :185-187).
+ */
+int hdn_triplet_l1_f32(const float* anchor, const float* positive, const float* negative, const long long* ids_or_null, float* loss,
+                       int N, int R, int D, int n_ids, float margin, float eps, void* stream);
+
+/*
+ * hdn_triplet_l1_bwd_f32: the gradients of the loss above for grad_loss [n_sel R] = d L / d loss.  v is recomputed by the forward's own device
+ * function, so the bits are the forward's.  A row is active iff v >= 0 (clamp_min's rule: the gradient passes at exactly 0, not at NaN).
+ * With g = grad_loss[row], s_ap = sgn((a - p) + eps), s_an = sgn((a - n) + eps), sgn(0) = 0, per element of an active row:
+ *   grad_a = g (s_ap - s_an),   grad_p = -g s_ap,   grad_n = g s_an
+ * and 0 in a row that is not active.  g {0, +-1, +-2} is exact: every gradient is exact given the row's activity.
+ * grad_a, grad_p, grad_n are full size [N,R,D]; with ids, the rows of samples that ids does not name are zero, written by this call (no zero-fill
+ * is needed before it), and an ids entry outside [0, N) names no sample.  A NULL gradient is neither computed nor written; all three NULL is
+ * HDN_E_SHAPE.  One wave per gradient row writes every element exactly once: no atomics, bit-reproducible.  (A wave finds its sample in ids by
+ * scanning the list, the lowest position wins: n_ids / 64 steps per row.)
+ * Checked in the forward's order: an input or grad_loss NULL -> HDN_E_NULL; the forward's shape rules and "no gradient asked for" -> HDN_E_SHAPE;
+ * the forward's limits -> HDN_E_LIMIT; the byte range of a gradient overlapping an input's, ids', grad_loss's or another gradient's -> HDN_E_ALIAS.
+ */
+int hdn_triplet_l1_bwd_f32(const float* anchor, const float* positive, const float* negative, const long long* ids_or_null, const float* grad_loss,
+                           float* grad_a_or_null, float* grad_p_or_null, float* grad_n_or_null, int N, int R, int D, int n_ids, float margin,
+                           float eps, void* stream);
+
+/*
  * Device-resident frame handling: the uint8 frame [H,W,C] (HWC, BGR as cv2.imread delivers it) is
  * uploaded once; crops and warps are kernels.  `params` / `M` are DEVICE float64 arrays so that positions and homographies
  * produced on the device never visit the host.
