@@ -13,6 +13,12 @@
 // results land in a small float64 state record that the crop / warp kernels of frame.hip read directly, so the whole frame
 // stays capturable in one hipGraph.  One wave per pair; dtypes follow the reference statement by statement (float32 scores and
 // regression values, float64 window blend and geometry); every multiply / add is individually rounded (contraction off).
+//
+// Non-finite scores follow np.argmax, which is what the reference runs: a NaN (blended) score IS the maximum, the lowest index among NaNs
+// wins, an all-NaN map answers cell 0 (so does a map of -inf).  The gates stay the reference's `best < 0.05` / `best < 0.25`, false for a
+// NaN: a NaN winner is decoded from its cell's (finite) regression values and reported with a NaN score, never gated.
+// Invariant: after the argmax best_i lies in [0, n) for ANY input - every candidate a lane ever holds is a (score of cell i, i) pair of
+// a cell it read (argmax_start / argmax_takes below), so cls[best_i], loc[best_i] and points[2 * best_i] are reads inside the maps.
 #include <math.h>
 
 #include "hdn_common.h"
@@ -36,13 +42,24 @@ __device__ __forceinline__ float class_score(const float* __restrict__ cls, int 
   return cls_channels == 1 ? sigmoid1(cls[i]) : softmax2_class1(cls[i], cls[n + i]);
 }
 
-// np.argmax: the largest value, the lowest index among equals.
+// np.argmax's order on (value, index) candidates: a NaN is above every number, then the larger value, then - among equals and among
+// NaNs - the lower index.  True when candidate (ov, oi) replaces (v, i).
+__device__ __forceinline__ bool argmax_takes(double ov, int oi, double v, int i) {
+  const bool on = ov != ov, vn = v != v;
+  if (on || vn) return on && (!vn || oi < i);
+  return ov > v || (ov == v && oi < i);
+}
+
+// The cell a lane starts from: its own first cell, or - an idle lane of a map smaller than the wave - cell 0 once more.  No lane holds a
+// sentinel: whatever the butterfly keeps is a cell of the map, and the duplicate of cell 0 ties with lane 0's own (same value, same index).
+__device__ __forceinline__ int argmax_start(int lane, int n) { return lane < n ? lane : 0; }
+
 __device__ __forceinline__ void wave_argmax(double& v, int& i) {
 #pragma unroll
   for (int s = 32; s >= 1; s >>= 1) {
     const double ov = __shfl_xor(v, s);
     const int oi = __shfl_xor(i, s);
-    if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
+    if (argmax_takes(ov, oi, v, i)) { v = ov; i = oi; }
   }
 }
 
@@ -57,12 +74,12 @@ __global__ __launch_bounds__(HDN_WAVE) void similarity_translation_kernel(const 
   seq += size_t(b) * HDN_SIM_SEQ_DOUBLES;
   state += size_t(b) * HDN_SIM_STATE_DOUBLES;
   const float keep = (float)(1.0 - window_influence);  // score (float32 array) * python float stays float32
-  double best = -INFINITY;
-  int best_i = 0x7fffffff;
-  for (int i = lane; i < n; i += HDN_WAVE) {
-    const float sc = class_score(cls, n, i, cls_channels);
-    const double ps = (double)rn_mul(sc, keep) + window[i] * window_influence;
-    if (ps > best) { best = ps; best_i = i; }  // ascending i per lane: the first maximum stays
+  const auto pscore = [&](int i) { return (double)rn_mul(class_score(cls, n, i, cls_channels), keep) + window[i] * window_influence; };
+  int best_i = argmax_start(lane, n);  // n >= 1: a cell of the map.  best_i in [0, n) from here on (header)
+  double best = pscore(best_i);
+  for (int i = lane + HDN_WAVE; i < n; i += HDN_WAVE) {
+    const double ps = pscore(i);
+    if (argmax_takes(ps, i, best, best_i)) { best = ps; best_i = i; }  // ascending i per lane: the first maximum / the first NaN stays
   }
   wave_argmax(best, best_i);
   if (lane == 0) {
@@ -101,11 +118,11 @@ __global__ __launch_bounds__(HDN_WAVE) void similarity_logpolar_kernel(const flo
   loc_lp += size_t(b) * 4 * n;
   seq += size_t(b) * HDN_SIM_SEQ_DOUBLES;
   state += size_t(b) * HDN_SIM_STATE_DOUBLES;
-  double best = -INFINITY;  // (float32 scores compared as doubles: exact)
-  int best_i = 0x7fffffff;
-  for (int i = lane; i < n; i += HDN_WAVE) {
+  int best_i = argmax_start(lane, n);  // best_i in [0, n) from here on (header)
+  double best = (double)class_score(cls_lp, n, best_i, cls_channels);  // (float32 scores compared as doubles: exact)
+  for (int i = lane + HDN_WAVE; i < n; i += HDN_WAVE) {
     const double sc = (double)class_score(cls_lp, n, i, cls_channels);
-    if (sc > best) { best = sc; best_i = i; }
+    if (argmax_takes(sc, i, best, best_i)) { best = sc; best_i = i; }
   }
   wave_argmax(best, best_i);
   if (lane == 0) {

@@ -497,7 +497,9 @@ int hdn_remap_linear_f32(const float* src, const float* mapx, const float* mapy,
  * hdn/models/model_builder_e2e_unconstrained_v2.py:131-158).  window[S*S] float64 and points[S*S,2] float32: the tables the
  * reference's constructor builds (hdn_tracker_proj_e2e.py:26-32).  mag = log(EXEMPLAR / 2) / EXEMPLAR and
  * rot_unit = (float)(2 pi / EXEMPLAR) are passed in as the host computed them.  The log-polar call reads the state record the
- * translation call wrote.  np.argmax semantics (first maximum); NaN logits are not ordered the way numpy orders them.
+ * translation call wrote.  np.argmax semantics throughout: the first maximum; a NaN (blended) score is the maximum, the first NaN wins,
+ * an all-NaN map answers cell 0.  best_idx / best_idx_lp lie in [0, S*S) for any input.  The gates are `score < 0.05` / `< 0.25`, false for a
+ * NaN: a NaN winner is decoded from its cell's regression values and reported with NaN scores, as the reference's numpy does.
  * cls_channels = cfg.BAN.KWARGS.cls_out_channels: 2 -> score = softmax over the two planes, class 1 (every shipped configuration);
  * 1 -> score = sigmoid of the single plane (hdn_tracker.py:85-87); anything else HDN_E_SHAPE.
  */
