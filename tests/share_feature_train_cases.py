@@ -15,7 +15,10 @@ term.  Every bound fixture keeps each float64 pre-activation z away from zero: m
 reference's own error on that layer's z (16: the geometry tests' "20 or more ulps" reasoning; a kernel as accurate as the reference on z then reads
 the same masks).  Fixtures are seeded draws (image and grad_out standard normal, Kaiming weights, gamma in [0.5, 1.5], bias in [-0.5, 0.5]) from the
 first seed offset >= 0 from SEED that satisfies the rule; the offsets are committed below and the host test re-derives them.  Beyond ~110k
-pre-activations per layer the rule stops being satisfiable, so no fixture is larger than one 127 x 127 image.
+pre-activations per layer the rule stops being satisfiable, so no BOUND fixture is larger than one 127 x 127 image; the exact fixtures of
+tests/share_feature_train_exact_cases.py need no margin and go beyond it.
+
+eps and momentum are one number for all three BatchNorms or one per layer (a 3-tuple); EPS3 / MOMENTA3 are the cases with three different ones.
 
 Cases: the shapes of the issue, (1,2,3), and both sides of every boundary of the launch rule of csrc/share_feature_train.hip - a workgroup owns 1024
 consecutive pixels of one image, a thread the pixels t, t + 256, ... of them (H W = 256 | 257 and 1024 | 1025), the weight finish adds 64 partials per
@@ -43,6 +46,9 @@ TRAIN_CASES = {
 }
 # the same for frozen statistics (eval mode, random running mean / var) and for the three-call step
 FROZEN_CASES = {(3, 9, 11): 0, (2, 17, 130): 0}
+EPS3 = (1e-5, 1e-3, 1e-1)                      # three different eps: a permutation of them between the layers moves every tensor far beyond the bound
+EPS3_CASES = {("train", (3, 9, 11)): 0, ("frozen", (3, 9, 11)): 0}             # (mode, shape) -> first seed offset under EPS3
+MOMENTA3 = (0.1, None, 0.5)                    # not all equal: the per-layer loop of PreShareFeature._update_running
 STEP_CASE = ((3, 9, 11), 0)
 HINGE_MARGIN = 1e-4                            # the step's triplet hinge argument stays this far from zero (its fp32 error is ~1e-6)
 OFFSETS = [(0, 0, 0, 0, 0), (1, 2, 3, 1, 2)]   # float offsets of out / grad_img, saved / grad_params, stats, img, grad_out in a 16-byte line
@@ -74,16 +80,22 @@ def draw(B, H, W, seed):
     return fix
 
 
-def load_params(module, fix, running=None, momentum=0.1):
+def per_layer(v):
+    """One value for all three BatchNorms, or one per layer."""
+    return tuple(v) if isinstance(v, (tuple, list)) else (v, v, v)
+
+
+def load_params(module, fix, running=None, momentum=0.1, eps=1e-5):
     """Copy the fixture's parameters (and, running = (mean, var), the buffers) into a PreShareFeature-like module; -> module."""
     seq = module.ShareFeature
+    momentum, eps = per_layer(momentum), per_layer(eps)
     with torch.no_grad():
         for l, (c, b) in enumerate(((0, 1), (3, 4), (6, 7))):
             lo, hi = LAYERS[l]
             seq[c].weight.copy_(fix["w%d" % (l + 1)])
             seq[b].weight.copy_(fix["gamma"][lo:hi])
             seq[b].bias.copy_(fix["bias"][lo:hi])
-            seq[b].momentum = momentum
+            seq[b].momentum, seq[b].eps = momentum[l], eps[l]
             if running is not None:
                 seq[b].running_mean.copy_(running[0][lo:hi])
                 seq[b].running_var.copy_(running[1][lo:hi])
@@ -107,26 +119,30 @@ def collect(module, y, x, zs=None):
     return out
 
 
-def stock(fix, dtype, train=True, running=None, momentum=0.1, calls=1):
+def stock(fix, dtype, train=True, running=None, momentum=0.1, calls=1, eps=1e-5):
     """The stock nn.Sequential on the CPU in `dtype`: `calls` forwards on fix['x'] (the last one with backward of fix['g']).  -> collect()'s dict with
-    'z' = the three layers' pre-activations (BatchNorm outputs) of the last call."""
+    'z' = the three layers' pre-activations (BatchNorm outputs) and 'c' = the three convolutions' outputs of the last call."""
     from hdn_amd.share_feature import PreShareFeature
-    m = load_params(PreShareFeature().to(dtype), fix, running, momentum).train(train)
-    zs = []
+    m = load_params(PreShareFeature().to(dtype), fix, running, momentum, eps).train(train)
+    zs, cs = [], []
     hooks = [m.ShareFeature[b].register_forward_hook(lambda mod, i, o: zs.append(o.detach().clone())) for b in (1, 4, 7)]
+    hooks += [m.ShareFeature[c].register_forward_hook(lambda mod, i, o: cs.append(o.detach().clone())) for c in (0, 3, 6)]
     x = fix["x"].detach().clone().to(dtype).requires_grad_(True)
     for _ in range(calls):
-        del zs[:]
+        del zs[:], cs[:]
         y = m.ShareFeature(x)
     y.backward(fix["g"].to(dtype))
     for h in hooks:
         h.remove()
-    return collect(m, y, x, list(zs))
+    out = collect(m, y, x, list(zs))
+    out["c"] = list(cs)
+    return out
 
 
 def restatement(fix, momentum=0.1, calls=1, eps=1e-5):
     """The float64 truth with batch statistics, BatchNorm's forward and backward written out.  Buffers start at PyTorch's (0, 1) and are updated `calls`
     times with the same batch.  -> the dict of stock()."""
+    momentum, eps = per_layer(momentum), per_layer(eps)
     d = lambda t: t.double()
     x, g = d(fix["x"]), d(fix["g"])
     ws = [d(fix["w1"]), d(fix["w2"]), d(fix["w3"])]
@@ -137,14 +153,14 @@ def restatement(fix, momentum=0.1, calls=1, eps=1e-5):
         c = F.conv2d(a, ws[l], padding=1)
         mean = c.sum(dim=(0, 2, 3), keepdim=True) / N
         var = ((c - mean) ** 2).sum(dim=(0, 2, 3), keepdim=True) / N
-        invstd = 1.0 / torch.sqrt(var + eps)
+        invstd = 1.0 / torch.sqrt(var + eps[l])
         xh = (c - mean) * invstd
         z = xh * gamma + bias
         acts.append(a)
         keep.append((gamma, invstd, xh, z))
         rm, rv = torch.zeros(hi - lo, dtype=torch.float64), torch.ones(hi - lo, dtype=torch.float64)
         for k in range(calls):
-            m = 1.0 / (k + 1) if momentum is None else momentum
+            m = 1.0 / (k + 1) if momentum[l] is None else momentum[l]
             rm = (1 - m) * rm + m * mean.reshape(-1)
             rv = (1 - m) * rv + m * (var.reshape(-1) * N / (N - 1))
         out["rm%d" % (l + 1)], out["rv%d" % (l + 1)], out["nbt%d" % (l + 1)] = rm, rv, calls
@@ -179,22 +195,23 @@ def running_of(fix):
 
 
 @functools.lru_cache(maxsize=None)
-def problem(shape, offset, mode="train"):
+def problem(shape, offset, mode="train", eps=1e-5):
     """(fixture, truth, reference) of one case at one seed offset; mode 'train' (batch statistics, momentum 0.1, one call) or 'frozen'."""
     fix = draw(*shape, SEED + offset)
     if mode == "train":
-        return fix, restatement(fix), stock(fix, torch.float32)
-    return fix, stock(fix, torch.float64, train=False, running=running_of(fix)), stock(fix, torch.float32, train=False, running=running_of(fix))
+        return fix, restatement(fix, eps=eps), stock(fix, torch.float32, eps=eps)
+    return (fix, stock(fix, torch.float64, train=False, running=running_of(fix), eps=eps),
+            stock(fix, torch.float32, train=False, running=running_of(fix), eps=eps))
 
 
-def first_offset(shape, mode="train"):
+def first_offset(shape, mode="train", eps=1e-5):
     """The first seed offset in [0, MAX_OFFSET) whose draw satisfies the margin rule, or None."""
     for off in range(MAX_OFFSET):
         if mode == "step":
             if step_margin_ok(*step_problem(shape, off)[1:]):
                 return off
             continue
-        _, truth, ref = problem(shape, off, mode)
+        _, truth, ref = problem(shape, off, mode, eps)
         if margin_ok(truth["z"], ref["z"]):
             return off
     return None
@@ -258,10 +275,10 @@ def step_margin_ok(truth, ref):
 
 
 # ================================================================================================================= on the device
-def run_module(fix, dev, train=True, running=None, momentum=0.1, calls=1, x_grad=True, p_grad=True, backward=True):
+def run_module(fix, dev, train=True, running=None, momentum=0.1, calls=1, x_grad=True, p_grad=True, backward=True, eps=1e-5):
     """hdn_amd.PreShareFeatureTrain on `dev`: `calls` forwards on fix['x'], then backward of fix['g'].  -> collect()'s dict (+ 'grad_fn')."""
     import hdn_amd
-    m = load_params(hdn_amd.PreShareFeatureTrain(), fix, running, momentum).to(dev).train(train)
+    m = load_params(hdn_amd.PreShareFeatureTrain(), fix, running, momentum, eps).to(dev).train(train)
     for p in m.parameters():
         p.requires_grad_(p_grad)
     x = fix["x"].detach().clone().to(dev).requires_grad_(x_grad)
@@ -292,7 +309,7 @@ def untouched(buf, lo, hi):
     return bool((raw[:lo] == BYTE).all()) and bool((raw[hi:] == BYTE).all())
 
 
-def run_raw(fix, dev, offsets=(0, 0, 0, 0, 0), frozen=False, need_x=True, need_params=True):
+def run_raw(fix, dev, offsets=(0, 0, 0, 0, 0), frozen=False, need_x=True, need_params=True, eps=1e-5):
     """One raw hdn_share_feature_train_fwd_f32 and one hdn_share_feature_bwd_f32: every output starts as NaN inside 0xA5 margins at the given float
     offsets; an output that is not asked for is NULL and its buffer 0xA5 everywhere.  -> (dict y, stats, gx | None, gp | None on the CPU, were all
     bytes outside the results left alone?)."""
@@ -301,6 +318,7 @@ def run_raw(fix, dev, offsets=(0, 0, 0, 0, 0), frozen=False, need_x=True, need_p
     B, _, H, W = fix["x"].shape
     n = B * H * W
     P = _lib.ptr
+    eps = per_layer(eps)
     xd, gd = at_offset(fix["x"], offsets[3], dev)[0], at_offset(fix["g"], offsets[4], dev)[0]
     par = {k: fix[k].to(dev) for k in ("w1", "w2", "w3", "gamma", "bias")}
     mv = torch.cat([fix["rmean"], fix["rvar"]]).to(dev) if frozen else None
@@ -317,7 +335,7 @@ def run_raw(fix, dev, offsets=(0, 0, 0, 0, 0), frozen=False, need_x=True, need_p
     ws = torch.full((nbytes // 4,), float("nan"), device=dev)
     st = _lib.stream_ptr(dev)
     rc = lib.hdn_share_feature_train_fwd_f32(P(xd), P(par["w1"]), P(par["w2"]), P(par["w3"]), P(par["gamma"]), P(par["bias"]),
-                                             P(mv) if frozen else None, 1e-5, 1e-5, 1e-5, 1 if frozen else 0, P(outs["y"][0]), P(outs["saved"][0]),
+                                             P(mv) if frozen else None, eps[0], eps[1], eps[2], 1 if frozen else 0, P(outs["y"][0]), P(outs["saved"][0]),
                                              P(outs["stats"][0]), P(ws), nbytes, B, H, W, st)
     _lib.check(rc, "hdn_share_feature_train_fwd_f32")
     ws.fill_(float("nan"))

@@ -30,7 +30,21 @@ def test_batch_statistics_every_tensor_within_the_bound(shape):
     check_bound(got, truth, ref, C.TENSORS, f"train {shape}")
 
 
-@pytest.mark.parametrize("shape, momentum", [((3, 9, 11), 0.1), ((5, 13, 33), None)])
+@pytest.mark.parametrize("mode, shape", list(C.EPS3_CASES))
+def test_three_different_eps_every_tensor_within_the_bound(mode, shape):
+    """eps1, eps2, eps3 all different: a permutation between the layers (the three stats_finish launches, table_kernel's selection) moves every
+    tensor far beyond the bound."""
+    fix, truth, ref = C.problem(shape, C.EPS3_CASES[mode, shape], mode, C.EPS3)
+    if mode == "train":
+        got = C.run_module(fix, DEV, eps=C.EPS3)
+        check_bound(got, truth, ref, C.TENSORS, f"three eps train {shape}")
+    else:
+        got = C.run_module(fix, DEV, train=False, running=C.running_of(fix), eps=C.EPS3)
+        check_bound(got, truth, ref, ("y",) + GRADS, f"three eps frozen {shape}")
+    assert got["grad_fn"]
+
+
+@pytest.mark.parametrize("shape, momentum", [((3, 9, 11), 0.1), ((5, 13, 33), None), ((3, 9, 11), C.MOMENTA3)])
 def test_running_buffers_after_two_calls(shape, momentum):
     fix = C.problem(shape, C.TRAIN_CASES[shape])[0]
     truth, ref = C.restatement(fix, momentum, calls=2), C.stock(fix, torch.float32, momentum=momentum, calls=2)

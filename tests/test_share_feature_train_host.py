@@ -40,6 +40,26 @@ def test_train_fixtures_keep_the_relu_margin_and_the_reference_its_own_bound(sha
         assert err <= bound, name
 
 
+@pytest.mark.parametrize("mode, shape", list(C.EPS3_CASES))
+def test_three_eps_fixtures_keep_the_relu_margin_and_feel_a_permutation(mode, shape):
+    off = C.EPS3_CASES[mode, shape]
+    assert len(set(C.EPS3)) == 3 and C.first_offset(shape, mode, C.EPS3) == off
+    fix, truth, ref = C.problem(shape, off, mode, C.EPS3)
+    assert C.margin_ok(truth["z"], ref["z"])
+    swapped = C.problem(shape, off, mode, (C.EPS3[1], C.EPS3[2], C.EPS3[0]))[1]        # what a kernel that permutes the three eps computes
+    for name in ("y", "gx", "gw1", "gw2", "gw3"):
+        err, bound = C.excess(swapped, truth, ref, name)
+        assert err > 10 * bound, name
+
+
+def test_restatement_with_three_momenta_is_float64_autograd():
+    assert None in C.MOMENTA3 and len(set(C.MOMENTA3)) == 3
+    fix = C.draw(3, 9, 11, C.SEED)
+    truth, auto = C.restatement(fix, C.MOMENTA3, 2), C.stock(fix, torch.float64, momentum=C.MOMENTA3, calls=2)
+    for name in C.TENSORS:
+        assert rel(truth[name], auto[name]) <= 1e-12, name
+
+
 @pytest.mark.parametrize("shape", list(C.FROZEN_CASES))
 def test_frozen_fixtures_keep_the_relu_margin(shape):
     assert C.first_offset(shape, "frozen") == C.FROZEN_CASES[shape]
