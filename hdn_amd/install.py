@@ -21,6 +21,8 @@ attribute the reference resolves at call time:
     ModelBuilder.template                                unchanged, then drops the heads' cached template-branch features
     ModelBuilder.stn_with_theta                          (install(train=True), while AFFINE_STN_TRAIN_BOUND) the differentiable HIP affine sampler
     {model_builder_e2e_unconstrained_v2, homo_model_builder}.triplet_loss   (install(train=True), while TRIPLET_TRAIN_BOUND) TripletMarginLossL1
+    model_builder_e2e_unconstrained_v2.{select_xr_focal_fuse_smooth_l1_loss_top_k, select_l1_loss_c, select_cross_entropy_loss, select_l1_loss,
+        kalyo_l1_loss}                                   (install(train=True), while SUP_LOSS_TRAIN_BOUND) the drop-ins of hdn_amd/losses.py
     hdn.tracker.tracker_builder.TRACKS['hdnTrackerHomoProje2e']   (install(tracker=True)) the device-resident tracker loop
 
 Training under install(train=True): every statement of the reference's training forwards that resolves to a drop-in is differentiable on the device -
@@ -40,7 +42,7 @@ import weakref
 
 import torch
 
-from . import affine, heads, homo_model, homography, logpolar, share_feature, triplet, xcorr
+from . import affine, heads, homo_model, homography, logpolar, losses, share_feature, triplet, xcorr
 
 _DLT = "homo_estimator.Deep_homography.Oneline_DLTv1"
 
@@ -140,6 +142,14 @@ TRIPLET_TRAIN_BOUND = True
 # the modules whose attribute `triplet_loss` is the reference's nn.TripletMarginLoss(margin=1.0, p=1, reduce=False, size_average=False)
 TRIPLET_SITES = ("hdn.models.model_builder_e2e_unconstrained_v2", _DLT + ".models.homo_model_builder")
 
+# Does install(train=True) bind the five loss drop-ins of hdn_amd.losses at the names model_builder_e2e_unconstrained_v2 imports from
+# hdn.models.loss?  Set by the outcome of tools/sup_loss_train_bench.py (profiles/sup_loss_train.json): True only while the reference's formulation
+# of :457-478 with the drop-ins inside is faster, forward and backward at B = 32, than with its own PyTorch functions.
+SUP_LOSS_TRAIN_BOUND = True
+
+SUP_LOSS_SITE = "hdn.models.model_builder_e2e_unconstrained_v2"
+SUP_LOSS_NAMES = ("select_xr_focal_fuse_smooth_l1_loss_top_k", "select_l1_loss_c", "select_cross_entropy_loss", "select_l1_loss", "kalyo_l1_loss")
+
 _MISSING = object()
 _saved = []  # (owner, attribute or dict key, original value, is_dict_item) in application order; undone by uninstall()
 
@@ -191,8 +201,10 @@ def install(strict: bool = False, modules: dict = None, tracker: bool = False, t
     module with differentiable=True) and, while SHARE_FEATURE_TRAIN_BOUND, preprocess.head['PreShareFeature'] to hdn_amd.share_feature.PreShareFeatureTrain
     (hip_train=True) and, while AFFINE_STN_TRAIN_BOUND, ModelBuilder.stn_with_theta to hdn_amd.affine.stn_with_theta and, while TRIPLET_TRAIN_BOUND,
     the attribute `triplet_loss` of the two TRIPLET_SITES modules to a hdn_amd.triplet.TripletMarginLossL1 of the same margin and eps (only where it
-    is an nn.TripletMarginLoss with p = 1, swap False and reduction 'none'), so that the reference's training
-    forward runs on the drop-ins; everything else is unchanged.  Returns the list of (module, attribute) pairs that were rebound;
+    is an nn.TripletMarginLoss with p = 1, swap False and reduction 'none') and, while SUP_LOSS_TRAIN_BOUND, the five SUP_LOSS_NAMES that
+    model_builder_e2e_unconstrained_v2 imports from hdn.models.loss to the drop-ins of hdn_amd.losses (only where the attribute exists;
+    select_xr_focal_fuse_smooth_l1_loss and select_l1_loss_lp, the WEIGHTED_MAP_LP: True branch, stay the reference's), so that the reference's
+    training forward runs on the drop-ins; everything else is unchanged.  Returns the list of (module, attribute) pairs that were rebound;
     with strict=True a site that cannot be imported raises instead of being skipped.  uninstall() reverses it."""
     done = []
 
@@ -254,6 +266,13 @@ def install(strict: bool = False, modules: dict = None, tracker: bool = False, t
             if isinstance(loss, torch.nn.TripletMarginLoss) and loss.p == 1 and not loss.swap and loss.reduction == "none":
                 _rebind(m, "triplet_loss", triplet.TripletMarginLossL1(margin=loss.margin, eps=loss.eps))
                 done.append((mod_name, "triplet_loss"))
+
+    if train and SUP_LOSS_TRAIN_BOUND:
+        m = get(SUP_LOSS_SITE)
+        for name in SUP_LOSS_NAMES:
+            if m is not None and hasattr(m, name):
+                _rebind(m, name, losses.DROP_INS[name])
+                done.append((SUP_LOSS_SITE, name))
 
     if tracker:
         tb = get("hdn.tracker.tracker_builder")

@@ -415,6 +415,68 @@ int hdn_triplet_l1_bwd_f32(const float* anchor, const float* positive, const flo
                            float eps, void* stream);
 
 /*
+ * The similarity model's supervised head losses (csrc/sup_losses.hip): up to five scalar losses of hdn/models/loss.py in one launch, one workgroup
+ * per loss, as model_builder_e2e_unconstrained_v2.py:457-478 and :516-523 use them (WEIGHTED_MAP_LP: False).  All selection - the sample mask, the
+ * label predicates, the label maximum, the counts, the top-k - happens in the kernel: no nonzero(), no host read, capturable in a graph.
+ * "selected" below means: label predicate AND sample selected.  losses [5] receives (a) .. (e) at index 0 .. 4; a loss whose pointers are all NULL is
+ * skipped and its entry is not written.
+ *
+ * (a) select_xr_focal_fuse_smooth_l1_loss_top_k: cls + label_cls (float [n,S,S]); p1 = the class-1 probability.
+ *   pos = sum{label > 0} |label - p1| / (n_pos + 1)
+ *   l = -log(1 - clamp(p1, 0.000001f, 0.9999999f)) over the cells with label == 0
+ *   neg = (sum of the k_eff largest l) / (k_eff + 1),  k = topk_per_sample n,  k_eff = min(k, n_neg)
+ *   loss = pos + neg
+ *   The k-th largest l, t, is found by a radix select on the bit patterns (l > 0); the sum is sum{l > t} + (k_eff - count_gt) t.  Where the reference
+ *   raises (fewer negatives than k) k_eff is used instead: a kernel cannot raise without a host read.  Python passes topk_per_sample = 100.
+ * (b) select_l1_loss_c: loc, label_loc_c [n,2,S,S] + label_cls.  max_c = the largest label_cls of the selected samples; cells: label > max_c - 0.2f;
+ *   loss = sum over the cells and both channels of smooth(pred - target) / (2 n_sel + 1),  smooth(d) = 0.5 d^2 if |d| < 1, |d| - 0.5 otherwise
+ *   A NaN label makes max_c NaN (torch.max), which selects nothing.  Labels that are all negative select every cell within 0.2 of their maximum.
+ * (c) select_cross_entropy_loss: cls_lp + label_cls_lp (int64 [n,S',S']);
+ *   loss = 0.5 mean{label == 1}(-logp1) + 0.5 mean{label == 0}(-logp0)
+ * (d) select_l1_loss: loc_lp, label_loc_lp [n,4,S',S'] + label_cls_lp; cells: label > 0;  loss = sum smooth(pred - target) / (4 n_sel + 1)
+ * (e) kalyo_l1_loss: rows, rows_target [n_rows,C], every row;  loss = sum smooth(rows - target) / (n_rows C + 1)
+ * The one-hit rule (the reference's nonzero().squeeze() turns one hit into a 0-d tensor, which its emptiness test takes for empty): with exactly
+ * one selected cell the term is 0 in (a) pos, (a) neg, (b) and both terms of (c); not in (d), where one row gives the ordinary value.  With no
+ * selected cell every term is 0.  A NaN in a selected prediction makes that loss NaN.
+ *
+ * form 0: the raw head maps cls [B,2,S,S], loc [B,2,S,S], cls_lp [B,2,S',S'], loc_lp [B,4,S',S']; F.softmax for (a) and F.log_softmax for (c) are
+ *   folded in, evaluated as PyTorch does: exp(x - max) / sum and (x - max) - log(sum exp(x - max)), with expf / logf (not the fast intrinsics).
+ *   if_unsup [B] (float, may be NULL = every sample): sample b is selected iff if_unsup[b] == 0; n is counted in the kernel.  No sample selected:
+ *   every loss is 0.
+ * form 1: what the reference's functions receive: cls / cls_lp [n,S,S,2] already softmaxed / log-softmaxed, B = n, if_unsup NULL.
+ * Every sum has a fixed order (thread t adds the cells t, t + 1024, ... ascending; a xor butterfly; the 16 wave sums in order): no float atomics,
+ * every output is bit-reproducible.  Integer LDS histograms only.
+ * Checked before the launch, in this order: losses NULL, a loss with some but not all of its pointers, or no loss at all -> HDN_E_NULL; form not 0
+ * or 1, if_unsup with form 1, B, S, S_lp, n_rows, C or topk_per_sample <= 0 where a present loss uses it -> HDN_E_SHAPE; B S^2 or B S_lp^2 > 40000
+ * (64 x 25 x 25: the l of (a) live in LDS), n_rows C > 2^20 -> HDN_E_LIMIT; losses overlapping an input -> HDN_E_ALIAS.
+ */
+int hdn_sup_losses_f32(const float* cls, const float* label_cls, const float* loc, const float* label_loc_c, const float* cls_lp,
+                       const long long* label_cls_lp, const float* loc_lp, const float* label_loc_lp, const float* rows, const float* rows_target,
+                       const float* if_unsup_or_null, float* losses, int B, int S, int S_lp, int n_rows, int C, int topk_per_sample, int form,
+                       void* stream);
+
+/*
+ * hdn_sup_losses_bwd_f32: the gradients of the losses above for grad_losses [5] = d L / d losses, one launch.  Every selection is repeated by the
+ * forward's own device functions, so the decisions are made on the forward's bits.  A gradient pointer that is NULL is neither computed nor written;
+ * the others are written in full (zero where nothing is selected, zero rows for unselected samples: no zero-fill is needed before the call).
+ * (a) positives: g sgn(p1 - label) / (n_pos + 1), sgn(0) = 0.  Negatives: every cell with l > t, and among the cells with l == t the lowest flat
+ *     indices (b S^2 + cell) until k_eff are reached - torch.topk's own choice among ties is unspecified - receive g / ((k_eff + 1)(1 - p1)) where
+ *     0.000001f <= p1 <= 0.9999999f (clamp passes the gradient on its closed interval) and 0 outside.  form 0: grad x1 = gp p1 p0, grad x0 = -grad x1;
+ *     form 1: channel 1 receives gp, channel 0 is written as zero.
+ * (b), (d), (e): g (d if |d| < 1, sgn(d) otherwise) / (C n_sel + 1), d = pred - target, on the selected cells.
+ * (c) a_1 = -0.5 g / n_1 on label == 1, a_0 = -0.5 g / n_0 on label == 0; form 1: written to those channels; form 0: grad x_j = a_j - softmax_j (a_0 + a_1).
+ * A term that the one-hit rule makes 0 has gradient 0.
+ * Checked in the forward's order: grad_losses NULL, or a gradient asked for a loss whose inputs are missing -> HDN_E_NULL (with the forward's NULL
+ * rules); the forward's shape rules and "no gradient asked for" -> HDN_E_SHAPE; the forward's limits -> HDN_E_LIMIT; a gradient overlapping an
+ * input, grad_losses or another gradient -> HDN_E_ALIAS.
+ */
+int hdn_sup_losses_bwd_f32(const float* cls, const float* label_cls, const float* loc, const float* label_loc_c, const float* cls_lp,
+                           const long long* label_cls_lp, const float* loc_lp, const float* label_loc_lp, const float* rows,
+                           const float* rows_target, const float* if_unsup_or_null, const float* grad_losses, float* grad_cls_or_null,
+                           float* grad_loc_or_null, float* grad_cls_lp_or_null, float* grad_loc_lp_or_null, float* grad_rows_or_null, int B, int S,
+                           int S_lp, int n_rows, int C, int topk_per_sample, int form, void* stream);
+
+/*
  * Device-resident frame handling: the uint8 frame [H,W,C] (HWC, BGR as cv2.imread delivers it) is
  * uploaded once; crops and warps are kernels.  `params` / `M` are DEVICE float64 arrays so that positions and homographies
  * produced on the device never visit the host.
