@@ -147,6 +147,12 @@ SIGNATURES = {
     "hdn_triplet_l1_bwd_f32": (_i, [_c_float_p] * 8 + [_i] * 4 + [ctypes.c_float] * 2 + [ctypes.c_void_p]),
     "hdn_sup_losses_f32": (_i, [_c_float_p] * 12 + [_i] * 7 + [ctypes.c_void_p]),
     "hdn_sup_losses_bwd_f32": (_i, [_c_float_p] * 17 + [_i] * 7 + [ctypes.c_void_p]),
+    "hdn_point_pick_f32": (_i, [_c_float_p] * 4 + [_i] * 5 + [ctypes.c_float] + [ctypes.c_double] * 2 + [ctypes.c_void_p]),
+    "hdn_point_pick_bwd_f32": (_i, [_c_float_p] * 4 + [_i] * 3 + [ctypes.c_float] + [ctypes.c_double] * 2 + [ctypes.c_void_p]),
+    "hdn_simi_affine_f32": (_i, [_c_float_p] * 5 + [ctypes.c_double] * 2 + [_c_float_p] + [_i] * 3 + [ctypes.c_double] * 2 + [ctypes.c_void_p]),
+    "hdn_simi_affine_bwd_f32": (_i, [_c_float_p] * 5 + [ctypes.c_double] * 2 + [_c_float_p] * 4 + [_i] * 3 + [ctypes.c_double] * 2 + [ctypes.c_void_p]),
+    "hdn_simi_warps_f32": (_i, [_c_float_p] * 15 + [_i] * 4 + [ctypes.c_float] + [ctypes.c_double] * 4 + [ctypes.c_void_p]),
+    "hdn_simi_warps_bwd_f32": (_i, [_c_float_p] * 12 + [_i] * 2 + [ctypes.c_float] + [ctypes.c_double] * 4 + [ctypes.c_void_p]),
 }
 
 ERRORS = {

@@ -21,18 +21,12 @@
 // a cell it read (argmax_start / argmax_takes below), so cls[best_i], loc[best_i] and points[2 * best_i] are reads inside the maps.
 #include <math.h>
 
+#include "argmax_order.h"
 #include "hdn_common.h"
 
 #pragma clang fp contract(off)
 
 namespace hdn {
-
-// softmax(1)[:, 1] of a 2-class logit pair as ATen's vectorised CPU kernel forms it: exp(x - max) for both, times 1 / sum.
-__device__ __forceinline__ float softmax2_class1(float x0, float x1) {
-  const float m = fmaxf(x0, x1);
-  const float e0 = expf(rn_sub(x0, m)), e1 = expf(rn_sub(x1, m));
-  return rn_mul(e1, rn_div(1.0f, rn_add(e0, e1)));
-}
 
 // score.sigmoid() of a 1-channel logit map (hdnTracker._convert_score, hdn_tracker.py:85-87) as ATen's CPU kernel forms it: 1 / (1 + exp(0 - x)).
 __device__ __forceinline__ float sigmoid1(float x) { return rn_div(1.0f, rn_add(1.0f, expf(rn_sub(0.0f, x)))); }
@@ -40,27 +34,6 @@ __device__ __forceinline__ float sigmoid1(float x) { return rn_div(1.0f, rn_add(
 // _convert_score of anchor i: cls_out_channels == 2 -> softmax class 1 of planes (0, 1); == 1 -> sigmoid of the single plane
 __device__ __forceinline__ float class_score(const float* __restrict__ cls, int n, int i, int cls_channels) {
   return cls_channels == 1 ? sigmoid1(cls[i]) : softmax2_class1(cls[i], cls[n + i]);
-}
-
-// np.argmax's order on (value, index) candidates: a NaN is above every number, then the larger value, then - among equals and among
-// NaNs - the lower index.  True when candidate (ov, oi) replaces (v, i).
-__device__ __forceinline__ bool argmax_takes(double ov, int oi, double v, int i) {
-  const bool on = ov != ov, vn = v != v;
-  if (on || vn) return on && (!vn || oi < i);
-  return ov > v || (ov == v && oi < i);
-}
-
-// The cell a lane starts from: its own first cell, or - an idle lane of a map smaller than the wave - cell 0 once more.  No lane holds a
-// sentinel: whatever the butterfly keeps is a cell of the map, and the duplicate of cell 0 ties with lane 0's own (same value, same index).
-__device__ __forceinline__ int argmax_start(int lane, int n) { return lane < n ? lane : 0; }
-
-__device__ __forceinline__ void wave_argmax(double& v, int& i) {
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) {
-    const double ov = __shfl_xor(v, s);
-    const int oi = __shfl_xor(i, s);
-    if (argmax_takes(ov, oi, v, i)) { v = ov; i = oi; }
-  }
 }
 
 __global__ __launch_bounds__(HDN_WAVE) void similarity_translation_kernel(const float* __restrict__ cls, const float* __restrict__ loc_c,

@@ -23,6 +23,8 @@ attribute the reference resolves at call time:
     {model_builder_e2e_unconstrained_v2, homo_model_builder}.triplet_loss   (install(train=True), while TRIPLET_TRAIN_BOUND) TripletMarginLossL1
     model_builder_e2e_unconstrained_v2.{select_xr_focal_fuse_smooth_l1_loss_top_k, select_l1_loss_c, select_cross_entropy_loss, select_l1_loss,
         kalyo_l1_loss}                                   (install(train=True), while SUP_LOSS_TRAIN_BOUND) the drop-ins of hdn_amd/losses.py
+    model_builder_e2e_unconstrained_v2.{lp_pick, combine_affine_c0_v2, combine_affine_lt0}   :27-28 (install(train=True), while
+        hdn.models.logpolar.Polar_Pick.get_polar_from_two_para_loc       SIMI_GEOMETRY_TRAIN_BOUND) the drop-ins of hdn_amd/simi_geometry.py
     hdn.tracker.tracker_builder.TRACKS['hdnTrackerHomoProje2e']   (install(tracker=True)) the device-resident tracker loop
 
 Training under install(train=True): every statement of the reference's training forwards that resolves to a drop-in is differentiable on the device -
@@ -42,7 +44,7 @@ import weakref
 
 import torch
 
-from . import affine, heads, homo_model, homography, logpolar, losses, share_feature, triplet, xcorr
+from . import affine, heads, homo_model, homography, logpolar, losses, share_feature, simi_geometry, triplet, xcorr
 
 _DLT = "homo_estimator.Deep_homography.Oneline_DLTv1"
 
@@ -150,6 +152,16 @@ SUP_LOSS_TRAIN_BOUND = True
 SUP_LOSS_SITE = "hdn.models.model_builder_e2e_unconstrained_v2"
 SUP_LOSS_NAMES = ("select_xr_focal_fuse_smooth_l1_loss_top_k", "select_l1_loss_c", "select_cross_entropy_loss", "select_l1_loss", "kalyo_l1_loss")
 
+# Does install(train=True) bind the drop-ins of hdn_amd.simi_geometry at the three names model_builder_e2e_unconstrained_v2 imports (:27-28: lp_pick,
+# combine_affine_c0_v2, combine_affine_lt0) and at Polar_Pick.get_polar_from_two_para_loc?  Set by the outcome of tools/simi_geometry_train_bench.py
+# (profiles/simi_geometry_train.json, "ahead"): True only while the reference's lines :377, :390-415 with the drop-ins inside are faster, forward and
+# backward at B = 32, than with their own PyTorch functions.
+SIMI_GEOMETRY_TRAIN_BOUND = True
+
+SIMI_GEOMETRY_SITE = "hdn.models.model_builder_e2e_unconstrained_v2"
+SIMI_GEOMETRY_NAMES = ("lp_pick", "combine_affine_c0_v2", "combine_affine_lt0")
+POLAR_PICK_SITE = ("hdn.models.logpolar", "Polar_Pick", "get_polar_from_two_para_loc")
+
 _MISSING = object()
 _saved = []  # (owner, attribute or dict key, original value, is_dict_item) in application order; undone by uninstall()
 
@@ -204,7 +216,9 @@ def install(strict: bool = False, modules: dict = None, tracker: bool = False, t
     is an nn.TripletMarginLoss with p = 1, swap False and reduction 'none') and, while SUP_LOSS_TRAIN_BOUND, the five SUP_LOSS_NAMES that
     model_builder_e2e_unconstrained_v2 imports from hdn.models.loss to the drop-ins of hdn_amd.losses (only where the attribute exists;
     select_xr_focal_fuse_smooth_l1_loss and select_l1_loss_lp, the WEIGHTED_MAP_LP: True branch, stay the reference's), so that the reference's
-    training forward runs on the drop-ins; everything else is unchanged.  Returns the list of (module, attribute) pairs that were rebound;
+    training forward runs on the drop-ins and, while SIMI_GEOMETRY_TRAIN_BOUND, the three SIMI_GEOMETRY_NAMES that the same module imports and
+    Polar_Pick.get_polar_from_two_para_loc to the drop-ins of hdn_amd.simi_geometry (only where the attribute exists; the method keeps the one it
+    replaces for a points table that is not the analytic one); everything else is unchanged.  Returns the list of (module, attribute) pairs that were rebound;
     with strict=True a site that cannot be imported raises instead of being skipped.  uninstall() reverses it."""
     done = []
 
@@ -273,6 +287,18 @@ def install(strict: bool = False, modules: dict = None, tracker: bool = False, t
             if m is not None and hasattr(m, name):
                 _rebind(m, name, losses.DROP_INS[name])
                 done.append((SUP_LOSS_SITE, name))
+
+    if train and SIMI_GEOMETRY_TRAIN_BOUND:
+        m = get(SIMI_GEOMETRY_SITE)
+        for name in SIMI_GEOMETRY_NAMES:
+            if m is not None and hasattr(m, name):
+                _rebind(m, name, simi_geometry.DROP_INS[name])
+                done.append((SIMI_GEOMETRY_SITE, name))
+        mod_name, cls_name, meth = POLAR_PICK_SITE
+        klass = getattr(get(mod_name), cls_name, None)
+        if isinstance(klass, type) and meth in klass.__dict__:
+            _rebind(klass, meth, simi_geometry.make_get_polar(klass.__dict__[meth]))
+            done.append((mod_name, cls_name + "." + meth))
 
     if tracker:
         tb = get("hdn.tracker.tracker_builder")

@@ -477,6 +477,62 @@ int hdn_sup_losses_bwd_f32(const float* cls, const float* label_cls, const float
                            int S_lp, int n_rows, int C, int topk_per_sample, int form, void* stream);
 
 /*
+ * The similarity model's training geometry between the head maps and the samplers (model_builder_e2e_unconstrained_v2.py:377, :390-415), csrc/simi_geometry.hip.
+ * fp32 throughout, every operation individually rounded (no contraction), no atomics, no host read; argmax order: csrc/argmax_order.h (NaN first, the
+ * larger value, the lower index).  n = S S; point(i) = (ori + stride (i % S), ori + stride (i / S)), ori = -(S / 2) stride, as generate_points(stride, S).
+ *
+ * hdn_point_pick_f32: one wave per sample.  cls [B,2,S,S], loc [B,2,S,S] (mode 0) or [B,4,S,S] (mode 1), best_idx int32 [B].
+ *   mode 0 (Polar_Pick.get_polar_from_two_para_loc, logpolar.py:304-324): best = argmax_i cls[b,1,i]; out [B,2]: out[b,c] = point_c(best) - mult loc[b,c,best].
+ *   mode 1 (lp_pick, point.py:35-53): best = argmax_i softmax2_class1(cls[b,0,i], cls[b,1,i]); out [2,B]: out[0,b] = scale =
+ *          expf((px - mult loc[b,0,best]) (float)mag), out[1,b] = rot = (py - mult loc[b,2,best]) (float)rot_unit.
+ * hdn_point_pick_bwd_f32: grad_loc (the shape of loc), every element written: zero, except [b,c,best] = -grad_out[b,c] mult (mode 0), [b,0,best] =
+ *   -((grad_out[0,b] out[0,b]) mag) mult and [b,2,best] = -(grad_out[1,b] rot_unit) mult (mode 1; `out` is the forward's, unused in mode 0).  A best_idx
+ *   outside [0, n) gives a zero row.
+ * cls_channels != 2, B < 1, S < 1, stride < 1, a mode that is not 0 or 1 -> HDN_E_SHAPE; S > 1024 or stride > 4096 -> HDN_E_LIMIT; a NULL pointer -> HDN_E_NULL.
+ */
+int hdn_point_pick_f32(const float* cls, const float* loc, float* out, int* best_idx, int B, int S, int cls_channels, int mode, int stride, float mult,
+                       double mag, double rot_unit, void* stream);
+int hdn_point_pick_bwd_f32(const int* best_idx, const float* grad_out, const float* out_or_null, float* grad_loc, int B, int S, int mode, float mult,
+                           double mag, double rot_unit, void* stream);
+
+/*
+ * hdn_simi_affine_f32: out [B,2,3] = [[a, -c, t0], [c, a, t1]], a = sc cosf(rot), c = sc sinf(rot), t0 = ((-a U - (-c) V) + W0) [/ out_sz],
+ * t1 = ((-c U - a V) + W1) [/ out_sz]; one thread per sample.  nm_shift [B,2], scale, rot [B]; cx, cy [B] or both NULL (then the scalars are used).
+ *   kind 0 (combine_affine_c0_v2, transform.py:442): sc = (float)(out_sz / in_sz) scale, U = (cx - out_sz / 2) in_sz / out_sz (fp32 steps for a vector,
+ *          double then rounded for the scalar), V likewise from cy, W = nm_shift, the division iff scale_h.
+ *   kind 1 (combine_affine_lt0, transform.py:486): sc = scale, U = nm_shift[b,0] + in_sz / 2, V = nm_shift[b,1] + in_sz / 2, W = (cx, cy), no division.
+ * hdn_simi_affine_bwd_f32: grad [B,2,3] -> the gradients of nm_shift [B,2], scale [B], rot [B]; each may be NULL (not all).
+ * B < 1, a kind that is not 0 or 1, in_sz or out_sz not positive, no gradient asked for -> HDN_E_SHAPE; exactly one of cx, cy NULL, or a NULL required pointer -> HDN_E_NULL.
+ */
+int hdn_simi_affine_f32(const float* nm_shift, const float* scale, const float* rot, const float* cx_or_null, const float* cy_or_null, double cx_scalar,
+                        double cy_scalar, float* out, int B, int kind, int scale_h, double in_sz, double out_sz, void* stream);
+int hdn_simi_affine_bwd_f32(const float* nm_shift, const float* scale, const float* rot, const float* cx_or_null, const float* cy_or_null,
+                            double cx_scalar, double cy_scalar, const float* grad, float* grad_nm_shift_or_null, float* grad_scale_or_null,
+                            float* grad_rot_or_null, int B, int kind, int scale_h, double in_sz, double out_sz, void* stream);
+
+/*
+ * hdn_simi_warps_f32: model_builder_e2e_unconstrained_v2.py:390-415 in one launch, one wave per sample.  cls_lp [B,2,S,S], loc_lp [B,4,S,S], polar [B,2],
+ * temp_cx, temp_cy [B], search_poly [B,4,2] ->
+ *   best_idx int32 [B], scale, rot [B]          mode 1 of hdn_point_pick_f32 with mult = stride_lp
+ *   affine_m          kind 0 (out_sz / 2, out_sz / 2, polar, scale, rot, scale_h)          affine_m_c_aug    kind 0 (temp_cx, temp_cy, 0, 1, 0, scale_h)
+ *   affine_m_lt0      kind 1 (out_sz / 2, out_sz / 2, polar, 1 / scale, -rot)              affine_m_lt0_aug  kind 1 (temp_cx, temp_cy, 0, 1, 0)      each [B,2,3]
+ *   pred_points [B,3,4] = [affine_m_lt0; 0 0 1] [x; y; 1] of the four corners of search_poly, aug_sear_points likewise from affine_m_lt0_aug
+ *   (a row is (m0 x + m1 y) + m2 1).
+ * hdn_simi_warps_bwd_f32: upstream gradients of scale, rot [B], affine_m, affine_m_lt0 [B,2,3], pred_points [B,3,4] (each may be NULL = zero) ->
+ *   grad_loc_lp [B,4,S,S] (every element written) and grad_polar [B,2]; each may be NULL (not both).  best_idx, scale, rot are the forward's.
+ * Error rules of hdn_point_pick_f32 and hdn_simi_affine_f32.
+ */
+int hdn_simi_warps_f32(const float* cls_lp, const float* loc_lp, const float* polar, const float* temp_cx, const float* temp_cy,
+                       const float* search_poly, int* best_idx, float* scale, float* rot, float* affine_m, float* affine_m_lt0, float* affine_m_c_aug,
+                       float* affine_m_lt0_aug, float* pred_points, float* aug_sear_points, int B, int S, int cls_channels, int stride, float stride_lp,
+                       double mag, double rot_unit, double in_sz, double out_sz, void* stream);
+int hdn_simi_warps_bwd_f32(const int* best_idx, const float* scale, const float* rot, const float* polar, const float* search_poly,
+                           const float* grad_scale_or_null, const float* grad_rot_or_null, const float* grad_affine_m_or_null,
+                           const float* grad_affine_m_lt0_or_null, const float* grad_pred_points_or_null, float* grad_loc_lp_or_null,
+                           float* grad_polar_or_null, int B, int S, float stride_lp, double mag, double rot_unit, double in_sz, double out_sz,
+                           void* stream);
+
+/*
  * Device-resident frame handling: the uint8 frame [H,W,C] (HWC, BGR as cv2.imread delivers it) is
  * uploaded once; crops and warps are kernels.  `params` / `M` are DEVICE float64 arrays so that positions and homographies
  * produced on the device never visit the host.
