@@ -153,6 +153,8 @@ SIGNATURES = {
     "hdn_simi_affine_bwd_f32": (_i, [_c_float_p] * 5 + [ctypes.c_double] * 2 + [_c_float_p] * 4 + [_i] * 3 + [ctypes.c_double] * 2 + [ctypes.c_void_p]),
     "hdn_simi_warps_f32": (_i, [_c_float_p] * 15 + [_i] * 4 + [ctypes.c_float] + [ctypes.c_double] * 4 + [ctypes.c_void_p]),
     "hdn_simi_warps_bwd_f32": (_i, [_c_float_p] * 12 + [_i] * 2 + [ctypes.c_float] + [ctypes.c_double] * 4 + [ctypes.c_void_p]),
+    "hdn_corner_losses_f32": (_i, [_c_float_p] * 9 + [_i, ctypes.c_void_p]),
+    "hdn_corner_losses_bwd_f32": (_i, [_c_float_p] * 12 + [_i, ctypes.c_void_p]),
 }
 
 ERRORS = {

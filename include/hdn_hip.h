@@ -533,6 +533,38 @@ int hdn_simi_warps_bwd_f32(const int* best_idx, const float* scale, const float*
                            void* stream);
 
 /*
+ * hdn_corner_losses_f32: the corner supervision of model_builder_e2e_unconstrained_v2.py:441-444, :481-523 and :552-556 in one launch (one workgroup;
+ * a sample on eight lanes), nothing read by the host.  H_mat [B,3,3], pred_points [B,3,4] (rows x, y, w), aug_sear_points [B,3,4] or NULL,
+ * template_poly [B,4,2], x [B,8] (batch_out['x']), if_pos, if_unsup [B], all fp32 -> out [6] fp32, counts [6] int32.
+ *   The sets, float comparisons as .eq() makes them (a flag that is neither 0 nor 1 fails them): sup: if_unsup == 0; sup_pos: if_unsup == 0 and
+ *   if_pos == 1; sup_neg: if_unsup == 0 and if_pos == 0; unsup: if_unsup == 1; unsup_pos: if_pos if_unsup == 1; neg: if_pos == 0.
+ *   counts = n_sup, n_sup_pos, n_sup_neg, n_unsup, n_unsup_pos, n_neg.   c_j = column j of [[0,0],[0,127],[127,127],[127,0]].
+ *   out[0] cor_err      = (sum over sup_pos, j, xy of |P_xy / P_w - template_poly|) / n_sup_pos / 4,  P = H_mat[b] pred_points[b]
+ *   out[1] cor_err_aug  = the same sum of |aug_sear_points[b][0:2] - template_poly| (no division by w); 0 when the pointer is NULL
+ *   out[2] cor_err_sim  = (sum over unsup_pos of |pred_points[b][0:2] - template_poly|) / n_unsup_pos / 4 (no division by w)
+ *   out[3] cor_pos_loss = (sum over sup_pos and r < 8 of k(delta[b][r] - x[b][r])) / (8 n_sup_pos + 1), k(d) = d d / 2 where |d| < 1, else |d| - 1/2;
+ *          off = pred_points_xy / pred_points_w - template_poly (fp32), H_gt = the system and elimination of hdn_dlt_solve_f32 on
+ *          (template_poly[b], off) in float64, rounded to fp32 once, Q = H_gt [c_j; 1], delta[b][2 j + c] = Q_c / Q_w - c_j[c]
+ *   out[4] cor_neg_loss = (sum over neg - supervised or not - of k(-x[b][r])) / (8 n_neg + 1) where n_sup_neg > 0, else 0 (the reference computes it
+ *          over every negative and reports it with a supervised one)
+ *   out[5] cor_loss     = out[3] + out[4]
+ *   An empty set gives 0.  A sample contributes to a term only through the sets above; its data is not read for the others.  Sums have a fixed
+ *   order: the outputs are bit-reproducible.  Unlike the reference, whose DLT_solve inverts every sample of the batch (torch.inverse raises for the
+ *   whole batch on one singular system), only the sup_pos samples are solved here.
+ * hdn_corner_losses_bwd_f32: grad_out [6] -> grad_H_mat [B,3,3], grad_pred_points [B,3,4] (the w row included), grad_aug_sear_points [B,3,4],
+ *   grad_x [B,8]; each may be NULL (not all).  Every element is written, rows of samples outside the sets are 0.  abs'(0) = 0, |d| = 1 takes the
+ *   linear branch; the path through H_gt is the adjoint solve of hdn_dlt_solve_bwd_f32, recomputed from the inputs.  First order only;
+ *   template_poly and the flags get no gradient.
+ * B < 1 or no gradient asked for -> HDN_E_SHAPE; B > 65536 -> HDN_E_LIMIT; a NULL required pointer, or grad_aug_sear_points without
+ * aug_sear_points -> HDN_E_NULL; nothing is launched then.
+ */
+int hdn_corner_losses_f32(const float* H_mat, const float* pred_points, const float* aug_sear_points_or_null, const float* template_poly,
+                          const float* x, const float* if_pos, const float* if_unsup, float* out, int* counts, int B, void* stream);
+int hdn_corner_losses_bwd_f32(const float* H_mat, const float* pred_points, const float* aug_sear_points_or_null, const float* template_poly,
+                              const float* x, const float* if_pos, const float* if_unsup, const float* grad_out, float* grad_H_mat_or_null,
+                              float* grad_pred_points_or_null, float* grad_aug_sear_points_or_null, float* grad_x_or_null, int B, void* stream);
+
+/*
  * Device-resident frame handling: the uint8 frame [H,W,C] (HWC, BGR as cv2.imread delivers it) is
  * uploaded once; crops and warps are kernels.  `params` / `M` are DEVICE float64 arrays so that positions and homographies
  * produced on the device never visit the host.
