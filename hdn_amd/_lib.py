@@ -145,6 +145,8 @@ SIGNATURES = {
     "hdn_affine_sample_bwd_f32": (_i, [_c_float_p] * 6 + [ctypes.c_longlong] + [_i] * 6 + [ctypes.c_void_p]),
     "hdn_triplet_l1_f32": (_i, [_c_float_p] * 5 + [_i] * 4 + [ctypes.c_float] * 2 + [ctypes.c_void_p]),
     "hdn_triplet_l1_bwd_f32": (_i, [_c_float_p] * 8 + [_i] * 4 + [ctypes.c_float] * 2 + [ctypes.c_void_p]),
+    "hdn_triplet_l1_mean_f32": (_i, [_c_float_p] * 8 + [_i] * 4 + [ctypes.c_float] * 3 + [ctypes.c_void_p]),
+    "hdn_triplet_l1_mean_bwd_f32": (_i, [_c_float_p] * 9 + [_i] * 4 + [ctypes.c_float] * 3 + [ctypes.c_void_p]),
     "hdn_sup_losses_f32": (_i, [_c_float_p] * 12 + [_i] * 7 + [ctypes.c_void_p]),
     "hdn_sup_losses_bwd_f32": (_i, [_c_float_p] * 17 + [_i] * 7 + [ctypes.c_void_p]),
     "hdn_point_pick_f32": (_i, [_c_float_p] * 4 + [_i] * 5 + [ctypes.c_float] + [ctypes.c_double] * 2 + [ctypes.c_void_p]),

@@ -161,3 +161,196 @@ int hdn_triplet_l1_bwd_f32(const float* anchor, const float* positive, const flo
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------------------------------------
+// The flag-selected mean of the rows above: hdn_triplet_l1_mean_f32, hdn_triplet_l1_mean_bwd_f32 (formulas: include/hdn_hip.h).  The two triplet terms
+// of the training forwards (model_builder_e2e_unconstrained_v2.py:430-440, homo_model_builder.py:174-199) select their samples with nonzero() and
+// divide by a length read on the host; here the sets are decided from if_pos / if_unsup in the kernels, so nothing is read by the host.
+//
+// Forward, two launches in one call.  rows: one wave per row of [N,R,D], as fwd_kernel; the row's clamped loss (row_v(), the bits of the kernels
+// above) goes to partial[row], 0 for a row of a sample that is not used, whose data is not read.  finish: ONE workgroup of 1024 threads; thread t
+// adds partial[t], partial[t + 1024], ... in ascending order, a wave adds its lanes in a fixed xor tree, thread 0 adds the sixteen waves in
+// ascending order: the order depends on (N, R) alone, no float atomics, no hand-off between workgroups inside a launch (the stream orders the two
+// kernels).  Backward: one wave per gradient row, every element written exactly once.  Each workgroup counts the sets itself (integers: no order).
+// Bounds: a flag index is < N, a row index < N R, an element index < N R D; partial has N R floats.
+namespace hdn {
+namespace triplet {
+
+constexpr int MEAN_MAX_N = 1 << 16;
+constexpr int FIN_BLOCK = 1024;
+
+// the reference's predicates, float comparisons as .eq() makes them: a flag of 0.5 or NaN fails both
+__device__ __forceinline__ bool is_sel(float pos, float un) { return rn_mul(pos, un) == 1.f; }  // (if_pos * if_unsup).eq(1)
+__device__ __forceinline__ bool is_neg(float pos) { return pos == 0.f; }                        // if_pos.eq(0)
+
+// is a sample read?  rule 0: the selected ones; rule 1: the selected ones where the batch has a negative, every sample otherwise; none while n_sel = 0
+__device__ __forceinline__ bool sample_used(bool sel, int rule, int n_sel, int n_neg) { return n_sel > 0 && (sel || (rule == 1 && n_neg == 0)); }
+
+// n_sel and n_neg of the batch, the same in every thread.  Every thread of the workgroup calls it (one barrier); red: 2 BLOCK / 64 ints of LDS.
+template <int BLOCK>
+__device__ __forceinline__ void count_sets(const float* __restrict__ if_pos, const float* __restrict__ if_unsup, int N, int* red, int& n_sel,
+                                           int& n_neg) {
+  int cs = 0, cn = 0;
+  for (int i = threadIdx.x; i < N; i += BLOCK) {
+    const float pos = if_pos[i];
+    cs += is_sel(pos, if_unsup[i]) ? 1 : 0;
+    cn += is_neg(pos) ? 1 : 0;
+  }
+#pragma unroll
+  for (int m = HDN_WAVE / 2; m >= 1; m >>= 1) {
+    cs += __shfl_xor(cs, m, HDN_WAVE);
+    cn += __shfl_xor(cn, m, HDN_WAVE);
+  }
+  if ((threadIdx.x & (HDN_WAVE - 1)) == 0) {
+    red[2 * (threadIdx.x / HDN_WAVE)] = cs;
+    red[2 * (threadIdx.x / HDN_WAVE) + 1] = cn;
+  }
+  __syncthreads();
+  n_sel = 0, n_neg = 0;
+  for (int w = 0; w < BLOCK / HDN_WAVE; ++w) {
+    n_sel += red[2 * w];
+    n_neg += red[2 * w + 1];
+  }
+}
+
+__global__ __launch_bounds__(HDN_BLOCK) void mean_rows_kernel(const float* __restrict__ a, const float* __restrict__ p, const float* __restrict__ n,
+                                                              const float* __restrict__ if_pos, const float* __restrict__ if_unsup,
+                                                              float* __restrict__ partial, int N, int R, int D, int rule, float margin, float eps) {
+  __shared__ int red[2 * ROWS];
+  int n_sel = 1, n_neg = 1;                                    // rule 0 asks for neither: a selected sample is used
+  if (rule == 1) count_sets<HDN_BLOCK>(if_pos, if_unsup, N, red, n_sel, n_neg);   // uniform over the launch: every thread meets the barrier
+  const int lane = threadIdx.x & (HDN_WAVE - 1);
+  const long long row = (long long)blockIdx.x * ROWS + (threadIdx.x / HDN_WAVE);
+  if (row >= (long long)N * R) return;                         // wave-uniform, after the barrier
+  const int s = (int)(row / R);
+  float out = 0.f;
+  if (sample_used(is_sel(if_pos[s], if_unsup[s]), rule, n_sel, n_neg)) {   // wave-uniform; nothing of an unused sample is read
+    const size_t off = size_t(row) * size_t(D);
+    const float v = row_v(a + off, p + off, n + off, D, lane, margin, eps);
+    out = v < 0.f ? 0.f : v;                                   // clamp_min: v >= 0 and NaN pass
+  }
+  if (lane == 0) partial[row] = out;
+}
+
+__global__ __launch_bounds__(FIN_BLOCK) void mean_finish_kernel(const float* __restrict__ partial, const float* __restrict__ if_pos,
+                                                                const float* __restrict__ if_unsup, float* __restrict__ out,
+                                                                int* __restrict__ counts, int N, long long rows, int rule, float denom) {
+  __shared__ int red[2 * (FIN_BLOCK / HDN_WAVE)];
+  __shared__ float red_f[FIN_BLOCK / HDN_WAVE];
+  int n_sel, n_neg;
+  count_sets<FIN_BLOCK>(if_pos, if_unsup, N, red, n_sel, n_neg);
+  float acc = 0.f;
+  for (long long i = threadIdx.x; i < rows; i += FIN_BLOCK) acc = rn_add(acc, partial[i]);
+#pragma unroll
+  for (int m = HDN_WAVE / 2; m >= 1; m >>= 1) acc = rn_add(acc, __shfl_xor(acc, m, HDN_WAVE));
+  if ((threadIdx.x & (HDN_WAVE - 1)) == 0) red_f[threadIdx.x / HDN_WAVE] = acc;
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  float S = red_f[0];
+  for (int w = 1; w < FIN_BLOCK / HDN_WAVE; ++w) S = rn_add(S, red_f[w]);
+  const float ns = (float)n_sel;
+  out[0] = n_sel > 0 ? (rule == 0 ? rn_div(rn_div(S, denom), ns) : rn_div(rn_div(S, ns), denom)) : 0.f;
+  counts[0] = n_sel;
+  counts[1] = n_neg;
+}
+
+__global__ __launch_bounds__(HDN_BLOCK) void mean_bwd_kernel(const float* __restrict__ a, const float* __restrict__ p, const float* __restrict__ n,
+                                                             const float* __restrict__ if_pos, const float* __restrict__ if_unsup,
+                                                             const float* __restrict__ gout, float* __restrict__ ga, float* __restrict__ gp,
+                                                             float* __restrict__ gn, int N, int R, int D, int rule, float denom, float margin,
+                                                             float eps) {
+  __shared__ int red[2 * ROWS];
+  int n_sel, n_neg;
+  count_sets<HDN_BLOCK>(if_pos, if_unsup, N, red, n_sel, n_neg);   // the sets as the forward found them
+  const int lane = threadIdx.x & (HDN_WAVE - 1);
+  const long long row = (long long)blockIdx.x * ROWS + (threadIdx.x / HDN_WAVE);
+  if (row >= (long long)N * R) return;                         // wave-uniform, after the barrier
+  const int s = (int)(row / R);
+  const size_t off = size_t(row) * size_t(D);
+  bool active = false;
+  if (sample_used(is_sel(if_pos[s], if_unsup[s]), rule, n_sel, n_neg))
+    active = row_v(a + off, p + off, n + off, D, lane, margin, eps) >= 0.f;   // clamp_min's rule, on the forward's bits
+  if (!active) {                                               // wave-uniform
+    for (int j = lane; j < D; j += HDN_WAVE) {
+      if (ga) ga[off + j] = 0.f;
+      if (gp) gp[off + j] = 0.f;
+      if (gn) gn[off + j] = 0.f;
+    }
+    return;
+  }
+  const float g = gout[0], ns = (float)n_sel;                  // n_sel > 0: a sample is used
+  const float c = rule == 0 ? rn_div(rn_div(g, denom), ns) : rn_div(rn_div(g, ns), denom);
+  for (int j = lane; j < D; j += HDN_WAVE) {
+    const float av = a[off + j];
+    const float s_ap = sgn(rn_add(rn_sub(av, p[off + j]), eps)), s_an = sgn(rn_add(rn_sub(av, n[off + j]), eps));
+    if (ga) ga[off + j] = rn_mul(c, rn_sub(s_ap, s_an));       // c {0, +-1, +-2}: exact
+    if (gp) gp[off + j] = rn_mul(-c, s_ap);
+    if (gn) gn[off + j] = rn_mul(c, s_an);
+  }
+}
+
+static int mean_check_dims(int N, int R, int D, int rule, float denom) {
+  if (N <= 0 || R <= 0 || D <= 0 || (rule != 0 && rule != 1) || !(denom > 0.f)) return HDN_E_SHAPE;
+  return HDN_OK;
+}
+
+static bool mean_over_limit(int N, int R, int D) { return N > MEAN_MAX_N || (long long)N * R > (1LL << 30) || D > (1 << 20); }
+
+}  // namespace triplet
+}  // namespace hdn
+
+extern "C" {
+
+int hdn_triplet_l1_mean_f32(const float* anchor, const float* positive, const float* negative, const float* if_pos, const float* if_unsup,
+                            float* partial, float* out, int* counts, int N, int R, int D, int rule, float denom, float margin, float eps,
+                            void* stream) {
+  using namespace hdn;
+  if (!anchor || !positive || !negative || !if_pos || !if_unsup || !partial || !out || !counts) return HDN_E_NULL;
+  if (triplet::mean_check_dims(N, R, D, rule, denom)) return HDN_E_SHAPE;
+  if (triplet::mean_over_limit(N, R, D)) return HDN_E_LIMIT;
+  const long long rows = (long long)N * R, in_bytes = rows * D * 4, flag_bytes = (long long)N * 4;
+  const void* const outs[3] = {partial, out, counts};
+  const long long out_bytes[3] = {rows * 4, 4, 8};
+  for (int i = 0; i < 3; ++i) {
+    for (const float* in : {anchor, positive, negative})
+      if (bytes_overlap(outs[i], out_bytes[i], in, in_bytes)) return HDN_E_ALIAS;
+    for (const float* in : {if_pos, if_unsup})
+      if (bytes_overlap(outs[i], out_bytes[i], in, flag_bytes)) return HDN_E_ALIAS;
+    for (int j = 0; j < i; ++j)
+      if (bytes_overlap(outs[i], out_bytes[i], outs[j], out_bytes[j])) return HDN_E_ALIAS;
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(triplet::mean_rows_kernel, dim3((unsigned)((rows + triplet::ROWS - 1) / triplet::ROWS)), dim3(HDN_BLOCK), 0, st, anchor,
+                     positive, negative, if_pos, if_unsup, partial, N, R, D, rule, margin, eps);
+  if (const int rc = launch_status()) return rc;
+  hipLaunchKernelGGL(triplet::mean_finish_kernel, dim3(1), dim3(triplet::FIN_BLOCK), 0, st, partial, if_pos, if_unsup, out, counts, N, rows, rule,
+                     denom);
+  return launch_status();
+}
+
+int hdn_triplet_l1_mean_bwd_f32(const float* anchor, const float* positive, const float* negative, const float* if_pos, const float* if_unsup,
+                                const float* grad_out, float* grad_a_or_null, float* grad_p_or_null, float* grad_n_or_null, int N, int R, int D,
+                                int rule, float denom, float margin, float eps, void* stream) {
+  using namespace hdn;
+  if (!anchor || !positive || !negative || !if_pos || !if_unsup || !grad_out) return HDN_E_NULL;
+  if (triplet::mean_check_dims(N, R, D, rule, denom) || (!grad_a_or_null && !grad_p_or_null && !grad_n_or_null)) return HDN_E_SHAPE;
+  if (triplet::mean_over_limit(N, R, D)) return HDN_E_LIMIT;
+  const long long rows = (long long)N * R, in_bytes = rows * D * 4, flag_bytes = (long long)N * 4;
+  float* const outs[3] = {grad_a_or_null, grad_p_or_null, grad_n_or_null};
+  for (int i = 0; i < 3; ++i) {
+    if (!outs[i]) continue;
+    for (const float* in : {anchor, positive, negative})
+      if (bytes_overlap(outs[i], in_bytes, in, in_bytes)) return HDN_E_ALIAS;
+    for (const float* in : {if_pos, if_unsup})
+      if (bytes_overlap(outs[i], in_bytes, in, flag_bytes)) return HDN_E_ALIAS;
+    if (bytes_overlap(outs[i], in_bytes, grad_out, 4)) return HDN_E_ALIAS;
+    for (int j = 0; j < i; ++j)
+      if (outs[j] && bytes_overlap(outs[i], in_bytes, outs[j], in_bytes)) return HDN_E_ALIAS;
+  }
+  hipLaunchKernelGGL(triplet::mean_bwd_kernel, dim3((unsigned)((rows + triplet::ROWS - 1) / triplet::ROWS)), dim3(HDN_BLOCK), 0,
+                     static_cast<hipStream_t>(stream), anchor, positive, negative, if_pos, if_unsup, grad_out, grad_a_or_null, grad_p_or_null,
+                     grad_n_or_null, N, R, D, rule, denom, margin, eps);
+  return launch_status();
+}
+
+}  // extern "C"

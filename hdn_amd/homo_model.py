@@ -253,9 +253,70 @@ class HomoModelBuilder(nn.Module):
             "homo_neg_loss": homo_neg_loss,
         }
 
-    def training_forward(self, data):
+    def _host_free_constants(self, B, H, W, dev):
+        """(M_tile, M_tile_inv, batch_inds) of training_forward(host_free=True) as device buffers, built once per (B, H, W, device) - outside any
+        capture, since building them uploads.  The inverse of the literal of :139-142 is written down: [[1/63.5, 0, -1], [0, 1/63.5, -1], [0, 0, 1]]."""
+        cache = self.__dict__.setdefault("_hdn_host_free_constants", {})
+        key = (B, H, W, str(dev))
+        if key not in cache:
+            if dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(f"HomoModelBuilder.training_forward(host_free=True): the constants of (B, H, W) = {(B, H, W)} are not on {dev} "
+                                   "yet and building them uploads; run one forward outside the capture first (the warm-up does)")
+            M = torch.tensor([[63.5, 0.0, 63.5], [0.0, 63.5, 63.5], [0.0, 0.0, 1.0]], device=dev)
+            M_inv = torch.tensor([[1.0 / 63.5, 0.0, -1.0], [0.0, 1.0 / 63.5, -1.0], [0.0, 0.0, 1.0]], device=dev)
+            batch_inds = torch.arange(0, B * H * W, H * W, device=dev).unsqueeze(1).expand(B, H * W).reshape(-1)
+            cache[key] = (M.unsqueeze(0).expand(B, 3, 3).contiguous(), M_inv.unsqueeze(0).expand(B, 3, 3).contiguous(), batch_inds)
+        return cache[key]
+
+    def _training_forward_host_free(self, data):
+        """training_forward(host_free=True): see there."""
+        from . import _lib
+        from .triplet import triplet_l1_mean
+
+        sf = self.ShareFeature
+        B, H, W = _check_data(data)
+        for k in ("if_pos", "if_unsup"):
+            if k not in data:
+                raise KeyError(f"data['{k}'] missing: host_free=True decides the sample sets on the device and needs both flags as [B] float")
+            if tuple(data[k].shape) != (B,):
+                raise ValueError(f"data['{k}'] must be [{B}] (one flag per sample), got {list(data[k].shape)}")
+        org, inp, h4p, patch_inds = data["org_imgs"], data["input_tensors"], data["h4p"], data["patch_indices"]
+        if_pos, if_unsup = data["if_pos"], data["if_unsup"]
+        dev = _lib.require_device(inp, if_pos, if_unsup)        # a flag on the host would be an upload
+        p1 = sf(inp[:, :1].contiguous())
+        p2 = sf(inp[:, 1:].contiguous())
+        x = self.backbone(torch.cat((p1, p2), dim=1))
+        x = self.fc(self.avgpool(x).view(x.size(0), -1))
+        H_mat = G.DLT_solve(h4p, x).squeeze(1)
+        M_tile, M_tile_inv, batch_inds = self._host_free_constants(B, H, W, dev)
+        pred = G.transform(H, W, M_tile_inv, H_mat, M_tile, org[:, :1], patch_inds, batch_inds)
+        pf = sf(pred)
+        value, counts = triplet_l1_mean(p2, pf, p1, if_pos, if_unsup, rule=1, denom=127 * 127, margin=1.0, eps=1e-6)
+        # homo_neg_loss (:176-178) without x[neg_ids]: the other samples' offsets are replaced (not multiplied) by 0 before the norm, whose
+        # gradient at 0 is 0, so a NaN in them reaches nothing; gated on n_neg, where the reference tests neg_ids.shape[0]
+        n_neg = counts[1]
+        x_neg = torch.where(if_pos.eq(0).unsqueeze(1), x, torch.zeros_like(x))
+        neg_sum = torch.sum(torch.norm(x_neg, p=2, dim=1))
+        homo_neg_loss = torch.where(n_neg > 0, neg_sum / n_neg.clamp(min=1).to(torch.float32), torch.zeros_like(neg_sum))
+        return {
+            "feature_loss": value.unsqueeze(0),
+            "pred_I2_d": pred[:1],
+            "x": x,
+            "H_mat": H_mat,
+            "patch_2_res_d": p2[:1],
+            "pred_I2_CnnFeature_d": pf[:1],
+            "homo_neg_loss": homo_neg_loss,
+        }
+
+    def training_forward(self, data, host_free: bool = False):
         """The reference's training forward (homo_model_builder.py:154-215) on the differentiable HIP operators; the returned dict has forward()'s
         keys and every loss carries the graph to the regressor and to ShareFeature.
+
+        host_free=True: the same forward with nothing read by or uploaded from the host, so that it can be captured in a graph.  data['if_pos']
+        and data['if_unsup'] are required, float [B] on the device.  feature_loss is hdn_amd.triplet_l1_mean(patch_2, pred_feat, patch_1, if_pos,
+        if_unsup, rule=1) (the sets and the divisor are decided in the kernel; 0 with no selected sample, where the reference divides by zero),
+        homo_neg_loss a masked expression on x [B,8] gated with torch.where on the kernel's n_neg, and M, its inverse (written down, no
+        torch.inverse and its error check) and batch_inds are device buffers built once per (B, H, W, device), outside any capture.
 
         In the reference's order: ShareFeature on each of the two channels (two calls, as :154-155: in train() mode each normalises with its own
         batch statistics and updates the running buffers), the module's own backbone / avgpool / fc (never the folded inference trunk),
@@ -273,6 +334,8 @@ class HomoModelBuilder(nn.Module):
             raise RuntimeError("HomoModelBuilder.training_forward: ShareFeature is in eval() mode with hip_train False, where it runs the fused "
                                "inference kernel and detaches; call .train(), or set ShareFeature.hip_train = True to keep the running statistics "
                                "and the graph")
+        if host_free:
+            return self._training_forward_host_free(data)
         B, H, W = _check_data(data)
         org, inp, h4p, patch_inds = data["org_imgs"], data["input_tensors"], data["h4p"], data["patch_indices"]
         dev = inp.device

@@ -13,6 +13,14 @@ triplet_l1() is inference-only by default: with autograd recording, an input tha
 differentiable=True (what TripletMarginLossL1 passes; hdn_amd.install.install(train=True) binds that module at the two `triplet_loss` sites while
 TRIPLET_TRAIN_BOUND) such a call goes through a torch.autograd.Function whose forward is the same launch and whose backward is first order only.
 Every output is bit-reproducible between calls (no atomics).  There is no CPU fallback.
+
+    triplet_l1_mean(anchor, positive, negative, if_pos, if_unsup, rule) -> (value, counts)
+                                                                 <- model_builder_e2e_unconstrained_v2.py:430-440 (rule 0: sim_loss)
+                                                                    homo_model_builder.py:174-199 (rule 1: feature_loss)
+
+is each site's whole term - the nonzero() selection, the rows, the sum and the division by a length that the reference reads on the host - with
+the sample sets decided from the flags in the kernels (hdn_triplet_l1_mean_f32 / hdn_triplet_l1_mean_bwd_f32), so that a training forward built on
+it can be captured in a graph.  `ids` needs the index list and therefore the host read; it remains for callers that hold one.
 """
 from __future__ import annotations
 
@@ -135,6 +143,95 @@ def triplet_l1(anchor, positive, negative, margin: float = 1.0, eps: float = 1e-
         _lib.require_device(anchor, positive, negative)
         return _TripletL1.apply(anchor, positive, negative, float(margin), float(eps), ids)
     return _launch(anchor, positive, negative, margin, eps, ids)
+
+
+# ------------------------------------------------------------------------------------------------------- the flag-selected mean: no host read
+def _check_mean(anchor, positive, negative, if_pos, if_unsup, rule, denom):
+    """(N, R, D) of the mean form: the inputs as _check sees them, flags [N], rule 0 or 1, denom > 0."""
+    N, R, D, _ = _check(anchor, positive, negative, None)
+    for k, v in (("if_pos", if_pos), ("if_unsup", if_unsup)):
+        if not isinstance(v, torch.Tensor):
+            raise TypeError(f"{k}: expected a torch.Tensor, got {type(v).__name__}")
+        if v.requires_grad:
+            raise ValueError(f"triplet_l1_mean has no gradient for {k}")
+        if tuple(v.shape) != (N,):
+            raise ValueError(f"{k} must be [{N}] (one flag per sample of the leading dimension), got {list(v.shape)}")
+    if rule not in (0, 1):
+        raise ValueError(f"rule must be 0 (similarity: model_builder_e2e_unconstrained_v2.py:430-440) or 1 (homography estimator: "
+                         f"homo_model_builder.py:174-199), got {rule!r}")
+    if not float(denom) > 0:
+        raise ValueError(f"denom must be > 0, got {denom!r}")
+    if anchor.numel() == 0:
+        raise ValueError(f"the inputs must not be empty, got {tuple(anchor.shape)}")
+    return N, R, D
+
+
+def _launch_mean(anchor, positive, negative, if_pos, if_unsup, rule, denom, margin, eps):
+    """One call of hdn_triplet_l1_mean_f32 -> (value 0-d fp32, counts int32 [2])."""
+    N, R, D = _check_mean(anchor, positive, negative, if_pos, if_unsup, rule, denom)
+    dev = _lib.require_device(anchor, positive, negative, if_pos, if_unsup)
+    a, p, n, fp, fu = (t.detach().contiguous() for t in (anchor, positive, negative, if_pos, if_unsup))
+    partial = torch.empty(N * R, dtype=torch.float32, device=dev)                     # (torch's caching allocator: no sync, graph-safe)
+    out, counts = torch.empty(1, dtype=torch.float32, device=dev), torch.empty(2, dtype=torch.int32, device=dev)
+    _lib.launch("triplet_l1_mean", dev, _lib.load().hdn_triplet_l1_mean_f32, _lib.ptr(a), _lib.ptr(p), _lib.ptr(n), _lib.ptr(fp), _lib.ptr(fu),
+                _lib.ptr(partial), _lib.ptr(out), _lib.ptr(counts), N, R, D, int(rule), float(denom), float(margin), float(eps))
+    return out[0], counts
+
+
+def triplet_l1_mean_backward(anchor, positive, negative, if_pos, if_unsup, grad_out, rule, denom=127 * 127, margin: float = 1.0,
+                             eps: float = 1e-6, need_anchor: bool = True, need_positive: bool = True, need_negative: bool = True):
+    """(grad_anchor | None, grad_positive | None, grad_negative | None), each of the inputs' full shape, of triplet_l1_mean for grad_out (one
+    element) = d L / d value: one call of hdn_triplet_l1_mean_bwd_f32.  The sets are recounted from the flags on the device; rows of unused
+    samples and inactive rows are zero, with an empty selection everything is.  Exact given each row's activity, bit-reproducible."""
+    need = (need_anchor, need_positive, need_negative)
+    if not any(need):
+        raise ValueError("triplet_l1_mean_backward: no gradient is asked for")
+    N, R, D = _check_mean(anchor, positive, negative, if_pos, if_unsup, rule, denom)
+    if not isinstance(grad_out, torch.Tensor) or grad_out.numel() != 1:
+        raise ValueError("grad_out must hold one element (the gradient of the 0-d value)")
+    dev = _lib.require_device(anchor, positive, negative, if_pos, if_unsup, grad_out)
+    a, p, n, fp, fu, g = (t.detach().contiguous() for t in (anchor, positive, negative, if_pos, if_unsup, grad_out))
+    grads = [torch.empty(anchor.shape, dtype=torch.float32, device=dev) if w else None for w in need]   # every element is written by the call
+    _lib.launch("triplet_l1_mean_backward", dev, _lib.load().hdn_triplet_l1_mean_bwd_f32, _lib.ptr(a), _lib.ptr(p), _lib.ptr(n), _lib.ptr(fp),
+                _lib.ptr(fu), _lib.ptr(g), _lib.opt(grads[0]), _lib.opt(grads[1]), _lib.opt(grads[2]), N, R, D, int(rule), float(denom),
+                float(margin), float(eps))
+    return tuple(grads)
+
+
+class _TripletL1Mean(torch.autograd.Function):
+    """(value, counts) of _launch_mean with a backward: hdn_triplet_l1_mean_bwd_f32 for the inputs that need it (first order only)."""
+
+    @staticmethod
+    def forward(ctx, anchor, positive, negative, if_pos, if_unsup, rule, denom, margin, eps):
+        ctx.save_for_backward(anchor, positive, negative, if_pos, if_unsup)
+        ctx.args = (rule, denom, margin, eps)
+        value, counts = _launch_mean(anchor, positive, negative, if_pos, if_unsup, rule, denom, margin, eps)
+        ctx.mark_non_differentiable(counts)
+        return value, counts
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_value, _grad_counts):
+        need = ctx.needs_input_grad[:3]
+        if not any(need):
+            return (None,) * 9
+        rule, denom, margin, eps = ctx.args
+        return triplet_l1_mean_backward(*ctx.saved_tensors, grad_value, rule, denom, margin, eps, *need) + (None,) * 6
+
+
+def triplet_l1_mean(anchor, positive, negative, if_pos, if_unsup, rule, denom=127 * 127, margin: float = 1.0, eps: float = 1e-6):
+    """The reference's two triplet terms without their nonzero() reads: anchor, positive, negative [N, ..., D] of one shape, if_pos, if_unsup
+    float [N] on the device -> (value 0-d, counts int32 [2] = n_sel, n_neg).  sel: if_pos * if_unsup == 1, neg: if_pos == 0, decided in the kernel.
+
+    rule 0 (sim_loss, model_builder_e2e_unconstrained_v2.py:430-440): the selected samples; value = sum / denom / n_sel.
+    rule 1 (feature_loss, homo_model_builder.py:174-199): the selected samples where the batch has a negative, every sample otherwise;
+    value = sum / n_sel / denom in both cases (the reference's own quirk).
+    n_sel == 0 gives 0 and zero gradients, where the reference skips the term (rule 0) or divides by zero (rule 1).  A sample that is not used
+    is not read: a NaN in it reaches neither the value nor a gradient.  The value carries the graph to the three inputs (first order only); the
+    flags must not require grad.  Bit-reproducible; capturable in a graph (nothing is read by or uploaded from the host)."""
+    _check_mean(anchor, positive, negative, if_pos, if_unsup, rule, denom)
+    _lib.require_device(anchor, positive, negative, if_pos, if_unsup)
+    return _TripletL1Mean.apply(anchor, positive, negative, if_pos, if_unsup, int(rule), float(denom), float(margin), float(eps))
 
 
 class TripletMarginLossL1(nn.Module):

@@ -415,6 +415,38 @@ int hdn_triplet_l1_bwd_f32(const float* anchor, const float* positive, const flo
                            float eps, void* stream);
 
 /*
+ * hdn_triplet_l1_mean_f32: the flag-selected mean of the loss rows above, the two triplet terms of the training forwards with their nonzero()
+ * selections and host-read divisors decided in the kernels (csrc/triplet_loss.hip); nothing is read by the host.  anchor, positive, negative
+ * [N,R,D], if_pos, if_unsup [N], all fp32 -> out [1] fp32, counts [2] int32 = n_sel, n_neg.  partial: N R floats of scratch, supplied by the caller.
+ *   The sets, float comparisons as .eq() makes them (a flag of 0.5 or NaN fails both):  sel: fp32(if_pos[b] if_unsup[b]) == 1;  neg: if_pos[b] == 0.
+ *   loss(b, r) = the row loss of hdn_triplet_l1_f32, computed by the same device function (the decision v >= 0 is made on the same bits).
+ *   S = sum of loss(b, r) over the rows of the used samples.
+ *   rule 0 (similarity model, model_builder_e2e_unconstrained_v2.py:430-440):  used = sel;  out = (S / denom) / n_sel
+ *   rule 1 (homography estimator, homo_model_builder.py:174-199):  used = sel where n_neg > 0, every sample where n_neg == 0;
+ *          out = (S / n_sel) / denom.  The divisor is n_sel in both cases: with no negative in the batch the reference sums every sample and
+ *          still divides by the number of selected ones (its own quirk, kept).
+ *   Empty selection: n_sel == 0 gives out = 0 and, in the backward, zero gradients, and nothing is read.  This differs from the reference on
+ *   purpose: it skips the term under rule 0 and divides by zero under rule 1 (a batch whose unsupervised samples are all negative makes its
+ *   total_loss NaN); a kernel cannot skip, and a caller that gates with torch.where passes a zero upstream gradient, which must not become 0 inf.
+ *   The data of a sample that is not used is not read: a NaN there reaches nothing.  S is summed in an order fixed by (N, R) alone (a row per
+ *   wave into partial, then one workgroup: thread t adds partial[t], partial[t + 1024], ..., a xor tree adds a wave's lanes, the sixteen waves
+ *   are added in ascending order): no float atomics, two calls are bit-equal.  Two launches on `stream`.
+ * hdn_triplet_l1_mean_bwd_f32: grad_out [1] -> grad_a, grad_p, grad_n [N,R,D]; each may be NULL (not all).  The sets are recounted from the flags.
+ *   Every element is written exactly once: rows of unused samples and inactive rows (v < 0 or NaN) are 0; an element of an active row is c k with
+ *   k = s_ap - s_an, -s_ap, s_an {0, +-1, +-2} as in hdn_triplet_l1_bwd_f32 and ONE fp32 factor per call, in the rule's order:
+ *   rule 0: c = (grad_out / denom) / n_sel;  rule 1: c = (grad_out / n_sel) / denom.  First order only; the flags get no gradient.
+ * Checked before the launch, in this order: a required pointer NULL -> HDN_E_NULL; N, R or D <= 0, rule outside {0, 1}, denom not > 0, or no
+ * gradient asked for -> HDN_E_SHAPE; N > 65536, N R > 2^30 or D > 2^20 -> HDN_E_LIMIT; the byte range of an output (partial, out, counts, a
+ * gradient) overlapping an input's, grad_out's or another output's -> HDN_E_ALIAS.  The three inputs may alias each other.
+ */
+int hdn_triplet_l1_mean_f32(const float* anchor, const float* positive, const float* negative, const float* if_pos, const float* if_unsup,
+                            float* partial, float* out, int* counts, int N, int R, int D, int rule, float denom, float margin, float eps,
+                            void* stream);
+int hdn_triplet_l1_mean_bwd_f32(const float* anchor, const float* positive, const float* negative, const float* if_pos, const float* if_unsup,
+                                const float* grad_out, float* grad_a_or_null, float* grad_p_or_null, float* grad_n_or_null, int N, int R, int D,
+                                int rule, float denom, float margin, float eps, void* stream);
+
+/*
  * The similarity model's supervised head losses (csrc/sup_losses.hip): up to five scalar losses of hdn/models/loss.py in one launch, one workgroup
  * per loss, as model_builder_e2e_unconstrained_v2.py:457-478 and :516-523 use them (WEIGHTED_MAP_LP: False).  All selection - the sample mask, the
  * label predicates, the label maximum, the counts, the top-k - happens in the kernel: no nonzero(), no host read, capturable in a graph.
