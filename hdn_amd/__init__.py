@@ -16,6 +16,7 @@ from .losses import (kalyo_l1_loss, select_cross_entropy_loss, select_l1_loss, s
 from .simi_geometry import (combine_affine_c0_v2, combine_affine_lt0, get_polar_from_two_para_loc, lp_pick, polar_pick,  # noqa: F401
                             similarity_warps)
 from .simi_train import SimiTrainConfig, simi_training_forward  # noqa: F401
+from .optim import GatedAMSGrad, grad_norm  # noqa: F401
 from .heads import MultiBAN, MultiCircBAN  # noqa: F401
 from .refine import homo_refine, refine_warp  # noqa: F401
 

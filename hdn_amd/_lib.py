@@ -157,6 +157,15 @@ SIGNATURES = {
     "hdn_simi_warps_bwd_f32": (_i, [_c_float_p] * 12 + [_i] * 2 + [ctypes.c_float] + [ctypes.c_double] * 4 + [ctypes.c_void_p]),
     "hdn_corner_losses_f32": (_i, [_c_float_p] * 9 + [_i, ctypes.c_void_p]),
     "hdn_corner_losses_bwd_f32": (_i, [_c_float_p] * 12 + [_i, ctypes.c_void_p]),
+    "hdn_opt_tensors_per_launch": (_i, []),
+    "hdn_opt_chunk": (_i, []),
+    "hdn_grad_sqnorm_partials": (ctypes.c_longlong, [ctypes.POINTER(ctypes.c_longlong), _i]),
+    "hdn_opt_state_floats": (ctypes.c_longlong, [ctypes.POINTER(ctypes.c_longlong), _i]),
+    "hdn_grad_sqnorm_f32": (_i, [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_longlong), _i, _c_float_p, ctypes.c_longlong, ctypes.c_void_p]),
+    "hdn_opt_gate_f32": (_i, [_c_float_p, ctypes.c_longlong, _c_float_p, ctypes.c_float, _i, ctypes.c_double, _c_float_p, _c_float_p,
+                              ctypes.POINTER(ctypes.c_void_p), _i, ctypes.c_double, ctypes.c_double] + [_c_float_p] * 3 + [ctypes.c_void_p]),
+    "hdn_amsgrad_apply_f32": (_i, [ctypes.POINTER(ctypes.c_void_p)] * 2 + [ctypes.POINTER(ctypes.c_longlong), _i] + [_c_float_p] * 3
+                              + [ctypes.c_longlong] + [_c_float_p] * 2 + [ctypes.c_double] * 4 + [_i, ctypes.c_void_p]),
 }
 
 ERRORS = {

@@ -211,7 +211,11 @@ class PreShareFeature(nn.Module):
 
     def _packed(self, name, tensors):
         """torch.cat of `tensors` (detached), rebuilt when one of them changed: gamma / bias / running statistics as the train kernels take them.
-        Six calls of a training step share one concatenation."""
+        Six calls of a training step share one concatenation.  Inside a graph capture nothing is cached: a replay does not pass through here, so
+        a graph that also holds an optimizer step (hdn_amd.optim) has to gather the live parameters itself, every time it runs."""
+        if tensors[0].is_cuda and torch.cuda.is_current_stream_capturing():
+            with torch.no_grad():
+                return torch.cat([t.detach().reshape(-1) for t in tensors])
         key = tuple((id(t), t.data_ptr(), t._version) for t in tensors)
         cache = self.__dict__.setdefault("_pack_cache", {})
         hit = cache.get(name)

@@ -597,6 +597,46 @@ int hdn_corner_losses_bwd_f32(const float* H_mat, const float* pred_points, cons
                               float* grad_pred_points_or_null, float* grad_aug_sear_points_or_null, float* grad_x_or_null, int B, void* stream);
 
 /*
+ * The optimizer stretch of a training iteration, tools/train.py:271-281 of the reference (is_valid_number(loss), clip_grad_norm_(10),
+ * Adam(amsgrad=True).step()), with nothing read by or uploaded from the host (csrc/opt_step.hip).  The three calls are made in this order on one
+ * stream.  `grads`, `params` and `numel` are HOST arrays of n entries; the device pointers in them travel to the kernels by value, at most
+ * hdn_opt_tensors_per_launch() tensors per launch (every launch's arguments stay within 4 KB), so a gradient allocated inside a graph capture is
+ * served; a NULL gradient is a tensor without a gradient in this step.  A launch's work items are chunks of hdn_opt_chunk() elements.
+ *
+ * hdn_grad_sqnorm_f32: partials[j] (float64) = the sum of squares of chunk j, chunks counted through the tensors in order, ceil(numel / chunk) per
+ *   tensor whether it has a gradient or not (0 then): hdn_grad_sqnorm_partials(numel, n) of them, a layout the sizes alone decide.  One writer per
+ *   partial, float64 accumulation in a fixed order, no atomics.
+ * hdn_opt_gate_f32: one workgroup.  norm = sqrt(the partials added in a fixed order, float64).  ctrl (four 32-bit words):
+ *     ctrl[0] status (int32): 1 when loss is given and isnan(loss) or isinf(loss) or loss > loss_limit (train.py:220-221: -inf is rejected, a loss
+ *             equal to the limit is not); else 2 when norm is not finite; else 0
+ *     ctrl[1] grad_norm = (float)norm, before clipping       ctrl[2] clip_coef = (float)min(1, max_norm / (norm + 1e-6)), 1 when clip == 0
+ *   and, only when status == 0, for every tensor i with a gradient: steps[i] += 1 (fp32), coef[i] = (float)(lr[group[i]] / (1 - beta1^t)),
+ *   coef[n + i] = (float)(1 / sqrt(1 - beta2^t)), t = the new steps[i], in float64.  lr (float64, one per group), group (int32 [n]), steps and coef
+ *   are device arrays; lr is read when the kernel runs.  n may be 0 (the norm alone); n <= 28672.
+ * hdn_amsgrad_apply_f32: returns after reading ctrl[0] when it is not 0 (no byte is written).  Else per element of every tensor with a gradient,
+ *   each operation rounded to fp32 on its own, sqrt and / correctly rounded, c = ctrl[2]:
+ *     g' = c g;  ge = g' + wd p;  m = b1 m + (1 - b1) ge;  v = b2 v + ((1 - b2) ge) ge;  vmax = max(vmax, v);
+ *     p = p - (coef[i] m) / (sqrt(vmax) coef[n + i] + eps);   write_grads != 0: g = g' (what clip_grad_norm_ leaves behind)
+ *   The moments are three flat buffers of state_floats >= hdn_opt_state_floats(numel, n) floats, 16-byte aligned; tensor i's slot starts at the sum
+ *   of the earlier sizes, each rounded up to a multiple of 4.  16-byte loads and stores where p and g are 16-byte aligned, a scalar path for the
+ *   last numel % 4 elements and for a misaligned view.  Bit-reproducible.
+ * Checked before any launch: a required pointer NULL (a parameter included) -> HDN_E_NULL; n < 0, a negative size, clip with max_norm not > 0, a
+ * beta outside [0, 1) -> HDN_E_SHAPE; a size above 2^40, too few partials or state floats, a misaligned pointer, n above the gate's limit ->
+ * HDN_E_LIMIT; a gradient overlapping its parameter -> HDN_E_ALIAS.  The two size queries are host only; negative = HDN_E_*.
+ */
+int hdn_opt_tensors_per_launch(void);
+int hdn_opt_chunk(void);
+long long hdn_grad_sqnorm_partials(const long long* numel, int n);
+long long hdn_opt_state_floats(const long long* numel, int n);
+int hdn_grad_sqnorm_f32(const float* const* grads, const long long* numel, int n, double* partials, long long n_partials, void* stream);
+int hdn_opt_gate_f32(const double* partials, long long n_partials, const float* loss_or_null, float loss_limit, int clip, double max_norm,
+                     const double* lr, const int* group, const float* const* grads, int n, double beta1, double beta2, float* ctrl, float* steps,
+                     float* coef, void* stream);
+int hdn_amsgrad_apply_f32(float* const* params, float* const* grads, const long long* numel, int n, float* exp_avg, float* exp_avg_sq,
+                          float* max_exp_avg_sq, long long state_floats, const float* ctrl, const float* coef, double beta1, double beta2,
+                          double eps, double weight_decay, int write_grads, void* stream);
+
+/*
  * Device-resident frame handling: the uint8 frame [H,W,C] (HWC, BGR as cv2.imread delivers it) is
  * uploaded once; crops and warps are kernels.  `params` / `M` are DEVICE float64 arrays so that positions and homographies
  * produced on the device never visit the host.
