@@ -104,6 +104,14 @@ SIGNATURES = {
     "hdn_conv3x3v_workspace_bytes": (ctypes.c_longlong, [_i] * 5),
     "hdn_conv3x3v_form": (_i, [_i] * 5),
     "hdn_conv3x3v_f32": (_i, [_c_float_p, ctypes.c_void_p, _c_float_p, _c_float_p, ctypes.c_void_p, ctypes.c_longlong] + [_i] * 7 + [ctypes.c_void_p]),
+    "hdn_pack_conv3x3d_dev_f32": (_i, [_c_float_p, _i, _i, _i, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p]),
+    "hdn_grad_scale_f32": (_i, [_c_float_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p]),
+    "hdn_conv3x3v_dgrad_workspace_bytes": (ctypes.c_longlong, [_i] * 4),
+    "hdn_conv3x3v_dgrad_form": (_i, [_i] * 4),
+    "hdn_conv3x3v_dgrad_f32": (_i, [_c_float_p, ctypes.c_void_p, ctypes.c_void_p, _c_float_p, ctypes.c_void_p, ctypes.c_longlong] + [_i] * 4 + [ctypes.c_void_p]),
+    "hdn_conv3x3v_wgrad_workspace_bytes": (ctypes.c_longlong, [_i] * 4),
+    "hdn_conv3x3v_wgrad_form": (_i, [_i] * 4),
+    "hdn_conv3x3v_wgrad_f32": (_i, [_c_float_p, _c_float_p, ctypes.c_void_p, _c_float_p, ctypes.c_void_p, ctypes.c_longlong] + [_i] * 4 + [ctypes.c_void_p]),
     "hdn_pack_simi_stem_bytes": (ctypes.c_longlong, []),
     "hdn_pack_simi_stem_f32": (_i, [_c_float_p, ctypes.c_void_p, ctypes.c_longlong]),
     "hdn_simi_stem_f32": (_i, [_c_float_p, ctypes.c_void_p, _c_float_p, _c_float_p] + [_i] * 3 + [ctypes.c_void_p]),

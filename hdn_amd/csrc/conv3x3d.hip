@@ -51,9 +51,17 @@ struct Cfg {
 
 // FINAL: the whole of K in this workgroup, epilogue here; otherwise slice blockIdx.y of K, raw joined sums to dst = workspace [z][M][CO]
 // VALID: the padding-0 pixel map — M = B So^2 output pixels, `d` is the STRIDE, a tap is never out of bounds; otherwise So == S and `d` is the dilation
-template <class C, bool SD, bool FINAL, bool VALID = false>
-__global__ __launch_bounds__(256) void conv3x3d_kernel(const float* __restrict__ x, const u32x4* __restrict__ wp, const float* __restrict__ bias,
-                                                       float* __restrict__ dst, int M, int S, int So, int d, int CI, int CO, int relu, int tm, int sps) {
+// MAP: the pixel map — SAME (padding = dilation), VALID (above) or FULL (padding 2, stride 1: So = S + 2 outputs per side, the tap (ky, kx) of output
+//   pixel (oy, ox) reads input pixel (oy + ky - 2, ox + kx - 2) under the out-of-image predicate: the input gradient of a valid convolution, see
+//   hdn_conv3x3v_dgrad_f32 further down).
+// GRAD: x is a GRADIENT — split as x 2^ge (ge: the exponent hdn_grad_scale_f32 chose from the data, conv3x3_train.hip) instead of the activations'
+//   fixed 2^-8, the join multiplies by 2^-ge; no bias, no ReLU.
+enum PixelMap { SAME = 0, VALID_MAP = 1, FULL = 2 };
+
+template <class C, bool SD, bool FINAL, int MAP, bool GRAD>
+__device__ __forceinline__ void conv3x3d_body(const float* __restrict__ x, const u32x4* __restrict__ wp, const float* __restrict__ bias,
+                                              float* __restrict__ dst, int M, int S, int So, int d, int CI, int CO, int relu, int tm, int sps, int ge) {
+  constexpr bool VALID = MAP == VALID_MAP;
   constexpr int MT = C::MT, NT = C::NT, WN = C::WN;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wn = wave % WN, wm = wave / WN;
@@ -75,6 +83,7 @@ __global__ __launch_bounds__(256) void conv3x3d_kernel(const float* __restrict__
     oy[i] = rm / So;
     ox[i] = rm - oy[i] * So;
     if constexpr (VALID) xr[i] = x + (((size_t)b * S + d * oy[i]) * S + d * ox[i]) * CI + 16 * g;      // the window's top-left pixel
+    else if constexpr (MAP == FULL) xr[i] = x + (((ptrdiff_t)b * S + oy[i]) * S + ox[i]) * CI + 16 * g;   // input pixel (oy, ox): read only at in-image taps
     else xr[i] = x + (size_t)m * CI + 16 * g;
   }
   const int chunks = CI >> 5, steps = 9 * chunks;
@@ -94,7 +103,8 @@ __global__ __launch_bounds__(256) void conv3x3d_kernel(const float* __restrict__
   u32x4 wa[NT][4];
   int tap = s0 / chunks, c = s0 - tap * chunks;                             // of the next step to load
   auto load = [&](int s) {
-    const int ky = tap / 3, kx = tap - 3 * ky, dy = VALID ? ky : (ky - 1) * d, dx = VALID ? kx : (kx - 1) * d;
+    const int ky = tap / 3, kx = tap - 3 * ky;
+    const int dy = VALID ? ky : MAP == FULL ? ky - 2 : (ky - 1) * d, dx = VALID ? kx : MAP == FULL ? kx - 2 : (kx - 1) * d;
     const ptrdiff_t off = ((ptrdiff_t)dy * S + dx) * CI + c * 32;
 #pragma unroll
     for (int i = 0; i < MT; ++i) {
@@ -116,7 +126,10 @@ __global__ __launch_bounds__(256) void conv3x3d_kernel(const float* __restrict__
 #pragma unroll
     for (int i = 0; i < MT; ++i)
 #pragma unroll
-      for (int qq = 0; qq < 4; ++qq) xv[i][qq] = xa[i][qq];
+      for (int qq = 0; qq < 4; ++qq) {
+        xv[i][qq] = xa[i][qq];
+        if constexpr (GRAD) xv[i][qq] = f4{ldexpf(xv[i][qq].x, ge), ldexpf(xv[i][qq].y, ge), ldexpf(xv[i][qq].z, ge), ldexpf(xv[i][qq].w, ge)};
+      }
 #pragma unroll
     for (int j = 0; j < NT; ++j)
 #pragma unroll
@@ -125,7 +138,7 @@ __global__ __launch_bounds__(256) void conv3x3d_kernel(const float* __restrict__
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
-      for (int i = 0; i < MT; ++i) mma_kstep<SD>(t, xv[i], wv, hi[i], lo[i]);
+      for (int i = 0; i < MT; ++i) mma_kstep<SD || GRAD>(t, xv[i], wv, hi[i], lo[i]);
   }
 
   // epilogue: register r of a lane is pixel m0 + 32 i + d_row(r, g), output channel 32 (nt0 + j) + li
@@ -140,8 +153,9 @@ __global__ __launch_bounds__(256) void conv3x3d_kernel(const float* __restrict__
       for (int rr = 0; rr < 16; ++rr) {
         const int mm = m0 + 32 * i + d_row(rr, g);
         if (mm < M) {
-          float v = join<SD>(hi[i][j][rr], lo[i][j][rr]);
-          if (FINAL) {
+          float v = join<SD || GRAD>(hi[i][j][rr], lo[i][j][rr]);
+          if constexpr (GRAD) v = ldexpf(v, -ge);
+          if (FINAL && !GRAD) {
             v += bv;
             if (relu) v = fmaxf(v, 0.f);
           }
@@ -149,6 +163,19 @@ __global__ __launch_bounds__(256) void conv3x3d_kernel(const float* __restrict__
         }
       }
   }
+}
+
+template <class C, bool SD, bool FINAL, bool VALID = false>
+__global__ __launch_bounds__(256) void conv3x3d_kernel(const float* __restrict__ x, const u32x4* __restrict__ wp, const float* __restrict__ bias,
+                                                       float* __restrict__ dst, int M, int S, int So, int d, int CI, int CO, int relu, int tm, int sps) {
+  conv3x3d_body<C, SD, FINAL, VALID ? VALID_MAP : SAME, false>(x, wp, bias, dst, M, S, So, d, CI, CO, relu, tm, sps, 0);
+}
+
+// the input gradient of the valid stride-1 convolution: x = dy [B, S, S, CI = the convolution's CO], So = S + 2, *expp = the split exponent
+template <class C, bool FINAL>
+__global__ __launch_bounds__(256) void conv3x3_dgrad_kernel(const float* __restrict__ x, const u32x4* __restrict__ wp, const int* __restrict__ expp,
+                                                            float* __restrict__ dst, int M, int S, int So, int CI, int CO, int tm, int sps) {
+  conv3x3d_body<C, false, FINAL, FULL, true>(x, wp, nullptr, dst, M, S, So, 1, CI, CO, 0, tm, sps, *expp);
 }
 
 // K steps per slice for a form that gives `wgs` workgroups over `steps` K steps (steps: one slice, no workspace)
@@ -240,6 +267,58 @@ static int run(const float* x, const void* wpacked, const float* bias, float* ou
   });
 }
 
+// ---- dgrad of the valid stride-1 convolution (hdn_conv3x3v_dgrad_f32): M = B S^2 pixels of gx, K = 9 CO, N = CI
+static int dgrad_shape(int B, int S, int CI, int CO, long long* M, long long* ndy) {
+  if (B <= 0 || S < 3 || CI <= 0 || CO <= 0 || CI % 32 || CO % 32) return HDN_E_SHAPE;
+  *M = (long long)B * S * S;
+  *ndy = (long long)B * (S - 2) * (S - 2) * CO;
+  if (*M * CI > INT_MAX || *ndy > INT_MAX || 9LL * CI * CO > INT_MAX) return HDN_E_LIMIT;
+  return HDN_OK;
+}
+
+static int dgrad_form(int B, int S, int CI, int CO) {
+  long long M, ndy;
+  if (const int rc = dgrad_shape(B, S, CI, CO, &M, &ndy)) return rc;
+  return (int)dispatch(M, CO, CI, [&](auto cfg, int sps) -> long long {
+    using C = decltype(cfg);
+    return C::MT | C::NT << 4 | C::WM << 8 | C::WN << 12 | cdiv(9 * (CO / 32), sps) << 16;
+  });
+}
+
+static long long dgrad_workspace(int B, int S, int CI, int CO) {
+  long long M, ndy;
+  if (const int rc = dgrad_shape(B, S, CI, CO, &M, &ndy)) return rc;
+  return dispatch(M, CO, CI, [&](auto, int sps) -> long long {
+    const int Z = cdiv(9 * (CO / 32), sps);
+    return Z > 1 ? Z * M * CI * 4 : 0;
+  });
+}
+
+static int dgrad_run(const float* dy, const void* wpacked_t, const int* expp, float* gx, void* ws, long long ws_bytes, int B, int S, int CI, int CO,
+                     void* stream) {
+  if (!dy || !wpacked_t || !expp || !gx) return HDN_E_NULL;
+  long long M, ndy;
+  if (const int rc = dgrad_shape(B, S, CI, CO, &M, &ndy)) return rc;
+  const long long ngx = M * CI;
+  if (bytes_overlap(gx, ngx * 4, dy, ndy * 4) || bytes_overlap(gx, ngx * 4, expp, 4)) return HDN_E_ALIAS;
+  if (!aligned16(dy) || !aligned16(wpacked_t) || !aligned16(gx)) return HDN_E_LIMIT;
+  if (const int rc = check_workspace(ws, ws_bytes, dgrad_workspace(B, S, CI, CO), dy, ndy * 4, gx, ngx * 4)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return (int)dispatch(M, CO, CI, [&](auto cfg, int sps) -> long long {
+    using C = decltype(cfg);
+    const int steps = 9 * (CO / 32), Z = cdiv(steps, sps), tm = cdiv((int)M, C::BM);
+    const dim3 grid((unsigned)((long long)tm * (CI / C::BN)), (unsigned)Z);
+    const u32x4* w = static_cast<const u32x4*>(wpacked_t);
+    if (Z == 1) {
+      hipLaunchKernelGGL((conv3x3_dgrad_kernel<C, true>), grid, dim3(256), 0, s, dy, w, expp, gx, (int)M, S - 2, S, CO, CI, tm, sps);
+      return launch_status();
+    }
+    hipLaunchKernelGGL((conv3x3_dgrad_kernel<C, false>), grid, dim3(256), 0, s, dy, w, expp, static_cast<float*>(ws), (int)M, S - 2, S, CO, CI, tm, sps);
+    if (const int rc = launch_status()) return rc;
+    return finish_slices(static_cast<float*>(ws), Z, nullptr, 0, gx, ngx, CI, s);
+  });
+}
+
 }  // namespace c3d
 }  // namespace hdn
 
@@ -263,4 +342,14 @@ extern "C" long long hdn_conv3x3v_workspace_bytes(int B, int S, int CI, int CO, 
 extern "C" int hdn_conv3x3v_f32(const float* x, const void* wpacked, const float* bias, float* out, void* ws, long long ws_bytes, int B, int S, int CI,
                                 int CO, int stride, int relu, int act_domain, void* stream) {
   return hdn::c3d::run<true>(x, wpacked, bias, out, ws, ws_bytes, B, S, CI, CO, stride, relu, act_domain, stream);
+}
+
+// ------------------------------------------------------------------------------- the input gradient of hdn_conv3x3v_f32 at stride 1: the FULL pixel map
+extern "C" int hdn_conv3x3v_dgrad_form(int B, int S, int CI, int CO) { return hdn::c3d::dgrad_form(B, S, CI, CO); }
+
+extern "C" long long hdn_conv3x3v_dgrad_workspace_bytes(int B, int S, int CI, int CO) { return hdn::c3d::dgrad_workspace(B, S, CI, CO); }
+
+extern "C" int hdn_conv3x3v_dgrad_f32(const float* dy, const void* wpacked_t, const int* exp, float* gx, void* ws, long long ws_bytes, int B, int S, int CI,
+                                      int CO, void* stream) {
+  return hdn::c3d::dgrad_run(dy, wpacked_t, exp, gx, ws, ws_bytes, B, S, CI, CO, stream);
 }

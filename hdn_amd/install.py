@@ -25,6 +25,8 @@ attribute the reference resolves at call time:
         kalyo_l1_loss}                                   (install(train=True), while SUP_LOSS_TRAIN_BOUND) the drop-ins of hdn_amd/losses.py
     model_builder_e2e_unconstrained_v2.{lp_pick, combine_affine_c0_v2, combine_affine_lt0}   :27-28 (install(train=True), while
         hdn.models.logpolar.Polar_Pick.get_polar_from_two_para_loc       SIMI_GEOMETRY_TRAIN_BOUND) the drop-ins of hdn_amd/simi_geometry.py
+    DepthwiseXCorr.forward / DepthwiseXCorrCirc.forward  (install(train=True), while HEAD_CONV_TRAIN_BOUND) in .train() mode the two 3x3 convolutions
+                                                         on hdn_amd.conv3x3_valid (hdn_amd/conv_train.py); the class's own forward otherwise
     hdn.tracker.tracker_builder.TRACKS['hdnTrackerHomoProje2e']   (install(tracker=True)) the device-resident tracker loop
 
 Training under install(train=True): every statement of the reference's training forwards that resolves to a drop-in is differentiable on the device -
@@ -44,7 +46,7 @@ import weakref
 
 import torch
 
-from . import affine, heads, homo_model, homography, logpolar, losses, share_feature, simi_geometry, triplet, xcorr
+from . import affine, conv_train, heads, homo_model, homography, logpolar, losses, share_feature, simi_geometry, triplet, xcorr
 
 _DLT = "homo_estimator.Deep_homography.Oneline_DLTv1"
 
@@ -162,6 +164,27 @@ SIMI_GEOMETRY_SITE = "hdn.models.model_builder_e2e_unconstrained_v2"
 SIMI_GEOMETRY_NAMES = ("lp_pick", "combine_affine_c0_v2", "combine_affine_lt0")
 POLAR_PICK_SITE = ("hdn.models.logpolar", "Polar_Pick", "get_polar_from_two_para_loc")
 
+# Does install(train=True) rebind DepthwiseXCorr.forward / DepthwiseXCorrCirc.forward to the dispatcher that, in .train() mode, runs
+# hdn_amd.conv_train.depthwise_xcorr_train_forward (the two 3x3 convolutions of a head branch, forward, dgrad and wgrad on HIP)?  Set by the outcome of
+# tools/head_conv_train_bench.py (profiles/head_conv_train.json): True only while the HIP path is faster than PyTorch-ROCm autograd through nn.Conv2d
+# on the step's 24 convolutions at B = 32, beyond both sides' spread.
+HEAD_CONV_TRAIN_BOUND = True
+
+# (module, class, the module attribute its forward resolves the correlation by)
+HEAD_CONV_SITES = (("hdn.models.head.ban", "DepthwiseXCorr", "xcorr_depthwise"), ("hdn.models.head.ban_lp", "DepthwiseXCorrCirc", "xcorr_depthwise_circular"))
+
+
+def _make_head_branch_forward(orig, module, xcorr_name):
+    """The dispatcher bound at a head branch's forward: .train() mode runs the HIP training forward with the correlation `module` resolves NOW (the
+    rebindings above included), any other mode the class's saved forward."""
+    def forward(self, kernel, search):
+        if self.training:
+            return conv_train.depthwise_xcorr_train_forward(self, kernel, search, getattr(module, xcorr_name))
+        return orig(self, kernel, search)
+    forward._hdn_wraps = orig
+    return forward
+
+
 _MISSING = object()
 _saved = []  # (owner, attribute or dict key, original value, is_dict_item) in application order; undone by uninstall()
 
@@ -218,7 +241,9 @@ def install(strict: bool = False, modules: dict = None, tracker: bool = False, t
     select_xr_focal_fuse_smooth_l1_loss and select_l1_loss_lp, the WEIGHTED_MAP_LP: True branch, stay the reference's), so that the reference's
     training forward runs on the drop-ins and, while SIMI_GEOMETRY_TRAIN_BOUND, the three SIMI_GEOMETRY_NAMES that the same module imports and
     Polar_Pick.get_polar_from_two_para_loc to the drop-ins of hdn_amd.simi_geometry (only where the attribute exists; the method keeps the one it
-    replaces for a points table that is not the analytic one); everything else is unchanged.  Returns the list of (module, attribute) pairs that were rebound;
+    replaces for a points table that is not the analytic one) and, while HEAD_CONV_TRAIN_BOUND, DepthwiseXCorr.forward and DepthwiseXCorrCirc.forward
+    (HEAD_CONV_SITES) to a dispatcher that runs hdn_amd.conv_train.depthwise_xcorr_train_forward in .train() mode and the class's own forward
+    otherwise; everything else is unchanged.  Returns the list of (module, attribute) pairs that were rebound;
     with strict=True a site that cannot be imported raises instead of being skipped.  uninstall() reverses it."""
     done = []
 
@@ -256,6 +281,14 @@ def install(strict: bool = False, modules: dict = None, tracker: bool = False, t
                 _rebind(klass, "_hdn_orig_forward", klass.__dict__["forward"])  # training-mode calls are deferred to it
             _rebind(klass, "forward", (lambda c: lambda self, z_fs, x_fs: heads.fused_forward(self, z_fs, x_fs, c))(circ))
             done.append((mod_name, cls_name + ".forward"))
+
+    if train and HEAD_CONV_TRAIN_BOUND:
+        for mod_name, cls_name, xcorr_name in HEAD_CONV_SITES:
+            m = get(mod_name)
+            klass = getattr(m, cls_name, None) if m is not None else None
+            if isinstance(klass, type) and "forward" in klass.__dict__ and not hasattr(klass.__dict__["forward"], "_hdn_wraps"):
+                _rebind(klass, "forward", _make_head_branch_forward(klass.__dict__["forward"], m, xcorr_name))
+                done.append((mod_name, cls_name + ".forward"))
 
     mb = get("hdn.models.model_builder_e2e_unconstrained_v2")
     if mb is not None and hasattr(mb, "ModelBuilder"):

@@ -967,6 +967,7 @@ int hdn_xcorr_north_launch_events(void* start_event, void* stop_event);
  * `w_packed` / `w1_packed`.  The ORDER inside a stream is the kernel's business and may change between library builds (the layout notes further
  * down describe the current one for readers of the kernels, they are not part of the contract); pack and run with the same library.
  * Every stream holds two fp16 pieces per (padded) weight, v = p0 + 2^-11 p1; a weight with |w| >= 65,504 or NaN -> HDN_E_LIMIT.
+ * (The one packer that runs on the device, hdn_pack_conv3x3d_dev_f32 further down, cannot raise inside a capture: it COUNTS such weights instead.)
  * hdn_pack_*_bytes: size of the stream (negative = HDN_E_SHAPE for a shape no kernel serves); the packers check `out_bytes` against it.
  *   hdn_pack_conv3x3_f32       w [C][C][3][3]                          -> hdn_conv3x3_bias_relu_f32 / hdn_conv3x3_chain_f32, C = 64 / 128 / 256 / 512
  *   hdn_pack_conv3x3s2_ds_f32  w [2CI][CI][3][3], w_ds [2CI][CI]       -> hdn_conv3x3s2_ds_f32 (backbone/resnet.py:78-94 conv1 and :162-169 downsample)
@@ -1120,6 +1121,55 @@ long long hdn_conv3x3v_workspace_bytes(int B, int S, int CI, int CO, int stride)
 int hdn_conv3x3v_form(int B, int S, int CI, int CO, int stride);                                /* resnet_atrous.py:70-81, 162-174 */
 int hdn_conv3x3v_f32(const float* x, const void* wpacked, const float* bias, float* out, void* ws, long long ws_bytes, int B, int S, int CI, int CO,
                      int stride, int relu, int act_domain, void* stream);                       /* resnet_atrous.py:70-81, 162-174 */
+
+/*
+ * Training the valid stride-1 convolution above — the heads' Conv2d(CI, CO, 3, bias=False) in front of the correlations, hdn/models/head/ban.py:55-64,
+ * ban_lp.py:17-26 (conv3x3_train.hip, conv3x3d.hip; additions to ABI 10).  Everything below is asynchronous on `stream`, allocates nothing, reads
+ * nothing back and can be captured into a graph.  The forward is hdn_conv3x3v_f32(stride 1, relu 0, bias NULL) on the mode-0 stream.
+ *
+ * hdn_pack_conv3x3d_dev_f32: hdn_pack_conv3x3d_f32 on the DEVICE.  w: device pointer to plain [CO][CI][3][3] fp32; out: device buffer of
+ *   hdn_pack_conv3x3d_bytes(CO, CI) bytes, 16-byte aligned (else HDN_E_LIMIT), not overlapping w (HDN_E_ALIAS).  mode 0: byte for byte the stream the host
+ *   packer writes from w; mode 1: the stream the host packer would write for w'[ci][co][ky][kx] = w[co][ci][2 - ky][2 - kx] (CO and CI swap roles:
+ *   the operand of hdn_conv3x3v_dgrad_f32); another mode, CO or CI no positive multiple of 32, a wrong out_bytes: HDN_E_SHAPE; NULL w or out: HDN_E_NULL.
+ *   RANGE.  The host packers return HDN_E_LIMIT for a weight with |w| >= 65,504 or NaN.  A device packer cannot raise inside a capture: it converts as
+ *   v_cvt_f16_f32 converts (inf / NaN pieces, which propagate into every output they enter) and ADDS the number of such weights to *bad_count, an int
+ *   on the device that the caller zeroes and reads outside a capture (integer atomic adds: the count does not depend on their order); may be NULL.
+ *
+ * hdn_grad_scale_f32: one pass over g[n] that writes ONE int to the device, the exponent e with amax 2^e in [2^14, 2^15), amax = max |g|:
+ *   e = 141 - (the 8-bit exponent field of amax), so scaling g by a power of two shifts e and changes nothing else; e = 0 when amax is 0, inf or NaN (a
+ *   NaN anywhere in g counts as amax); a subnormal amax counts as the smallest normal number (e = 140).  The maximum is taken over bit patterns with
+ *   integer operations — the same in any order, no float atomics.  g 16-byte aligned (HDN_E_LIMIT), n >= 1 (HDN_E_SHAPE), exp_out not inside g (HDN_E_ALIAS).
+ *   With this e every element v of g is carried by its two fp16 pieces within max(2^-22 |v|, 2^-50 amax).
+ *
+ * hdn_conv3x3v_dgrad_f32: gx[B,S,S,CI] = the FULL correlation (padding 2) of dy[B,So,So,CO], So = S - 2, with the mode-1 stream `wpacked_t` — the third
+ *   pixel map of conv3x3d.hip's kernel: output side So + 2, tap (ky, kx) of output pixel (y, x) reads dy at (y + ky - 2, x + kx - 2) when that is inside
+ *   the image.  dy is split as dy 2^e with e = *exp (device pointer, what hdn_grad_scale_f32 wrote for dy), the join multiplies by 2^-e: both exact.
+ *   Forms A / B / C over M = B S^2 pixels, N = CI, K = 9 CO in tap-major steps, K split and finish pass exactly as hdn_conv3x3v_f32; the summation order
+ *   depends on (B, S, CI, CO) only.  S >= 3, B >= 1, CI and CO positive multiples of 32 (HDN_E_SHAPE); more than 2^31 - 1 elements in dy or gx, a
+ *   pointer that is not 16-byte aligned, a workspace too small: HDN_E_LIMIT; gx overlapping dy, exp or ws, ws overlapping dy: HDN_E_ALIAS; NULL dy,
+ *   wpacked_t, exp, gx, or ws where one is needed: HDN_E_NULL.  No range guard: a gradient is scaled by its own amax.
+ *
+ * hdn_conv3x3v_wgrad_f32: gw[co][ci][ky][kx] = sum over (b, oy, ox) of dy[b,oy,ox,co] x[b,oy+ky,ox+kx,ci], plain [CO][CI][3][3] fp32 (what weight.grad
+ *   is), x[B,S,S,CI] and dy[B,So,So,CO] channels-last.  Both operands are split in the kernel (x as activations, 2^-8, inside the range guard on x; dy by
+ *   *exp), three piece products into hi / lo accumulators.  K is the pixel axis: it walks in units of (8 consecutive images, one output row), a unit in
+ *   segments of 8 output pixels whose dy tile and 3 x 10 x halo are staged once for all nine taps; workgroups of W = 4 / 2 / 1 waves (the largest W with
+ *   32 W dividing CO) own 32 W x 32 (co, ci) x 9 taps; K is split into at most 16 slices of whole units that write partial sums to `ws` [z][CO][CI][3][3]
+ *   and a finish pass adds them in slice order.  Deterministic, no atomics; the summation order depends on (B, S, CI, CO) only.  Checks as dgrad's, with
+ *   x in place of wpacked_t and gw in place of gx.
+ *
+ * *_workspace_bytes: bytes needed, 0 = none (ws may be NULL then), negative = HDN_E_*.  *_form: the launch form, for tests and profiles (no part of the
+ *   ABI): dgrad as hdn_conv3x3v_form; wgrad W | (K slices) << 16.  Host only.
+ */
+int hdn_pack_conv3x3d_dev_f32(const float* w, int CO, int CI, int mode, void* out, long long out_bytes, int* bad_count, void* stream);  /* ban.py:55-64 */
+int hdn_grad_scale_f32(const float* g, long long n, int* exp_out, void* stream);                                                        /* ban.py:55-64 */
+long long hdn_conv3x3v_dgrad_workspace_bytes(int B, int S, int CI, int CO);                                                             /* ban.py:55-64 */
+int hdn_conv3x3v_dgrad_form(int B, int S, int CI, int CO);                                                                              /* ban.py:55-64 */
+int hdn_conv3x3v_dgrad_f32(const float* dy, const void* wpacked_t, const int* exp, float* gx, void* ws, long long ws_bytes, int B, int S, int CI, int CO,
+                           void* stream);                                                                                               /* ban.py:55-64 */
+long long hdn_conv3x3v_wgrad_workspace_bytes(int B, int S, int CI, int CO);                                                             /* ban.py:55-64 */
+int hdn_conv3x3v_wgrad_form(int B, int S, int CI, int CO);                                                                              /* ban.py:55-64 */
+int hdn_conv3x3v_wgrad_f32(const float* x, const float* dy, const int* exp, float* gw, void* ws, long long ws_bytes, int B, int S, int CI, int CO,
+                           void* stream);                                                                                               /* ban.py:55-64 */
 
 /*
  * First stage of the similarity branch's ResNet-50 in one launch (simi_stem.hip; an addition to ABI 10):
