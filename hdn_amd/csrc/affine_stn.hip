@@ -14,9 +14,8 @@
 // gradient (PyTorch's zeros padding gives 0 there too).
 //
 // grad_theta is deterministic: a lane adds its channels in ascending order (channels_bwd of geometry.h, the channel walk of every sampler backward),
-// then block_sum_store / reduce_partials_kernel of geometry.h (wave xor
-// tree, waves in ascending order through LDS, one partial of six floats per (sample, block) in the workspace, a second launch of the same call adds
-// them in a fixed order).  64 partials per sample at 127 x 127: the second launch's one wave per sample reads each partial once.  grad_img is an fp32
+// then block_sum_store of reduce.h (its fixed order; one partial of six floats per (sample, block) in the workspace) and reduce_partials_kernel of
+// geometry.h (a second launch of the same call adds them in a fixed order).  64 partials per sample at 127 x 127: the second launch's one wave per sample reads each partial once.  grad_img is an fp32
 // atomicAdd scatter into the buffer the call zero-fills on the stream, NOT bit-reproducible between calls.
 #include "geometry.h"
 
@@ -89,7 +88,7 @@ __global__ __launch_bounds__(HDN_BLOCK) void sample_kernel(const float* __restri
 __global__ __launch_bounds__(HDN_BLOCK) void sample_bwd_kernel(const float* __restrict__ img, const float* __restrict__ theta,
                                                                const float* __restrict__ gout, float* __restrict__ part, float* __restrict__ gimg,
                                                                int C, int H, int W, int Ho, int Wo) {
-  __shared__ float red[gbwd::WAVES * 6];
+  __shared__ float red[BLOCK_WAVES * 6];
   const int b = blockIdx.y;
   const int pix = blockIdx.x * HDN_BLOCK + threadIdx.x;
   float acc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -108,7 +107,7 @@ __global__ __launch_bounds__(HDN_BLOCK) void sample_bwd_kernel(const float* __re
     acc[0] = rn_mul(ax, p.X); acc[1] = rn_mul(ax, p.Y); acc[2] = ax;
     acc[3] = rn_mul(ay, p.X); acc[4] = rn_mul(ay, p.Y); acc[5] = ay;
   }
-  if (part) gbwd::block_sum_store<6>(acc, red, part + (size_t(b) * gridDim.x + blockIdx.x) * 6);  // kernel-uniform branch
+  if (part) block_sum_store<6, BLOCK_WAVES>(acc, red, part + (size_t(b) * gridDim.x + blockIdx.x) * 6);  // kernel-uniform branch
 }
 
 static int check_dims(int B, int C, int H, int W, int Ho, int Wo) {

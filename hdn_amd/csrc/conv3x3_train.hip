@@ -25,6 +25,7 @@
 
 #include "hdn_common.h"
 #include "mfma_split.h"
+#include "reduce.h"
 
 namespace hdn {
 namespace c3t {
@@ -64,10 +65,9 @@ __global__ __launch_bounds__(HDN_BLOCK) void amax_bits_kernel(const float* __res
     m = max(max(m, v.x & 0x7fffffffu), max(v.y & 0x7fffffffu, max(v.z & 0x7fffffffu, v.w & 0x7fffffffu)));
   }
   if (blockIdx.x == 0 && threadIdx.x < (n & 3)) m = max(m, __float_as_uint(gp[(n4 << 2) + threadIdx.x]) & 0x7fffffffu);
-#pragma unroll
-  for (int d = HDN_WAVE / 2; d > 0; d >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, d));
-  __shared__ unsigned part[HDN_BLOCK / HDN_WAVE];
-  if ((threadIdx.x & (HDN_WAVE - 1)) == 0) part[threadIdx.x / HDN_WAVE] = m;
+  m = wave_max(m);
+  __shared__ unsigned part[BLOCK_WAVES];
+  if (lane_id() == 0) part[wave_id()] = m;
   __syncthreads();
   if (threadIdx.x == 0) {                                  // one atomic per workgroup: thousands on one address cost more than the pass itself
     m = max(max(part[0], part[1]), max(part[2], part[3]));

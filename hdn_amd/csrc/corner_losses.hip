@@ -9,9 +9,8 @@
 // registers, in float64, as hdn_dlt_solve_f32 solves it.  The six sample sets are decided from the flags in the kernel (set_flags): nothing is
 // read by the host, nothing is uploaded.
 //
-// Forward: ONE workgroup of 1024 threads walks the batch 128 samples at a time.  A lane adds its terms in ascending sample order, a wave adds its
-// lanes in a fixed xor tree, the sixteen waves are added in ascending order through LDS: no float atomics, every output has the same bits on
-// every call.  Backward: 32 samples per workgroup; each workgroup recounts the sets (integers: no order), then a row depends on its own sample
+// Forward: ONE workgroup of 1024 threads walks the batch 128 samples at a time.  A lane adds its terms in ascending sample order, the workgroup adds its
+// lanes in the fixed order of reduce.h (block_sum_store): no float atomics, every output has the same bits on every call.  Backward: 32 samples per workgroup; each workgroup recounts the sets (integers: no order), then a row depends on its own sample
 // and on the counts alone.
 //
 // A sample outside a set is never loaded for that set's terms: its lanes compute on a stand-in (H = I, the corners of the 127-square,
@@ -149,31 +148,10 @@ __global__ __launch_bounds__(FWD_BLOCK) void fwd_kernel(const float* __restrict_
       for (int q = 0; q < N_SETS; ++q) cnt[q] += s.in[q] ? 1 : 0;
     }
   }
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-#pragma unroll
-    for (int q = 0; q < 5; ++q) acc[q] = rn_add(acc[q], __shfl_xor(acc[q], m, HDN_WAVE));
-#pragma unroll
-    for (int q = 0; q < N_SETS; ++q) cnt[q] += __shfl_xor(cnt[q], m, HDN_WAVE);
-  }
-  if ((tid & (HDN_WAVE - 1)) == 0) {
-    for (int q = 0; q < 5; ++q) red_f[(tid >> 6) * 5 + q] = acc[q];
-    for (int q = 0; q < N_SETS; ++q) red_i[(tid >> 6) * N_SETS + q] = cnt[q];
-  }
+  block_sum_store<5, FWD_WAVES>(acc, red_f, tot_f);
+  block_sum_store<N_SETS, FWD_WAVES>(cnt, red_i, tot_i);
   __syncthreads();
-  if (tid < 5) {
-    float v = red_f[tid];
-    for (int w = 1; w < FWD_WAVES; ++w) v = rn_add(v, red_f[w * 5 + tid]);
-    tot_f[tid] = v;
-  }
-  if (tid >= HDN_WAVE && tid < HDN_WAVE + N_SETS) {
-    const int q = tid - HDN_WAVE;
-    int v = 0;
-    for (int w = 0; w < FWD_WAVES; ++w) v += red_i[w * N_SETS + q];
-    tot_i[q] = v;
-    counts[q] = v;
-  }
-  __syncthreads();
+  if (tid < N_SETS) counts[tid] = tot_i[tid];
   if (tid != 0) return;
   const int n_sp = tot_i[N_SUP_POS], n_sn = tot_i[N_SUP_NEG], n_up = tot_i[N_UNSUP_POS], n_ng = tot_i[N_NEG];
   out[0] = n_sp > 0 ? rn_div(rn_div(tot_f[0], (float)n_sp), 4.f) : 0.f;
@@ -192,23 +170,15 @@ __global__ __launch_bounds__(HDN_BLOCK) void bwd_kernel(const float* __restrict_
                                                         const float* __restrict__ gout, float* __restrict__ gH, float* __restrict__ gpp,
                                                         float* __restrict__ gaug, float* __restrict__ gx, int B) {
   __shared__ float src_s[HDN_BLOCK], off_s[HDN_BLOCK];
-  __shared__ int red_i[(HDN_BLOCK / HDN_WAVE) * 4];
+  __shared__ int red_i[BLOCK_WAVES * 4];
   const int tid = threadIdx.x, r = tid & 7, j = r >> 1, c = r & 1;
   // the counts, as the forward found them
-  int cnt[4] = {0, 0, 0, 0};  // sup_pos, sup_neg, unsup_pos, neg
+  int n[4] = {0, 0, 0, 0};  // sup_pos, sup_neg, unsup_pos, neg
   for (int i = tid; i < B; i += HDN_BLOCK) {
     const Sets s = set_flags(if_pos[i], if_unsup[i], true);
-    cnt[0] += s.in[N_SUP_POS], cnt[1] += s.in[N_SUP_NEG], cnt[2] += s.in[N_UNSUP_POS], cnt[3] += s.in[N_NEG];
+    n[0] += s.in[N_SUP_POS], n[1] += s.in[N_SUP_NEG], n[2] += s.in[N_UNSUP_POS], n[3] += s.in[N_NEG];
   }
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) cnt[q] += __shfl_xor(cnt[q], m, HDN_WAVE);
-  if ((tid & (HDN_WAVE - 1)) == 0)
-    for (int q = 0; q < 4; ++q) red_i[(tid >> 6) * 4 + q] = cnt[q];
-  __syncthreads();
-  int n[4];
-  for (int q = 0; q < 4; ++q) n[q] = red_i[q] + red_i[4 + q] + red_i[8 + q] + red_i[12 + q];
+  block_sum<BLOCK_WAVES>(n, red_i);
   // d L / d (the five sums): out = (S / n) / 4 and S / tsz; cor_loss adds slot 3, and slot 4 where it is reported
   const float k0 = n[0] > 0 ? rn_div(rn_div(gout[0], 4.f), (float)n[0]) : 0.f;
   const float k1 = n[0] > 0 ? rn_div(rn_div(gout[1], 4.f), (float)n[0]) : 0.f;

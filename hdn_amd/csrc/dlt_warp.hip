@@ -144,9 +144,8 @@ __global__ __launch_bounds__(HDN_BLOCK) void warp_kernel(const float* __restrict
     if (pix < H * W) ok += warp_pixel(im, th, ob, pix / W, pix - (pix / W) * W, C, H, W) ? 1u : 0u;
   }
   if (count) {  // kernel-uniform branch: one atomic per wave
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) ok += __shfl_xor(ok, m, HDN_WAVE);
-    if ((threadIdx.x & (HDN_WAVE - 1)) == 0 && ok) atomicAdd(count, ok);
+    ok = wave_sum(ok);
+    if (lane_id() == 0 && ok) atomicAdd(count, ok);
   }
 }
 
@@ -207,12 +206,12 @@ __global__ __launch_bounds__(L1_THREADS) void l1_score_kernel(const float* __res
       p[q & 3] += (base + q * L1_THREADS + (int)threadIdx.x < n) ? fabsf(av[q] - bv[q]) : 0.f;
     s += (p[0] + p[1]) + (p[2] + p[3]);
   }
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, HDN_WAVE);
-  if ((threadIdx.x & (HDN_WAVE - 1)) == 0) part[threadIdx.x >> 6] = s;
+  s = wave_sum(s);
+  if (lane_id() == 0) part[wave_id()] = s;
   __syncthreads();
   if (threadIdx.x < HDN_WAVE) {
     float t = threadIdx.x < L1_THREADS / HDN_WAVE ? part[threadIdx.x] : 0.f;
+    // not block_sum (reduce.h): the 16 wave partials are added by a second butterfly (8 .. 1), not in ascending order; the tracker's scores are pinned to it
 #pragma unroll
     for (int m = 8; m >= 1; m >>= 1) t += __shfl_xor(t, m, HDN_WAVE);
     if (threadIdx.x == 0) out[blockIdx.x] = t * scale;

@@ -84,7 +84,7 @@ int finish_slices(const float* ws, int Z, const float* bias, int relu, float* ou
 
 // AdaptiveAvgPool2d(1) + flatten + Linear(C, O) of the regressor's tail (homo_model_builder.py:161-165) as one launch: one
 // workgroup per sample; a thread owns channels tid, tid + 256, ...: the mean over the HW positions (summed in position order, then
-// times 1 / HW), its O partial products, then a workgroup reduction per output (wave shuffles, one LDS word per wave and output).
+// times 1 / HW), its O partial products, then a workgroup reduction per output (the wave butterfly of reduce.h, one LDS word per wave and output).
 // Replaces at::mean + a hipBLASLt GEMM (5 + 7 us at B = 64, two latency-bound launches at the tracker's B = 1).
 constexpr int AF_MAX_OUT = 16, AF_THREADS = 512;
 template <bool NHWC>
@@ -123,13 +123,14 @@ __global__ __launch_bounds__(AF_THREADS) void avgpool_fc_kernel(const float* __r
 #pragma unroll
   for (int o = 0; o < AF_MAX_OUT; ++o) {
     float v = acc[o];
+    // wave_sum's order (reduce.h), by hand: through the inlined helper this kernel, which is on the tracker's frame path, is allocated 73 VGPRs, not 57
 #pragma unroll
     for (int d = HDN_WAVE / 2; d > 0; d >>= 1) v += __shfl_xor(v, d);
     if (lane == 0) part[wave][o] = v;
   }
   __syncthreads();
   if (tid < O) {
-    float v = bias ? bias[tid] : 0.f;
+    float v = bias ? bias[tid] : 0.f;  // not block_sum (reduce.h): the sum starts from the bias, bias + p0 + p1 + ..., as the regressor's outputs are pinned
 #pragma unroll
     for (int k = 0; k < AF_THREADS / HDN_WAVE; ++k) v += part[k][tid];
     out[(size_t)b * O + tid] = v;

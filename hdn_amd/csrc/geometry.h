@@ -7,6 +7,7 @@
 #include <initializer_list>
 
 #include "hdn_common.h"
+#include "reduce.h"
 
 #pragma clang fp contract(off)
 
@@ -171,11 +172,9 @@ __device__ __forceinline__ double solve8(Row9 row, int r) {
 }
 
 // ------------------------------------------------------------------------------------------------ shared by the backward kernels
-// (geometry_bwd.hip, affine_stn.hip): the per-channel loop of a bilinear sampler's backward, the fixed-order reductions behind the deterministic
-// parameter gradients and the entry points' host sequence.
+// (geometry_bwd.hip, affine_stn.hip): the per-channel loop of a bilinear sampler's backward, the second launch behind the deterministic parameter
+// gradients (the first is block_sum_store of reduce.h) and the entry points' host sequence.
 namespace gbwd {
-
-constexpr int WAVES = HDN_BLOCK / HDN_WAVE;
 
 // The four taps of one bilinear sample as its backward needs them.
 struct Taps {
@@ -211,28 +210,6 @@ __device__ __forceinline__ void channels_bwd(const Taps& t, const float* __restr
   }
 }
 
-// v[q] summed over the block in a fixed order; thread q < N then writes the sum to dst[q].  lds: WAVES * N floats.  Every thread of the block calls it.
-template <int N>
-__device__ __forceinline__ void block_sum_store(float (&v)[N], float* lds, float* __restrict__ dst) {
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int q = 0; q < N; ++q) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v[q] = rn_add(v[q], __shfl_xor(v[q], m, HDN_WAVE));
-  }
-  if ((tid & (HDN_WAVE - 1)) == 0) {
-#pragma unroll
-    for (int q = 0; q < N; ++q) lds[(tid >> 6) * N + q] = v[q];
-  }
-  __syncthreads();
-  if (tid < N) {
-    float s = lds[tid];
-#pragma unroll
-    for (int w = 1; w < WAVES; ++w) s = rn_add(s, lds[w * N + tid]);
-    dst[tid] = s;
-  }
-}
-
 // out[b][q] = scale[q] * (partials part[b][0 .. nblk)[q] added in a fixed order); one wave per sample.
 template <int N>
 __global__ __launch_bounds__(HDN_WAVE) void reduce_partials_kernel(const float* __restrict__ part, float* __restrict__ out, int nblk, const float s0,
@@ -244,15 +221,13 @@ __global__ __launch_bounds__(HDN_WAVE) void reduce_partials_kernel(const float* 
   for (int q = 0; q < N; ++q) {
     float s = 0.f;
     for (int k = lane; k < nblk; k += HDN_WAVE) s = rn_add(s, p[size_t(k) * N + q]);
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) s = rn_add(s, __shfl_xor(s, m, HDN_WAVE));
+    s = wave_sum(s);
     if (lane == 0) out[b * N + q] = rn_mul(q == 0 ? s0 : s1, s);
   }
 }
 
 inline int zero_fill(float* p, long long floats, hipStream_t st) {
-  const hipError_t e = hipMemsetAsync(p, 0, size_t(floats) * sizeof(float), st);
-  return e == hipSuccess ? HDN_OK : -(1000 + (int)e);
+  return hip_status(hipMemsetAsync(p, 0, size_t(floats) * sizeof(float), st));
 }
 
 // an output may not be an input or the other output

@@ -7,9 +7,9 @@
 // threads, one pixel per lane in the sampler, WARP_PX_PER_THREAD per thread in the warp, one 8-lane group per sample in the solve.
 //
 // grad_polar / grad_theta (a sum over every pixel and channel of a sample) are deterministic and use no atomics: a lane adds its channels (and, in
-// the warp, its pixels) in ascending order, a wave adds its lanes in a fixed xor tree (32 .. 1), the block's waves are added in ascending order through
-// LDS (block_sum_store, geometry.h) and written as one partial per (sample, block) into the caller's workspace; reduce_partials_kernel (geometry.h), a second launch of the same call, has one
-// wave per sample add the partials (lane l takes blocks l, l + 64, ... in ascending order, then the same tree).  Nothing depends on the batch size:
+// the warp, its pixels) in ascending order, the block adds them in the fixed order of reduce.h (block_sum_store) and writes one partial per
+// (sample, block) into the caller's workspace; reduce_partials_kernel (geometry.h), a second launch of the same call, has one wave per sample
+// add the partials (lane l takes blocks l, l + 64, ... in ascending order, then wave_sum).  Nothing depends on the batch size:
 // sample b of a batch has the bits of that sample run alone.
 // grad_img is a scatter: plain fp32 atomicAdd (one global_atomic_add_f32) into the buffer that the call zero-fills on the stream first.  The order in
 // which colliding taps arrive is not fixed, so grad_img is NOT bit-reproducible between calls on arbitrary data.
@@ -25,7 +25,7 @@ __global__ __launch_bounds__(HDN_BLOCK) void logpolar_bwd_kernel(const float* __
                                                                  const float* __restrict__ rho, const float* __restrict__ cosT,
                                                                  const float* __restrict__ sinT, const float* __restrict__ gout,
                                                                  float* __restrict__ part, float* __restrict__ gimg, int C, int H, int W, int S) {
-  __shared__ float red[WAVES * 2];
+  __shared__ float red[BLOCK_WAVES * 2];
   const int n = blockIdx.y;
   const int pix = blockIdx.x * HDN_BLOCK + threadIdx.x;
   float acc[2] = {0.f, 0.f};  // sum over channels of gout * d out / d px, d out / d py, times the border rule
@@ -41,7 +41,7 @@ __global__ __launch_bounds__(HDN_BLOCK) void logpolar_bwd_kernel(const float* __
     acc[0] = rn_mul(acc[0], mx);
     acc[1] = rn_mul(acc[1], my);
   }
-  if (part) block_sum_store<2>(acc, red, part + (size_t(n) * gridDim.x + blockIdx.x) * 2);  // kernel-uniform branch
+  if (part) block_sum_store<2, BLOCK_WAVES>(acc, red, part + (size_t(n) * gridDim.x + blockIdx.x) * 2);  // kernel-uniform branch
 }
 
 // ---------------------------------------------------------------------------------------------------------------- DLT solve
@@ -84,7 +84,7 @@ __global__ __launch_bounds__(HDN_BLOCK) void dlt_solve_bwd_kernel(const float* _
 __global__ __launch_bounds__(HDN_BLOCK) void warp_bwd_kernel(const float* __restrict__ img, const float* __restrict__ theta,
                                                              const float* __restrict__ gout, float* __restrict__ part,
                                                              float* __restrict__ gimg, int C, int H, int W) {
-  __shared__ float red[WAVES * 9];
+  __shared__ float red[BLOCK_WAVES * 9];
   const int b = blockIdx.y;
   const size_t HW = size_t(H) * W;
   float th[9];
@@ -119,7 +119,7 @@ __global__ __launch_bounds__(HDN_BLOCK) void warp_bwd_kernel(const float* __rest
       acc[6] = rn_add(acc[6], rn_mul(g2, p.gx)); acc[7] = rn_add(acc[7], rn_mul(g2, p.gy)); acc[8] = rn_add(acc[8], g2);
     }
   }
-  if (part) block_sum_store<9>(acc, red, part + (size_t(b) * gridDim.x + blockIdx.x) * 9);  // kernel-uniform branch
+  if (part) block_sum_store<9, BLOCK_WAVES>(acc, red, part + (size_t(b) * gridDim.x + blockIdx.x) * 9);  // kernel-uniform branch
 }
 
 }  // namespace gbwd

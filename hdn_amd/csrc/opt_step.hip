@@ -18,6 +18,7 @@
 // Bounds: chunk c of tensor t covers elements [c CHUNK, min(numel, (c + 1) CHUNK)) of p, g and slot[t] + the same of the moments; the entry point
 // checks slot[t] + numel[t] <= state_floats and the partial count before any launch.
 #include "hdn_common.h"
+#include "reduce.h"
 
 #include <math.h>
 
@@ -63,7 +64,7 @@ __device__ __forceinline__ int find_tensor(const int* chunk0, int n, int chunk) 
 }
 
 __global__ __launch_bounds__(HDN_BLOCK) void sqnorm_kernel(const NormTable tb, double* __restrict__ partials) {
-  __shared__ double red[HDN_BLOCK / HDN_WAVE];
+  __shared__ double red[BLOCK_WAVES];
   const int tid = threadIdx.x;
   const int total = tb.chunk0[tb.n];
   for (int chunk = blockIdx.x; chunk < total; chunk += gridDim.x) {
@@ -91,12 +92,8 @@ __global__ __launch_bounds__(HDN_BLOCK) void sqnorm_kernel(const NormTable tb, d
         for (int i = tid; i < count; i += HDN_BLOCK) acc += (double)g[i] * (double)g[i];
       }
     }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, HDN_WAVE);
-    if ((tid & (HDN_WAVE - 1)) == 0) red[tid >> 6] = acc;
-    __syncthreads();
-    if (tid == 0) partials[chunk] = ((red[0] + red[1]) + red[2]) + red[3];
-    __syncthreads();  // red is written again in the next round
+    acc = block_sum<BLOCK_WAVES>(acc, red);  // its leading barrier: red is written again in the next round
+    if (tid == 0) partials[chunk] = acc;
   }
 }
 
@@ -110,7 +107,7 @@ __global__ __launch_bounds__(HDN_BLOCK) void gate_kernel(const double* __restric
   const int tid = threadIdx.x;
   double acc = 0.0;
   for (long long i = tid; i < n_partials; i += HDN_BLOCK) acc += partials[i];
-  red[tid] = acc;
+  red[tid] = acc;  // not reduce.h's order: a 256-slot LDS tree over doubles (strides 128 .. 1), kept because grad_norm's bits are pinned by it
   __syncthreads();
   for (int s = HDN_BLOCK / 2; s >= 1; s >>= 1) {
     if (tid < s) red[tid] += red[tid + s];

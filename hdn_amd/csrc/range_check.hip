@@ -10,6 +10,7 @@
 
 #include "hdn_common.h"
 #include "mfma_split.h"
+#include "reduce.h"
 
 namespace hdn {
 namespace {
@@ -20,9 +21,8 @@ __global__ __launch_bounds__(HDN_BLOCK) void absmax_kernel(const float* __restri
   unsigned m = 0;
   for (long long i = (long long)blockIdx.x * HDN_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * HDN_BLOCK)
     m = max(m, __float_as_uint(x[i]) & 0x7fffffffu);           // |x| as bits: ordered like the value; NaN sorts above inf
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
-  if ((threadIdx.x & 63) == 0 && m) atomicMax(out, m);
+  m = wave_max(m);
+  if (lane_id() == 0 && m) atomicMax(out, m);
 }
 
 }  // namespace

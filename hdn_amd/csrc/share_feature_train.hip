@@ -11,18 +11,19 @@
 // is 64 KB and the whole step is launch- and bandwidth-bound); padding is zero in activation space, so a tap outside the plane contributes 0, not
 // relu(beta).
 //
-// Every sum over pixels is deterministic and uses no atomics: a thread adds its pixels in ascending order, a wave its lanes in a fixed xor tree
-// (32 .. 1), a workgroup its waves in ascending order through LDS, and the workgroup writes one partial into the workspace; the finish launch adds the
-// partials in a fixed order (thread t takes partials t, t + T, ..., then the same tree).  The statistics and S1 / S2 are carried in float64 from the
+// Every sum over pixels is deterministic and uses no atomics: a thread adds its pixels in ascending order, the workgroup adds its threads in the fixed
+// order of reduce.h and writes one partial into the workspace; the finish launch adds the partials in a fixed order (thread t takes partials
+// t, t + T, ..., then the same reduction).  The statistics and S1 / S2 are carried in float64 from the
 // first add on (fp64 adds are not the limit here); the weight gradients add fp32 products in fp32 inside a workgroup (1024 terms, a tree) and in
 // float64 across workgroups.  grad_img is a gather like every other plane, so it is bit-reproducible too.
 #include "hdn_common.h"
+#include "reduce.h"
 
 namespace hdn {
 namespace sft {
 
-constexpr int WAVES = HDN_BLOCK / HDN_WAVE;
-constexpr int PX = 4;                  // pixels per thread
+constexpr int WAVES = BLOCK_WAVES;
+constexpr int PX = 4;                 // pixels per thread
 constexpr int PXB = HDN_BLOCK * PX;    // pixels per workgroup
 constexpr int NCH = 13;                // 4 + 8 + 1 BatchNorm channels, layers concatenated
 constexpr int NPAR = 36 + 288 + 72 + 13 + 13;
@@ -37,42 +38,11 @@ __device__ __forceinline__ void make_ab(float gamma, float bias, float mean, flo
   *beta = __builtin_fmaf(-mean, a, bias);
 }
 
-// v[q] summed over the workgroup in a fixed order; thread q < N then writes the sum to dst[q * stride].  lds: WAVES * N values.  Every thread calls it.
-template <int N, typename T>
-__device__ __forceinline__ void block_sum_store(T (&v)[N], T* lds, T* __restrict__ dst, size_t stride) {
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int q = 0; q < N; ++q) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v[q] = v[q] + __shfl_xor(v[q], m, HDN_WAVE);
-  }
-  if ((tid & (HDN_WAVE - 1)) == 0) {
-#pragma unroll
-    for (int q = 0; q < N; ++q) lds[(tid >> 6) * N + q] = v[q];
-  }
-  __syncthreads();
-  if (tid < N) {
-    T s = lds[tid];
-#pragma unroll
-    for (int w = 1; w < WAVES; ++w) s = s + lds[w * N + tid];
-    dst[size_t(tid) * stride] = s;
-  }
-}
-
 // p[0], p[stride], ... p[(n - 1) stride] added in a fixed order by the whole workgroup; every thread gets the sum.  lds: WAVES doubles.
 __device__ __forceinline__ double block_total(const double* __restrict__ p, int n, int stride, double* lds) {
-  const int tid = threadIdx.x;
   double s = 0.0;
-  for (int k = tid; k < n; k += HDN_BLOCK) s += p[size_t(k) * stride];
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, HDN_WAVE);
-  if ((tid & (HDN_WAVE - 1)) == 0) lds[tid >> 6] = s;
-  __syncthreads();
-  double t = lds[0];
-#pragma unroll
-  for (int w = 1; w < WAVES; ++w) t += lds[w];
-  __syncthreads();
-  return t;
+  for (int k = threadIdx.x; k < n; k += HDN_BLOCK) s += p[size_t(k) * stride];
+  return block_sum<WAVES>(s, lds);
 }
 
 // the activation a = relu(c alpha + beta) of one input channel at (y, x), 0 outside the plane; FIRST: the plane is the image itself
@@ -127,7 +97,7 @@ __global__ __launch_bounds__(HDN_BLOCK) void conv_stats_kernel(const float* __re
       sums[2 * co + 1] += d * d;
     }
   }
-  if (part) block_sum_store<2 * CO, double>(sums, red, part + size_t(blockIdx.x) * 2 * CO, 1);  // kernel-uniform branch
+  if (part) block_sum_store<2 * CO, WAVES>(sums, red, part + size_t(blockIdx.x) * 2 * CO);  // kernel-uniform branch
 }
 
 // one workgroup: the partials of CO channels -> mean, invstd, unbiased variance (stats[ch0 ..], three rows of NCH) and the table entries
@@ -203,7 +173,7 @@ __global__ __launch_bounds__(HDN_BLOCK) void bn_reduce_kernel(const float* __res
       sums[2 * co + 1] += (double)dz * (double)xh;
     }
   }
-  block_sum_store<2 * CO, double>(sums, red, part + size_t(blockIdx.x) * 2 * CO, 1);
+  block_sum_store<2 * CO, WAVES>(sums, red, part + size_t(blockIdx.x) * 2 * CO);
 }
 
 // one workgroup: S1, S2 of CO channels into the table (for the apply launch) and, gpar != NULL, into grad_bias / grad_gamma
@@ -304,27 +274,22 @@ __global__ __launch_bounds__(HDN_BLOCK) void conv_weight_adjoint_kernel(const fl
       for (int k = 0; k < 9; ++k) acc[co * 9 + k] = __builtin_fmaf(d, a[k], acc[co * 9 + k]);
     }
   }
-  // thread q = co 9 + k of the store owns weight (co, ci, k)
-  const int nblk = gridDim.x;
-  {
-    const int tid = threadIdx.x;
+  // block_sum_store's order with the store spelled out: thread q = co 9 + k owns weight (co, ci, k), whose place (co CI 9 + ci 9 + k) nblk + blk
+  // is no base + q stride once CI > 1
+  const int nblk = gridDim.x, tid = threadIdx.x;
 #pragma unroll
-    for (int q = 0; q < CO * 9; ++q) {
+  for (int q = 0; q < CO * 9; ++q) acc[q] = wave_sum(acc[q]);
+  if (lane_id() == 0) {
 #pragma unroll
-      for (int m = 32; m >= 1; m >>= 1) acc[q] = rn_add(acc[q], __shfl_xor(acc[q], m, HDN_WAVE));
-    }
-    if ((tid & (HDN_WAVE - 1)) == 0) {
+    for (int q = 0; q < CO * 9; ++q) red[wave_id() * CO * 9 + q] = acc[q];
+  }
+  __syncthreads();
+  if (tid < CO * 9) {
+    float s = red[tid];
 #pragma unroll
-      for (int q = 0; q < CO * 9; ++q) red[(tid >> 6) * CO * 9 + q] = acc[q];
-    }
-    __syncthreads();
-    if (tid < CO * 9) {
-      float s = red[tid];
-#pragma unroll
-      for (int wv = 1; wv < WAVES; ++wv) s = rn_add(s, red[wv * CO * 9 + tid]);
-      const int co = tid / 9, k = tid - co * 9;
-      part[size_t((co * CI + ci) * 9 + k) * nblk + blockIdx.x] = s;
-    }
+    for (int wv = 1; wv < WAVES; ++wv) s = rn_add(s, red[wv * CO * 9 + tid]);
+    const int co = tid / 9, k = tid - co * 9;
+    part[size_t((co * CI + ci) * 9 + k) * nblk + blockIdx.x] = s;
   }
 }
 
@@ -333,8 +298,7 @@ __global__ __launch_bounds__(HDN_WAVE) void weight_finish_kernel(const float* __
   const float* p = part + size_t(blockIdx.x) * nblk;
   double s = 0.0;
   for (int k = threadIdx.x; k < nblk; k += HDN_WAVE) s += (double)p[k];
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, HDN_WAVE);
+  s = wave_sum(s);
   if (threadIdx.x == 0) gw[blockIdx.x] = (float)s;
 }
 

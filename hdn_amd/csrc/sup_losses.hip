@@ -5,8 +5,8 @@
 //
 // One launch, one workgroup of T = 1024 threads per loss (blockIdx.x = loss; a loss whose pointers are NULL returns at once).  Everything the
 // reference selects with nonzero() is a predicate here: the sample mask (if_unsup[b] == 0), the label tests, the label maximum of (b), the counts and
-// the top-k of (a).  Thread t owns the cells t, t + T, ... and adds its terms in ascending order; a xor butterfly adds the 64 lanes of a wave and
-// every thread adds the 16 wave sums in wave order: the order is fixed, so every output is bit-reproducible.  No float atomics.
+// the top-k of (a).  Thread t owns the cells t, t + T, ... and adds its terms in ascending order; the workgroup adds its threads with block_sum
+// of reduce.h: the order is fixed, so every output is bit-reproducible.  No float atomics.
 //
 // Top-k of (a): l = -log(1 - p) is positive, so its bit pattern orders as its value.  The l of every negative cell is kept in LDS (4 bytes per cell,
 // 0 for a cell that is no negative: at most MAX_CELLS = 40000 cells, 156.25 KiB, which is where the limit comes from), and the k-th largest is found
@@ -14,6 +14,7 @@
 // the k largest is sum{l > t} + (k - count_gt) t.  The backward repeats the selection (same device function, same bits), then ranks the cells equal to
 // t by flat index over contiguous chunks and an exclusive scan, and keeps the lowest k - count_gt of them.
 #include "hdn_common.h"
+#include "reduce.h"
 
 #pragma clang fp contract(off)
 
@@ -33,45 +34,9 @@ struct Scratch {
   int pick[2];
 };
 
-__device__ __forceinline__ float block_sum(float v, Scratch& s) {
-#pragma unroll
-  for (int m = HDN_WAVE / 2; m >= 1; m >>= 1) v = rn_add(v, __shfl_xor(v, m, HDN_WAVE));
-  __syncthreads();
-  if ((threadIdx.x & (HDN_WAVE - 1)) == 0) s.f[threadIdx.x / HDN_WAVE] = v;
-  __syncthreads();
-  float t = s.f[0];
-#pragma unroll
-  for (int w = 1; w < NW; ++w) t = rn_add(t, s.f[w]);
-  return t;
-}
-
-__device__ __forceinline__ int block_sum(int v, Scratch& s) {
-#pragma unroll
-  for (int m = HDN_WAVE / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, HDN_WAVE);
-  __syncthreads();
-  if ((threadIdx.x & (HDN_WAVE - 1)) == 0) s.i[threadIdx.x / HDN_WAVE] = v;
-  __syncthreads();
-  int t = 0;
-#pragma unroll
-  for (int w = 0; w < NW; ++w) t += s.i[w];
-  return t;
-}
-
-__device__ __forceinline__ float block_max(float v, Scratch& s) {   // NaN-free input
-#pragma unroll
-  for (int m = HDN_WAVE / 2; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, HDN_WAVE));
-  __syncthreads();
-  if ((threadIdx.x & (HDN_WAVE - 1)) == 0) s.f[threadIdx.x / HDN_WAVE] = v;
-  __syncthreads();
-  float t = s.f[0];
-#pragma unroll
-  for (int w = 1; w < NW; ++w) t = fmaxf(t, s.f[w]);
-  return t;
-}
-
-// exclusive prefix sum of one int per thread, in thread order
+// exclusive prefix sum of one int per thread, in thread order (a scan, not a reduction: it is not in reduce.h)
 __device__ __forceinline__ int block_scan_exclusive(int v, Scratch& s) {
-  const int lane = threadIdx.x & (HDN_WAVE - 1), wave = threadIdx.x / HDN_WAVE;
+  const int lane = lane_id(), wave = wave_id();
   int inc = v;
 #pragma unroll
   for (int d = 1; d < HDN_WAVE; d <<= 1) {
@@ -92,7 +57,7 @@ __device__ __forceinline__ int count_samples(const float* __restrict__ mask, int
   if (!mask) return B;
   int n = 0;
   for (int b = threadIdx.x; b < B; b += T) n += mask[b] == 0.f;
-  return block_sum(n, s);
+  return block_sum<NW>(n, s.i);
 }
 
 __device__ __forceinline__ float sgn(float x) { return x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f); }
@@ -169,9 +134,9 @@ __device__ SelA select_a(const float* __restrict__ cls, const float* __restrict_
     lb[i] = bits;
   }
   SelA r;
-  r.n_pos = block_sum(n_pos, s);
-  n_neg = block_sum(n_neg, s);
-  r.pos_sum = block_sum(pos_sum, s);
+  r.n_pos = block_sum<NW>(n_pos, s.i);
+  n_neg = block_sum<NW>(n_neg, s.i);
+  r.pos_sum = block_sum<NW>(pos_sum, s.f);
   const long long k = (long long)topk * n;
   r.k_eff = n_neg <= 1 ? 0 : (int)(k < n_neg ? k : n_neg);     // one negative: the reference's 0-d index, the term is 0
   r.rem = 0;
@@ -210,7 +175,7 @@ __device__ SelA select_a(const float* __restrict__ cls, const float* __restrict_
     const unsigned bits = lb[i];
     if (bits > prefix) acc = rn_add(acc, __uint_as_float(bits));
   }
-  r.top_sum = rn_add(block_sum(acc, s), rn_mul((float)rem, __uint_as_float(prefix)));
+  r.top_sum = rn_add(block_sum<NW>(acc, s.f), rn_mul((float)rem, __uint_as_float(prefix)));
   return r;
 }
 
@@ -287,8 +252,8 @@ __device__ float threshold_b(const float* __restrict__ flabel, const float* __re
       const float L = flabel[i];
       if (L != L) nan = 1; else m = fmaxf(m, L);
     }
-  m = block_max(m, s);
-  nan = block_sum(nan, s);
+  m = block_max<NW>(m, s.f);
+  nan = block_sum<NW>(nan, s.i);
   return nan ? __builtin_nanf("") : rn_sub(m, 0.2f);
 }
 
@@ -311,8 +276,8 @@ __device__ void fwd_smooth(const float* __restrict__ pred, const float* __restri
       acc = rn_add(acc, smooth_l1(rn_sub(pred[idx], tgt[idx])));
     }
   }
-  n_sel = block_sum(n_sel, s);
-  acc = block_sum(acc, s);
+  n_sel = block_sum<NW>(n_sel, s.i);
+  acc = block_sum<NW>(acc, s.f);
   if (threadIdx.x == 0) *out = (one_hit_zero && n_sel <= 1) ? 0.f : rn_div(acc, (float)(C * n_sel + 1));
 }
 
@@ -321,7 +286,7 @@ __device__ void bwd_smooth(const float* __restrict__ pred, const float* __restri
   const float thr = kind == 1 ? threshold_b(flabel, mask, B, S2, s) : 0.f;
   int n_sel = 0;
   for (int i = threadIdx.x; i < B * S2; i += T) n_sel += sample_on(mask, i / S2) && cell_on(kind, flabel, ilabel, thr, i);
-  n_sel = block_sum(n_sel, s);
+  n_sel = block_sum<NW>(n_sel, s.i);
   const float gs = (one_hit_zero && n_sel <= 1) ? 0.f : rn_div(g, (float)(C * n_sel + 1));
   for (int i = threadIdx.x; i < B * S2; i += T) {
     const int b = i / S2, c = i - b * S2;
@@ -362,10 +327,10 @@ __device__ void fwd_c(const float* __restrict__ x, const long long* __restrict__
       ++n0;
     }
   }
-  n1 = block_sum(n1, s);
-  n0 = block_sum(n0, s);
-  s1 = block_sum(s1, s);
-  s0 = block_sum(s0, s);
+  n1 = block_sum<NW>(n1, s.i);
+  n0 = block_sum<NW>(n0, s.i);
+  s1 = block_sum<NW>(s1, s.f);
+  s0 = block_sum<NW>(s0, s.f);
   const float pos = n1 <= 1 ? 0.f : rn_div(s1, (float)n1), neg = n0 <= 1 ? 0.f : rn_div(s0, (float)n0);
   if (threadIdx.x == 0) *out = rn_add(rn_mul(pos, 0.5f), rn_mul(neg, 0.5f));
 }
@@ -378,8 +343,8 @@ __device__ void bwd_c(const float* __restrict__ x, const long long* __restrict__
       n1 += label[i] == 1;
       n0 += label[i] == 0;
     }
-  n1 = block_sum(n1, s);
-  n0 = block_sum(n0, s);
+  n1 = block_sum<NW>(n1, s.i);
+  n0 = block_sum<NW>(n0, s.i);
   const float u1 = n1 <= 1 ? 0.f : -rn_div(rn_mul(0.5f, g), (float)n1), u0 = n0 <= 1 ? 0.f : -rn_div(rn_mul(0.5f, g), (float)n0);
   for (int i = threadIdx.x; i < B * S2; i += T) {
     const int b = i / S2, c = i - b * S2;

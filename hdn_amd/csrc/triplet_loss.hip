@@ -4,8 +4,8 @@
 // difference inside the absolute value, the loss is clamp_min((margin + d_ap) - d_an, 0).
 //
 // One wave per row, HDN_BLOCK / HDN_WAVE = 4 rows per workgroup.  A row of the reference is 127 floats and only 4-byte aligned, so lane l reads the
-// dwords l, l + 64, ... of the three rows (coalesced, no wider access anywhere) and the two distances are reduced by a xor butterfly, which leaves the
-// same sum in every lane.  The call is three reads of a 2 MB tensor at B = 32: launch and latency, not bandwidth; 3048 waves at 24 x 127 rows.
+// dwords l, l + 64, ... of the three rows (coalesced, no wider access anywhere) and the two distances are reduced by wave_sum of reduce.h, which
+// leaves the same sum in every lane.  The call is three reads of a 2 MB tensor at B = 32: launch and latency, not bandwidth; 3048 waves at 24 x 127 rows.
 //
 // The gather is folded into the addressing: with `ids`, row r of the result is row r % R of sample ids[r / R]; no gathered copy exists.  The sample
 // index is checked against [0, N) before any address is formed: an index outside gives NaN loss rows and takes no part in the backward.
@@ -15,6 +15,7 @@
 // forward's own function, so the decision v >= 0 is made on the forward's bits - and writes g sgn(.) per element, or zeros for a row that is not
 // selected or not active.  Every gradient element is written exactly once by one lane: no atomics, no zero-fill pass, bit-reproducible.
 #include "hdn_common.h"
+#include "reduce.h"
 
 #pragma clang fp contract(off)
 
@@ -29,7 +30,7 @@ __device__ __forceinline__ float term(float x, float y, float eps) { return fabs
 __device__ __forceinline__ float sgn(float x) { return x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f); }  // sgn(0) = 0; NaN -> 0
 
 // v = (margin + d_ap) - d_an of one row, the same value in every lane of the wave.  Lane l adds the elements l, l + 64, ... in ascending order, then
-// the butterfly adds the 64 partial sums.  The forward and the backward both call it.
+// wave_sum (reduce.h) adds the 64 partial sums.  The forward and the backward both call it.
 __device__ __forceinline__ float row_v(const float* __restrict__ a, const float* __restrict__ p, const float* __restrict__ n, int D, int lane,
                                        float margin, float eps) {
   float d_ap = 0.f, d_an = 0.f;
@@ -38,12 +39,7 @@ __device__ __forceinline__ float row_v(const float* __restrict__ a, const float*
     d_ap = rn_add(d_ap, term(av, pv, eps));
     d_an = rn_add(d_an, term(av, nv, eps));
   }
-#pragma unroll
-  for (int m = HDN_WAVE / 2; m >= 1; m >>= 1) {
-    d_ap = rn_add(d_ap, __shfl_xor(d_ap, m, HDN_WAVE));
-    d_an = rn_add(d_an, __shfl_xor(d_an, m, HDN_WAVE));
-  }
-  return rn_sub(rn_add(margin, d_ap), d_an);
+  return rn_sub(rn_add(margin, wave_sum(d_ap)), wave_sum(d_an));
 }
 
 __global__ __launch_bounds__(HDN_BLOCK) void fwd_kernel(const float* __restrict__ a, const float* __restrict__ p, const float* __restrict__ n,
@@ -169,8 +165,7 @@ int hdn_triplet_l1_bwd_f32(const float* anchor, const float* positive, const flo
 //
 // Forward, two launches in one call.  rows: one wave per row of [N,R,D], as fwd_kernel; the row's clamped loss (row_v(), the bits of the kernels
 // above) goes to partial[row], 0 for a row of a sample that is not used, whose data is not read.  finish: ONE workgroup of 1024 threads; thread t
-// adds partial[t], partial[t + 1024], ... in ascending order, a wave adds its lanes in a fixed xor tree, thread 0 adds the sixteen waves in
-// ascending order: the order depends on (N, R) alone, no float atomics, no hand-off between workgroups inside a launch (the stream orders the two
+// adds partial[t], partial[t + 1024], ... in ascending order, block_sum of reduce.h adds the threads: the order depends on (N, R) alone, no float atomics, no hand-off between workgroups inside a launch (the stream orders the two
 // kernels).  Backward: one wave per gradient row, every element written exactly once.  Each workgroup counts the sets itself (integers: no order).
 // Bounds: a flag index is < N, a row index < N R, an element index < N R D; partial has N R floats.
 namespace hdn {
@@ -186,31 +181,18 @@ __device__ __forceinline__ bool is_neg(float pos) { return pos == 0.f; }        
 // is a sample read?  rule 0: the selected ones; rule 1: the selected ones where the batch has a negative, every sample otherwise; none while n_sel = 0
 __device__ __forceinline__ bool sample_used(bool sel, int rule, int n_sel, int n_neg) { return n_sel > 0 && (sel || (rule == 1 && n_neg == 0)); }
 
-// n_sel and n_neg of the batch, the same in every thread.  Every thread of the workgroup calls it (one barrier); red: 2 BLOCK / 64 ints of LDS.
+// n_sel and n_neg of the batch, the same in every thread.  Every thread of the workgroup calls it (block_sum's barriers); red: 2 BLOCK / 64 ints of LDS.
 template <int BLOCK>
 __device__ __forceinline__ void count_sets(const float* __restrict__ if_pos, const float* __restrict__ if_unsup, int N, int* red, int& n_sel,
                                            int& n_neg) {
-  int cs = 0, cn = 0;
+  int c[2] = {0, 0};
   for (int i = threadIdx.x; i < N; i += BLOCK) {
     const float pos = if_pos[i];
-    cs += is_sel(pos, if_unsup[i]) ? 1 : 0;
-    cn += is_neg(pos) ? 1 : 0;
+    c[0] += is_sel(pos, if_unsup[i]) ? 1 : 0;
+    c[1] += is_neg(pos) ? 1 : 0;
   }
-#pragma unroll
-  for (int m = HDN_WAVE / 2; m >= 1; m >>= 1) {
-    cs += __shfl_xor(cs, m, HDN_WAVE);
-    cn += __shfl_xor(cn, m, HDN_WAVE);
-  }
-  if ((threadIdx.x & (HDN_WAVE - 1)) == 0) {
-    red[2 * (threadIdx.x / HDN_WAVE)] = cs;
-    red[2 * (threadIdx.x / HDN_WAVE) + 1] = cn;
-  }
-  __syncthreads();
-  n_sel = 0, n_neg = 0;
-  for (int w = 0; w < BLOCK / HDN_WAVE; ++w) {
-    n_sel += red[2 * w];
-    n_neg += red[2 * w + 1];
-  }
+  block_sum<BLOCK / HDN_WAVE>(c, red);
+  n_sel = c[0], n_neg = c[1];
 }
 
 __global__ __launch_bounds__(HDN_BLOCK) void mean_rows_kernel(const float* __restrict__ a, const float* __restrict__ p, const float* __restrict__ n,
@@ -241,13 +223,8 @@ __global__ __launch_bounds__(FIN_BLOCK) void mean_finish_kernel(const float* __r
   count_sets<FIN_BLOCK>(if_pos, if_unsup, N, red, n_sel, n_neg);
   float acc = 0.f;
   for (long long i = threadIdx.x; i < rows; i += FIN_BLOCK) acc = rn_add(acc, partial[i]);
-#pragma unroll
-  for (int m = HDN_WAVE / 2; m >= 1; m >>= 1) acc = rn_add(acc, __shfl_xor(acc, m, HDN_WAVE));
-  if ((threadIdx.x & (HDN_WAVE - 1)) == 0) red_f[threadIdx.x / HDN_WAVE] = acc;
-  __syncthreads();
+  const float S = block_sum<FIN_BLOCK / HDN_WAVE>(acc, red_f);
   if (threadIdx.x != 0) return;
-  float S = red_f[0];
-  for (int w = 1; w < FIN_BLOCK / HDN_WAVE; ++w) S = rn_add(S, red_f[w]);
   const float ns = (float)n_sel;
   out[0] = n_sel > 0 ? (rule == 0 ? rn_div(rn_div(S, denom), ns) : rn_div(rn_div(S, ns), denom)) : 0.f;
   counts[0] = n_sel;
