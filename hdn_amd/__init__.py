@@ -19,6 +19,7 @@ from .simi_train import SimiTrainConfig, simi_training_forward  # noqa: F401
 from .optim import GatedAMSGrad, grad_norm  # noqa: F401
 from .heads import MultiBAN, MultiCircBAN  # noqa: F401
 from .conv_train import conv3x3_valid, depthwise_xcorr_train_forward  # noqa: F401
+from .bn_train import batchnorm_relu_train  # noqa: F401
 from .refine import homo_refine, refine_warp  # noqa: F401
 
 __version__ = "0.1.0"

@@ -112,6 +112,10 @@ SIGNATURES = {
     "hdn_conv3x3v_wgrad_workspace_bytes": (ctypes.c_longlong, [_i] * 4),
     "hdn_conv3x3v_wgrad_form": (_i, [_i] * 4),
     "hdn_conv3x3v_wgrad_f32": (_i, [_c_float_p, _c_float_p, ctypes.c_void_p, _c_float_p, ctypes.c_void_p, ctypes.c_longlong] + [_i] * 4 + [ctypes.c_void_p]),
+    "hdn_bn_relu_train_workspace_bytes": (ctypes.c_longlong, [_i] * 3),
+    "hdn_bn_relu_train_form": (_i, [_i] * 3),
+    "hdn_bn_relu_train_fwd_f32": (_i, [_c_float_p] * 7 + [ctypes.c_double] * 2 + [ctypes.c_void_p, ctypes.c_longlong] + [_i] * 5 + [ctypes.c_void_p]),
+    "hdn_bn_relu_train_bwd_f32": (_i, [_c_float_p] * 8 + [ctypes.c_void_p, ctypes.c_longlong] + [_i] * 5 + [ctypes.c_void_p]),
     "hdn_pack_simi_stem_bytes": (ctypes.c_longlong, []),
     "hdn_pack_simi_stem_f32": (_i, [_c_float_p, ctypes.c_void_p, ctypes.c_longlong]),
     "hdn_simi_stem_f32": (_i, [_c_float_p, ctypes.c_void_p, _c_float_p, _c_float_p] + [_i] * 3 + [ctypes.c_void_p]),

@@ -2,7 +2,8 @@
 
     conv3x3_valid(x, weight)                 autograd Function: forward hdn_conv3x3v_f32, backward hdn_conv3x3v_dgrad_f32 / hdn_conv3x3v_wgrad_f32
     depthwise_xcorr_train_forward(...)       DepthwiseXCorr.forward / DepthwiseXCorrCirc.forward (ban.py:73-78, ban_lp.py:35-40) with the two 3x3
-                                             convolutions on conv3x3_valid; BatchNorm, ReLU, the correlation and the 1x1 tail are the modules' own
+                                             convolutions on conv3x3_valid and, while install.HEAD_BN_TRAIN_BOUND, their BatchNorm + ReLU on
+                                             bn_train.batchnorm_relu_train; the correlation and the 1x1 tail are the modules' own
 
 The weight streams are rebuilt ON THE DEVICE by hdn_pack_conv3x3d_dev_f32 at every call: a replayed optimizer step changes the weight's bytes in place,
 which no version counter sees, so nothing about a weight is cached but the BUFFER its stream is written to.  After the first call of a shape nothing is
@@ -13,7 +14,7 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib
+from . import _lib, bn_train
 
 _cache = {}   # (device index, what, CO, CI[, B, S]) -> persistent device buffer (packed streams, the exponent, the packer's counter)
 launches = {"pack": 0, "forward": 0, "scale": 0, "dgrad": 0, "wgrad": 0}   # calls made, for tests ("launches only what is asked")
@@ -164,11 +165,22 @@ def qualifies(conv, x=None) -> bool:
 
 
 def _branch(seq, x):
-    """seq = Sequential(Conv2d, BatchNorm2d, ReLU): the convolution through conv3x3_valid when it qualifies, then the sequential's own remaining modules
-    (running statistics, momentum and eps stay PyTorch's)."""
+    """seq = Sequential(Conv2d, BatchNorm2d, ReLU): the convolution through conv3x3_valid when it qualifies; then, while install.HEAD_BN_TRAIN_BOUND
+    (read now) and the sequential is exactly that triple with a BatchNorm2d in training mode that bn_train.qualifies, BatchNorm + ReLU as one
+    batchnorm_relu_train on the module's own parameters and buffers (channels-last in, contiguous NCHW out; num_batches_tracked advanced on the
+    device); else the sequential's own remaining modules."""
     if not (isinstance(seq, torch.nn.Sequential) and len(seq) >= 1 and qualifies(seq[0], x)):
         return seq(x)
     y = conv3x3_valid(x, seq[0].weight)
+    from . import install   # (install imports this module)
+    # (seq[1].training: a BatchNorm2d frozen by its own .eval() inside a .train() parent normalises by its running statistics and leaves them alone)
+    if (install.HEAD_BN_TRAIN_BOUND and len(seq) == 3 and isinstance(seq[2], torch.nn.ReLU) and seq[1].training
+            and bn_train.qualifies(seq[1], y)):
+        bn = seq[1]
+        y = bn_train.batchnorm_relu_train(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps, relu=True, out_nchw=True)
+        if bn.num_batches_tracked is not None:
+            bn.num_batches_tracked.add_(1)
+        return y
     for m in list(seq)[1:]:
         y = m(y)
     return y

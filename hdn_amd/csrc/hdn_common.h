@@ -166,6 +166,22 @@ inline bool bytes_overlap(const void* a, long long na, const void* b, long long 
   return pa < pb + nb && pb < pa + na;
 }
 
+// an operand of an entry point as a byte range (p NULL: absent)
+struct Range {
+  const void* p;
+  long long bytes;
+};
+
+// does any of the first n_out ranges (the outputs) overlap another range of the list?
+inline bool any_output_overlaps(const Range* r, int n_out, int n) {
+  for (int i = 0; i < n_out; ++i) {
+    if (!r[i].p) continue;
+    for (int j = i + 1; j < n; ++j)
+      if (r[j].p && bytes_overlap(r[i].p, r[i].bytes, r[j].p, r[j].bytes)) return true;
+  }
+  return false;
+}
+
 // the entry points' checks of a K-slice workspace of `need` bytes (need <= 0: none is used, nothing is checked) beside the input x and the output:
 // NULL -> HDN_E_NULL, unaligned or too small -> HDN_E_LIMIT, overlapping x or out -> HDN_E_ALIAS, in that order
 inline int check_workspace(const void* ws, long long ws_bytes, long long need, const void* x, long long x_bytes, const void* out, long long out_bytes) {

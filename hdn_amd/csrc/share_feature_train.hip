@@ -303,21 +303,6 @@ __global__ __launch_bounds__(HDN_WAVE) void weight_finish_kernel(const float* __
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host
-struct Range {
-  const void* p;
-  long long bytes;
-};
-
-// does any of the first n_out ranges (the outputs) overlap another range of the list?
-static bool any_output_overlaps(const Range* r, int n_out, int n) {
-  for (int i = 0; i < n_out; ++i) {
-    if (!r[i].p) continue;
-    for (int j = i + 1; j < n; ++j)
-      if (r[j].p && bytes_overlap(r[i].p, r[i].bytes, r[j].p, r[j].bytes)) return true;
-  }
-  return false;
-}
-
 static int check_shape(int B, int H, int W) {
   if (B <= 0 || H <= 0 || W <= 0) return HDN_E_SHAPE;
   if ((long long)B * H * W * NCH > 0x7fffffffLL) return HDN_E_LIMIT;

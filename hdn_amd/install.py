@@ -26,7 +26,8 @@ attribute the reference resolves at call time:
     model_builder_e2e_unconstrained_v2.{lp_pick, combine_affine_c0_v2, combine_affine_lt0}   :27-28 (install(train=True), while
         hdn.models.logpolar.Polar_Pick.get_polar_from_two_para_loc       SIMI_GEOMETRY_TRAIN_BOUND) the drop-ins of hdn_amd/simi_geometry.py
     DepthwiseXCorr.forward / DepthwiseXCorrCirc.forward  (install(train=True), while HEAD_CONV_TRAIN_BOUND) in .train() mode the two 3x3 convolutions
-                                                         on hdn_amd.conv3x3_valid (hdn_amd/conv_train.py); the class's own forward otherwise
+                                                         on hdn_amd.conv3x3_valid (hdn_amd/conv_train.py) and, while HEAD_BN_TRAIN_BOUND, their
+                                                         BatchNorm + ReLU on hdn_amd.batchnorm_relu_train; the class's own forward otherwise
     hdn.tracker.tracker_builder.TRACKS['hdnTrackerHomoProje2e']   (install(tracker=True)) the device-resident tracker loop
 
 Training under install(train=True): every statement of the reference's training forwards that resolves to a drop-in is differentiable on the device -
@@ -170,6 +171,13 @@ POLAR_PICK_SITE = ("hdn.models.logpolar", "Polar_Pick", "get_polar_from_two_para
 # on the step's 24 convolutions at B = 32, beyond both sides' spread.
 HEAD_CONV_TRAIN_BOUND = True
 
+# Does that training forward also run a head branch's BatchNorm2d (batch statistics) + ReLU as one hdn_amd.bn_train.batchnorm_relu_train, channels-last
+# in and NCHW out, in place of the modules, the layout copies around the correlation and the copy behind the inplace ReLU?  It has no rebinding site of
+# its own: hdn_amd.conv_train._branch reads it at every call, inside the forward that HEAD_CONV_TRAIN_BOUND binds.  Set by the outcome of
+# tools/head_bn_train_bench.py (profiles/head_bn_train.json, "ahead"): True only while the HIP path is faster than the stock modules and copies on the
+# step's 24 sites at B = 32, beyond both sides' spread.
+HEAD_BN_TRAIN_BOUND = False
+
 # (module, class, the module attribute its forward resolves the correlation by)
 HEAD_CONV_SITES = (("hdn.models.head.ban", "DepthwiseXCorr", "xcorr_depthwise"), ("hdn.models.head.ban_lp", "DepthwiseXCorrCirc", "xcorr_depthwise_circular"))
 
@@ -243,7 +251,7 @@ def install(strict: bool = False, modules: dict = None, tracker: bool = False, t
     Polar_Pick.get_polar_from_two_para_loc to the drop-ins of hdn_amd.simi_geometry (only where the attribute exists; the method keeps the one it
     replaces for a points table that is not the analytic one) and, while HEAD_CONV_TRAIN_BOUND, DepthwiseXCorr.forward and DepthwiseXCorrCirc.forward
     (HEAD_CONV_SITES) to a dispatcher that runs hdn_amd.conv_train.depthwise_xcorr_train_forward in .train() mode and the class's own forward
-    otherwise; everything else is unchanged.  Returns the list of (module, attribute) pairs that were rebound;
+    otherwise (inside it, while HEAD_BN_TRAIN_BOUND, a branch's BatchNorm + ReLU run as hdn_amd.batchnorm_relu_train); everything else is unchanged.  Returns the list of (module, attribute) pairs that were rebound;
     with strict=True a site that cannot be imported raises instead of being skipped.  uninstall() reverses it."""
     done = []
 

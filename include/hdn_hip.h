@@ -1172,6 +1172,42 @@ int hdn_conv3x3v_wgrad_f32(const float* x, const float* dy, const int* exp, floa
                            void* stream);                                                                                               /* ban.py:55-64 */
 
 /*
+ * BatchNorm2d on batch statistics, optionally followed by ReLU, forward and backward — the pair between a head branch's 3x3 convolution and its
+ * correlation, hdn/models/head/ban.py:55-64, ban_lp.py:17-26 (bn_train.hip; additions to ABI 10).  One BatchNorm over N = B P values per channel, P the
+ * pixel count of one image; c is the pre-normalisation map, channels-last, [N][C] row-major:
+ *   mean = sum c / N                 var = sum (c - mean)^2 / N   (biased)
+ *   invstd = 1 / sqrt(var + eps)     alpha = gamma invstd
+ *   z = (c - mean) alpha + beta      y = relu ? max(z, 0) : z     (subtract first, then one fma; a NaN z stays a NaN in y)
+ *   backward, dz = dy [z > 0] (relu) or dy, the mask recomputed from c by the same statement of z:
+ *   S1 = sum dz    S2 = sum dz x^,  x^ = (c - mean) invstd    dbeta = S1    dgamma = S2    dc = alpha (dz - S1 / N - x^ S2 / N)
+ * Sums over pixels are float64 from the product on, rounded to fp32 once; fixed order, no atomics: two calls give the same bits, and the order
+ * depends on (B, P, C) and the launch form only (the form on (B, P, C) and the measurement switch below).
+ * Layouts: c and dc channels-last, 16-byte aligned.  y / dy by flag: 0 channels-last (16-byte aligned), 1 NCHW planes y[(b C + ch) P + p] (4-byte
+ * aligned).  stats: mean[C], invstd[C], written by the forward, read by the backward.  running_mean / running_var: NULL (track_running_stats=False) or
+ * updated in place, r = (1 - momentum) r + momentum s with s = mean or var N / (N - 1), in float64 from the float64 statistics, rounded once.
+ * Backward: a NULL gradient output is neither computed nor written; with dc NULL the apply pass is skipped; all three NULL: HDN_E_SHAPE.
+ * Checks, in this order: a required pointer NULL (ws where the form needs one): HDN_E_NULL; B, P or C not positive, C no multiple of 32, N < 2, a flag
+ * outside 0 / 1, eps <= 0, momentum outside [0, 1]: HDN_E_SHAPE; C > 2048, N C > 2^31 - 1, c / dc / ws (or a channels-last y / dy) not 16-byte aligned,
+ * ws too small: HDN_E_LIMIT; an output's byte range (y, stats, the running buffers, dc, dgamma, dbeta, ws) overlapping an input's or another
+ * output's: HDN_E_ALIAS.  Asynchronous on `stream`, allocates nothing, reads nothing back: can be captured into a graph.
+ * hdn_bn_relu_train_workspace_bytes: bytes needed by either direction, 0 = none (ws may be NULL), negative = HDN_E_*.  hdn_bn_relu_train_form: the launch
+ * form (0: one launch, a workgroup per 32 channels through statistics and normalisation; 1: partial sums, finish, apply), for tests and profiles, no
+ * part of the ABI.  Both host only.
+ * Measurement switch: the environment variable HDN_BN_TRAIN_FUSED_ROWS (a positive integer), read by the query, the form function and both entry
+ * points at every call, replaces the row count up to which form 0 is used (tools/head_bn_train_bench.py forces either form with it).  It is no
+ * tuning knob: leave it unset.  Whoever changes it between a workspace query and its launch gets HDN_E_LIMIT or NULL checks as for any wrong
+ * workspace; between two calls, another launch form and with it another (still fixed) summation order.
+ */
+long long hdn_bn_relu_train_workspace_bytes(int B, int P, int C);                                                                      /* ban.py:55-64 */
+int hdn_bn_relu_train_form(int B, int P, int C);                                                                                        /* ban.py:55-64 */
+int hdn_bn_relu_train_fwd_f32(const float* c, const float* gamma, const float* beta, float* y, float* stats, float* running_mean_or_null,
+                              float* running_var_or_null, double momentum, double eps, void* ws, long long ws_bytes, int B, int P, int C, int relu,
+                              int y_layout, void* stream);                                                                              /* ban.py:55-64 */
+int hdn_bn_relu_train_bwd_f32(const float* dy, const float* c, const float* gamma, const float* beta, const float* stats, float* dc_or_null,
+                              float* dgamma_or_null, float* dbeta_or_null, void* ws, long long ws_bytes, int B, int P, int C, int relu, int dy_layout,
+                              void* stream);                                                                                            /* ban.py:55-64 */
+
+/*
  * First stage of the similarity branch's ResNet-50 in one launch (simi_stem.hip; an addition to ABI 10):
  *   out[B,Sp,Sp,64] = maxpool3x3/s2/p1( relu( conv7x7 / s2 / p0 (x[B,3,S,S], w[64][3][7][7]) + bias[co] ) ),  Sc = (S - 7) / 2 + 1,  Sp = (Sc - 1) / 2 + 1,
  * x NCHW fp32, out channels-last fp32 (255 -> 125 -> 63, 127 -> 61 -> 31).  Square inputs with 7 <= S <= 255: S < 7, B <= 0 or act_domain != 0 (the
